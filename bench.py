@@ -17,6 +17,12 @@ decodes its own contiguous range of global codewords (weak scaling, no
 data-path collective); the barrier, the max-over-ranks time and the error
 counters use torch.distributed (RCCL on the node).
 
+A plain run sets up, warms up, times the steps and prints the headline figure.
+`--full` adds everything else (decode-kernel time with roofline and HBM
+figures, error counters, host API timings, CPU baseline, parity spot check);
+`--dump-outputs DIR` writes the bits of the last timed step for comparison
+between builds.
+
 Prints ONE JSON line on rank 0.
 """
 import argparse
@@ -36,6 +42,7 @@ sys.path.insert(0, ROOT)
 VALU_PEAK = 256 * 4 * 32 * 2.4e9     # lane-ops/s: 256 CU x 4 SIMD-32 x 2.4 GHz, a wave64 per 2 cycles (MI355X_MICROARCH.md)
 HBM_PEAK = 8.0e12                    # B/s (spec)
 SEED = 12345
+DUMP_BYTES = 48 << 20                # --dump-outputs writes at most this much
 
 
 def log(*a):
@@ -53,8 +60,17 @@ def parse():
     ap.add_argument("--n", type=int, default=752)
     ap.add_argument("--rate", default="1/3")
     ap.add_argument("--algo", default="max-log")
-    ap.add_argument("--cpu-seconds", type=float, default=12.0)
-    ap.add_argument("--no-cpu", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also report what the headline figure does not need: the decode "
+                    "kernel's launch time (HIP events) with its VALU roofline and HBM figures, the error counters, "
+                    "and on one GPU the host-pointer API timings, the CPU baseline and the parity spot check "
+                    "against the oracle (the last three unless --no-cpu)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last timed step computed to DIR/bits.npy (float32): "
+                    "rank 0's decoded bits [B, 2N], or a fixed seeded sample of its rows (ascending) when all of "
+                    f"them would exceed {DUMP_BYTES >> 20} MiB")
+    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="with --full: length of the CPU baseline sample")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the host API, CPU baseline and parity legs")
     ap.add_argument("--fused", action="store_true", help="one launch (k_turbo_decode_syms, demap inside the "
                     "decoder waves) instead of k_demap_planes + k_turbo_decode (A/B; measured slower)")
     ap.add_argument("--overlap", action=argparse.BooleanOptionalAction, default=False,
@@ -265,6 +281,20 @@ def host_api(codec, llr_rows, hb, dev):
     return res
 
 
+def dump_outputs(dirname, bits):
+    """--dump-outputs: the bits of the last timed step as DIR/bits.npy (float32).
+    All rows when they fit in DUMP_BYTES, else a sample of rows drawn once from
+    SEED (ascending), the same rows in every run with the same arguments."""
+    import torch
+    B, k = bits.shape
+    rows = DUMP_BYTES // (4 * k)
+    if B > rows:
+        idx = np.sort(np.random.default_rng(SEED).choice(B, size=rows, replace=False))
+        bits = bits[torch.from_numpy(idx).to(bits.device)]
+    os.makedirs(dirname, exist_ok=True)
+    np.save(os.path.join(dirname, "bits.npy"), bits.cpu().numpy().astype(np.float32))
+
+
 def main():
     args = parse()
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
@@ -323,7 +353,9 @@ def main():
         torch.cuda.synchronize()
         log(f"[rank {rank}] warmup {i + 1}/{args.warmup}")
 
-    evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(args.steps)]
+    # --full: events around the decode launch of every timed step (its kernel time, for the roofline)
+    evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) if args.full else None
+           for _ in range(args.steps)]
     if dist:
         tdist.barrier()
     torch.cuda.synchronize()
@@ -334,33 +366,31 @@ def main():
     if dist:
         tdist.barrier()
     elapsed = time.perf_counter() - t_start
-    # k_turbo_decode launch duration: events recorded on the stream the kernel runs on
-    dec_ms = float(np.mean([a.elapsed_time(b) for a, b in evs]))
-    log(f"[rank {rank}] timed {args.steps} steps in {elapsed:.3f}s, decode kernel {dec_ms:.2f} ms/launch")
+    log(f"[rank {rank}] timed {args.steps} steps in {elapsed:.3f}s")
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, bits)
 
-    # error counters (not timed): info-bit errors, frame errors, codewords, against the generator's bits
-    errs = count_errors(codec, bits, SEED, cw0=cw0)
     red_dev = device if (not dist or args.dist_backend == "nccl") else torch.device("cpu")
-    cnt = torch.tensor([int(errs.sum(dtype=torch.int64)), int((errs > 0).sum()), B], dtype=torch.int64,
-                       device=red_dev)
     tmax = torch.tensor([elapsed], dtype=torch.float64, device=red_dev)
-    dmax = torch.tensor([dec_ms], dtype=torch.float64, device=red_dev)
-    Sh.reduce_counters(cnt, tdist)
     Sh.reduce_max(tmax, tdist)
-    Sh.reduce_max(dmax, tdist)
     elapsed = float(tmax)
     total_cw = B * world * args.steps
     value = total_cw / elapsed
+    if args.full:
+        # k_turbo_decode launch duration: events recorded on the stream the kernel runs on
+        dec_ms = float(np.mean([a.elapsed_time(b) for a, b in evs]))
+        log(f"[rank {rank}] decode kernel {dec_ms:.2f} ms/launch")
+        # error counters (not timed): info-bit errors, frame errors, codewords, against the generator's bits
+        errs = count_errors(codec, bits, SEED, cw0=cw0)
+        cnt = torch.tensor([int(errs.sum(dtype=torch.int64)), int((errs > 0).sum()), B], dtype=torch.int64,
+                           device=red_dev)
+        dmax = torch.tensor([dec_ms], dtype=torch.float64, device=red_dev)
+        Sh.reduce_counters(cnt, tdist)
+        Sh.reduce_max(dmax, tdist)
 
     if rank == 0:
         wl = (f"{args.mod} soft-LLR demap + DVB-RCS2 turbo N={args.n} couples ({2 * args.n} info bits) "
               f"r={args.rate}, 8 it {args.algo}-MAP")
-        kname = "k_turbo_decode_logmap" if codec.algo else "k_turbo_decode"
-        ops = 2 * codec.iterations * codec.N * 768            # SURVEY §8(d) lane-op count per codeword
-        valu_achieved = B * ops / (dec_ms * 1e-3)              # per GPU: this rank's launch
-        alg_bytes = B * (4 * codec.n_coded + 4 * codec.k_info)  # f32 LLRs in + int32 bits out per codeword
-        tr, why = measured_traffic(wl, kname)
-        traffic = tr["hbm_bytes_per_codeword"] * B if tr else None
         out = {
             "metric": "codewords/sec + info-bits/sec, N=1504 r=1/3 8-iter max-log-MAP @1/2/4/8 GPU",
             "value": value,
@@ -378,31 +408,40 @@ def main():
                     f"{args.mod} -> AWGN)",
             "config": {"workload": wl, "codewords_per_gpu_per_step": B, "ebn0_db": args.ebn0,
                        "parallelism": f"codeword shards x{world}"},
-            "roofline": {
-                "bound": "valu", "kernel": kname,
-                "achieved": valu_achieved / 1e12, "peak": VALU_PEAK / 1e12, "unit": "T lane-op/s",
-                "frac": valu_achieved / VALU_PEAK,
-                "traffic": traffic,
-                "note": "SURVEY §8(d): the recursions are VALU issue work, W = 2*I*N*768 f32 lane-ops per codeword "
-                        f"({ops}); achieved = W x codewords per launch / k_turbo_decode launch time (HIP events "
-                        "on its stream); peak = 256 CU x 4 SIMD-32 x 2.4 GHz (a wave64 VALU op per 2 cycles). "
-                        "traffic = rocprof-measured HBM bytes per launch (profiles/traffic.json, used only when "
-                        "stamped with the sha256 of the loaded libtdec.so)",
-            },
-            "hbm": {
-                "algorithmic_GBps": alg_bytes / (dec_ms * 1e-3) / 1e9, "peak_GBps": HBM_PEAK / 1e9,
-                "algorithmic_frac": alg_bytes / (dec_ms * 1e-3) / HBM_PEAK,
-                "algorithmic_bytes_per_codeword": alg_bytes / B,
-                "measured_bytes_per_codeword": tr["hbm_bytes_per_codeword"] if tr else None,
-                "measured_GBps": (traffic / (dec_ms * 1e-3) / 1e9) if traffic else None,
-                "measured_source": tr.get("source") if tr else why,
-            },
-            "decode_kernel_ms": dec_ms,
-            "decode_kernel_ms_max_over_ranks": float(dmax),
-            "ber": {"bit_errors": int(cnt[0]), "frame_errors": int(cnt[1]), "codewords": int(cnt[2]),
-                    "info_ber": int(cnt[0]) / (int(cnt[2]) * codec.k_info)},
         }
-        if world == 1 and not args.no_cpu:
+        if args.full:
+            kname = "k_turbo_decode_logmap" if codec.algo else "k_turbo_decode"
+            ops = 2 * codec.iterations * codec.N * 768            # SURVEY §8(d) lane-op count per codeword
+            valu_achieved = B * ops / (dec_ms * 1e-3)              # per GPU: this rank's launch
+            alg_bytes = B * (4 * codec.n_coded + 4 * codec.k_info)  # f32 LLRs in + int32 bits out per codeword
+            tr, why = measured_traffic(wl, kname)
+            traffic = tr["hbm_bytes_per_codeword"] * B if tr else None
+            out.update({
+                "roofline": {
+                    "bound": "valu", "kernel": kname,
+                    "achieved": valu_achieved / 1e12, "peak": VALU_PEAK / 1e12, "unit": "T lane-op/s",
+                    "frac": valu_achieved / VALU_PEAK,
+                    "traffic": traffic,
+                    "note": "SURVEY §8(d): the recursions are VALU issue work, W = 2*I*N*768 f32 lane-ops per codeword "
+                            f"({ops}); achieved = W x codewords per launch / k_turbo_decode launch time (HIP events "
+                            "on its stream); peak = 256 CU x 4 SIMD-32 x 2.4 GHz (a wave64 VALU op per 2 cycles). "
+                            "traffic = rocprof-measured HBM bytes per launch (profiles/traffic.json, used only when "
+                            "stamped with the sha256 of the loaded libtdec.so)",
+                },
+                "hbm": {
+                    "algorithmic_GBps": alg_bytes / (dec_ms * 1e-3) / 1e9, "peak_GBps": HBM_PEAK / 1e9,
+                    "algorithmic_frac": alg_bytes / (dec_ms * 1e-3) / HBM_PEAK,
+                    "algorithmic_bytes_per_codeword": alg_bytes / B,
+                    "measured_bytes_per_codeword": tr["hbm_bytes_per_codeword"] if tr else None,
+                    "measured_GBps": (traffic / (dec_ms * 1e-3) / 1e9) if traffic else None,
+                    "measured_source": tr.get("source") if tr else why,
+                },
+                "decode_kernel_ms": dec_ms,
+                "decode_kernel_ms_max_over_ranks": float(dmax),
+                "ber": {"bit_errors": int(cnt[0]), "frame_errors": int(cnt[1]), "codewords": int(cnt[2]),
+                        "info_ber": int(cnt[0]) / (int(cnt[2]) * codec.k_info)},
+            })
+        if args.full and world == 1 and not args.no_cpu:
             syms_host = syms[:min(B, 80000)].cpu().numpy()
             from oracle import oracle as O
             llr_rows = np.stack([-O.demap(s, cons, bps, nve, div_f32=div32)[:codec.n_coded]

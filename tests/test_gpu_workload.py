@@ -119,7 +119,7 @@ def _run(cmd, timeout=240):
 
 
 def test_bench_spawns_ranks_and_matches_single_rank_counters():
-    common = ["--steps", "1", "--warmup", "1", "--no-cpu", "--n", "212", "--mod", "QPSK", "--ebn0", "1.0"]
+    common = ["--steps", "1", "--warmup", "1", "--full", "--no-cpu", "--n", "212", "--mod", "QPSK", "--ebn0", "1.0"]
     two = json.loads(_run([sys.executable, "bench.py", "--gpus", "2", "--all-on-device0", "--dist-backend", "gloo",
                            "--batch", "4096", *common]).strip().splitlines()[-1])
     one = json.loads(_run([sys.executable, "bench.py", "--gpus", "1", "--batch", "8192", *common])
@@ -135,7 +135,7 @@ def test_bench_rccl_path_single_rank_under_torchrun():
     max time) on the one GPU a test box has: one rank with --dist-always.  Counters
     equal the plain single-process run's."""
     # (no "--n": torchrun's own parser takes it for an abbreviation of its options)
-    common = ["--steps", "1", "--warmup", "1", "--no-cpu", "--mod", "QPSK", "--ebn0", "1.0", "--batch", "8192"]
+    common = ["--steps", "1", "--warmup", "1", "--full", "--no-cpu", "--mod", "QPSK", "--ebn0", "1.0", "--batch", "8192"]
     port = str(28500 + os.getpid() % 1000)
     rccl = json.loads(_run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1",
                             "--master-addr", "127.0.0.1", "--master-port", port, "bench.py", "--gpus", "1",

@@ -11,11 +11,12 @@ for what in "$@"; do
     c3) ./tools/prof_config.sh ${T}_c3 --mod 8PSK --rate 1/2 --algo log-map --batch 1048576 --steps 3 --warmup 1 || exit $? ;;
     c4) ./tools/prof_config.sh ${T}_c4 --mod 256QAM --batch 1048576 --steps 3 --warmup 1 || exit $? ;;
     sweep)
-      mkdir -p gpurun_out/${T}_sweep
+      S=${PROF_OUT:-prof_out}/${T}_sweep
+      mkdir -p $S
       for il in reference valid-perm; do
         timeout -k 10 600 python -u -m modulations_amd.ber --mod 256QAM --n 752 --rate 1/3 --ebn0=-2:10:1 \
-          --codewords 10000000 --batch 1048576 --interleaver $il --out gpurun_out/${T}_sweep/c4_${il}.json \
-          > gpurun_out/${T}_sweep/c4_${il}.log 2>&1 || exit $?
+          --codewords 10000000 --batch 1048576 --interleaver $il --out $S/c4_${il}.json \
+          > $S/c4_${il}.log 2>&1 || exit $?
       done ;;
   esac
 done

@@ -7,7 +7,7 @@ WRITE_SIZE come from separate --pmc passes, are in KiB, and on gfx950 FETCH_SIZE
 reads exactly half the bytes of a wide coalesced streaming read, so
 hbm_bytes = 2 * FETCH_SIZE * 1024 + WRITE_SIZE * 1024.
 
-usage: tools/prof_summary.py gpurun_out/r01 profiles/r01 [batch] [workload string: stamp profiles/traffic.json]
+usage: tools/prof_summary.py prof_out/r01 profiles/r01 [batch] [workload string: stamp profiles/traffic.json]
 """
 import collections
 import csv

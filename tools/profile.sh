@@ -1,10 +1,10 @@
 #!/bin/bash
 # Kernel trace + PMC passes (separate runs, as MI355X_MICROARCH.md prescribes) of one command.
-#   tools/profile.sh <outdir under gpurun_out> <command...>
-# then: python tools/prof_summary.py gpurun_out/<outdir> profiles/<name> <codewords per launch>
+#   tools/profile.sh <outdir under ${PROF_OUT:-prof_out}> <command...>
+# then: python tools/prof_summary.py ${PROF_OUT:-prof_out}/<outdir> profiles/<name> <codewords per launch>
 set -euo pipefail
 cd /tmp && export TMPDIR=/tmp && cd - > /dev/null
-OUT=gpurun_out/$1
+OUT=${PROF_OUT:-prof_out}/$1
 shift
 P="timeout -k 10 300 rocprofv3"
 $P --kernel-trace --stats -d $OUT/kt -o kt --output-format csv -- "$@"
