@@ -100,6 +100,75 @@ int mdm_iq_quantize(int device, const void *sig, int sig_f64, long n, int8_t *iq
 int mdm_iq_dequantize_dev(int device, const uint8_t *d_raw, long n_pairs, float *d_sig, void *stream);
 int mdm_iq_dequantize(int device, const uint8_t *raw, long n_pairs, float *sig);
 
+/* ---- Burst-receive chain (SDRModem._process_received, sdr_modem.py:523-664) -------------
+ * Four steps that turn a captured IQ file into symbols.  Complex128 arrays are
+ * interleaved f64 pairs; small device results are 16-byte records. */
+
+/* _correct_freq (sdr_modem.py:282-285): out[i] = (sig[i] - dc) * (cos th, sin th),
+ * th = w * ((i0 + i) / fs), an f64 division on the device; i0: index of sig[0]
+ * in the capture (0 for a whole one, so a long capture can be mixed in pieces).  w: the f64 the
+ * reference forms, the imaginary part of -1j*2*np.pi*f_offset (host).  sig:
+ * complex64 or complex128 (sig_f64); out: complex128, numpy's complex product.
+ * dc (host, 2 doubles, nullable): the mean that _process_received :529 removes
+ * first, subtracted in the signal's precision. */
+int mdm_mix_dev(int device, const void *d_sig, int sig_f64, long n, long i0, const double *dc, double w, double fs,
+                double *d_out, void *stream);
+int mdm_mix(int device, const void *sig, int sig_f64, long n, long i0, const double *dc, double w, double fs,
+            double *out);
+
+/* Power detection (sdr_modem.py:528-546): rx = sig - dc, power = |rx|^2 (in the
+ * signal's precision), smooth = np.convolve(power, ones(win)/win, 'same') in
+ * f64 (1 <= win <= 1024, n >= win), threshold = 0.3 * max(smooth), burst_start =
+ * the first i < n - preamble_len whose next preamble_len/2 flags smooth >
+ * threshold are all set, else -1.  dc (host, 2 doubles, nullable = 0): the
+ * HOST computes np.mean(sig) with numpy (in the signal's precision) and passes
+ * it in; the device does not form the mean.  Three launches (smooth + max;
+ * flags + per-tile runs; scan), no host round trip.  smooth is a difference
+ * of blocked prefix sums: within 32 eps (1024 + win) / win max(power).
+ * d_result: 16 device bytes = int64 burst_start, f64 max(smooth).
+ * d_scratch: 16 * ceil(n / 1024) device bytes.  d_smooth: nullable, n f64. */
+int mdm_burst_find_dev(int device, const void *d_sig, int sig_f64, long n, const double *dc, int win,
+                       long preamble_len, double *d_smooth, void *d_result, void *d_scratch, void *stream);
+int mdm_burst_find(int device, const void *sig, int sig_f64, long n, const double *dc, int win, long preamble_len,
+                   long long *burst_start, double *max_power, double *smooth);
+
+/* Sync search (sdr_modem.py:568-579): corr[i] = | sum_k region[i + k] * conj(w[k]) |,
+ * i < n_region - n_w + 1 (np.abs(scipy.signal.correlate(region, w, 'valid'))),
+ * its first maximum (np.argmax) and that value.  region, w: complex128 (w in
+ * DEVICE memory for the _dev form), 1 <= n_w <= 1024, n_region >= n_w.
+ * f64 fma accumulation in ascending k.  corr: nullable (only the peak leaves
+ * the device).  d_result: 16 device bytes = f64 peak, int64 argmax.
+ * d_scratch: 16 * ceil((n_region - n_w + 1) / 1024) device bytes. */
+int mdm_xcorr_peak_dev(int device, const double *d_region, long n_region, const double *d_w, int n_w, double *d_corr,
+                       void *d_result, void *d_scratch, void *stream);
+int mdm_xcorr_peak(int device, const double *region, long n_region, const double *w, int n_w, double *corr,
+                   long long *argmax, double *peak);
+
+/* Phase detectors of the carrier loops. */
+enum {
+    MDM_CR_BPSK = 0, /* err = imag * sign(real): _carrier_recovery_bpsk :296, _carrier_recovery_data :314 */
+    MDM_CR_QUAD = 1, /* err = sign(re)*im - sign(im)*re: QPSK and the QAMs, :316                          */
+    MDM_CR_PSK8 = 2  /* err = sin(p - round(p / (pi/4)) * (pi/4)), p = angle: :318-320                     */
+};
+
+/* Both carrier loops (sdr_modem.py:287-325), batched: n_cand independent
+ * streams syms[n_cand][n] (complex128), per stream init phase / freq, alpha
+ * and detector kind.  Per step, in f64 and the reference's operation order:
+ * out[i] = s[i] * exp(-j phase); freq += (alpha*0.1) * err; phase += alpha*err + freq
+ * (np.sign(0) = 0, np.round half to even).  out: [n_cand][n] complex128;
+ * final: [n_cand][2] = phase, freq after the last step (what
+ * _carrier_recovery_bpsk returns).  All arrays of the _dev form are DEVICE
+ * memory; it cannot read the kinds, so an unknown kind there yields NaNs,
+ * while mdm_carrier returns MDM_EINVAL.
+ * This kernel is LATENCY-BOUND: one lane per stream, sequential in i, a sincos
+ * (8PSK: also an atan2 and a sin) on every step's critical path.  It exists to
+ * keep the chain on the device and to run many candidates or bursts at once
+ * (sps offsets x 2 sync rotations x bursts), not to win on a single stream. */
+int mdm_carrier_dev(int device, const double *d_syms, int n_cand, long n, const double *d_phase, const double *d_freq,
+                    const double *d_alpha, const int32_t *d_kind, double *d_out, double *d_final, void *stream);
+int mdm_carrier(int device, const double *syms, int n_cand, long n, const double *phase, const double *freq,
+                const double *alpha, const int32_t *kind, double *out, double *final_state);
+
 const char *mdm_last_error(void);
 
 #ifdef __cplusplus

@@ -166,6 +166,8 @@ MDM_ENAN = -8
 MODEM_EXPORTS = (
     "mdm_map_dev", "mdm_map", "mdm_demod_dev", "mdm_demod", "mdm_fir_dev", "mdm_fir",
     "mdm_iq_quantize_dev", "mdm_iq_quantize", "mdm_iq_dequantize_dev", "mdm_iq_dequantize", "mdm_last_error",
+    "mdm_mix_dev", "mdm_mix", "mdm_burst_find_dev", "mdm_burst_find", "mdm_xcorr_peak_dev", "mdm_xcorr_peak",
+    "mdm_carrier_dev", "mdm_carrier",
 )
 _mlib = None
 
@@ -182,6 +184,14 @@ def _declare_modem(L):
     L.mdm_iq_quantize.argtypes = [i, _vp, i, l, _vp]
     L.mdm_iq_dequantize_dev.argtypes = [i, _vp, l, _vp, _vp]
     L.mdm_iq_dequantize.argtypes = [i, _vp, l, _vp]
+    L.mdm_mix_dev.argtypes = [i, _vp, i, l, l, _vp, d, d, _vp, _vp]
+    L.mdm_mix.argtypes = [i, _vp, i, l, l, _vp, d, d, _vp]
+    L.mdm_burst_find_dev.argtypes = [i, _vp, i, l, _vp, i, l, _vp, _vp, _vp, _vp]
+    L.mdm_burst_find.argtypes = [i, _vp, i, l, _vp, i, l, _vp, _vp, _vp]
+    L.mdm_xcorr_peak_dev.argtypes = [i, _vp, l, _vp, i, _vp, _vp, _vp, _vp]
+    L.mdm_xcorr_peak.argtypes = [i, _vp, l, _vp, i, _vp, _vp, _vp]
+    L.mdm_carrier_dev.argtypes = [i, _vp, i, l, _vp, _vp, _vp, _vp, _vp, _vp, _vp]
+    L.mdm_carrier.argtypes = [i, _vp, i, l, _vp, _vp, _vp, _vp, _vp, _vp]
     for name in MODEM_EXPORTS:
         getattr(L, name).restype = C.c_int
     L.mdm_last_error.argtypes = []

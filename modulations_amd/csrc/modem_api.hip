@@ -61,7 +61,7 @@ int launch_check(const char *what) {
 
 // Host staging: device buffers + private stream, freed on scope exit.
 struct Stage {
-    void *p[3] = {nullptr, nullptr, nullptr};
+    void *p[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     hipStream_t st = nullptr;
     int init() {
         HIPCHK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
@@ -361,6 +361,183 @@ int mdm_iq_dequantize(int device, const uint8_t *raw, long n_pairs, float *sig) 
     if ((rc = s.init()) || (rc = s.alloc(0, ib)) || (rc = s.alloc(1, ob)) || (rc = s.h2d(0, raw, ib))) return rc;
     if ((rc = mdm_iq_dequantize_dev(device, (const uint8_t *)s.p[0], n_pairs, (float *)s.p[1], s.st))) return rc;
     if ((rc = s.d2h(sig, 1, ob))) return rc;
+    return s.sync();
+}
+
+// ---------------------------------------------------------------- receive chain: mixer -----
+int mdm_mix_dev(int device, const void *d_sig, int sig_f64, long n, long i0, const double *dc, double w, double fs,
+                double *d_out, void *stream) {
+    if (n < 0) return fail(MDM_EINVAL, "negative sample count");
+    if (n == 0) return 0;
+    if (!d_sig || !d_out) return fail(MDM_EINVAL, "null buffer");
+    Guard g(device);
+    hipStream_t st = (hipStream_t)stream;
+    const double dr = dc ? dc[0] : 0.0, di = dc ? dc[1] : 0.0;
+    if (sig_f64)
+        hipLaunchKernelGGL((k_mix<double>), grid_for(n), dim3(BLOCK), 0, st, (const double2 *)d_sig, n, i0, dc ? 1 : 0,
+                           dr, di, w, fs, (double2 *)d_out);
+    else
+        hipLaunchKernelGGL((k_mix<float>), grid_for(n), dim3(BLOCK), 0, st, (const float2 *)d_sig, n, i0,
+                           dc ? 1 : 0, (float)dr, (float)di, w, fs, (double2 *)d_out);
+    return launch_check("k_mix");
+}
+
+int mdm_mix(int device, const void *sig, int sig_f64, long n, long i0, const double *dc, double w, double fs,
+            double *out) {
+    if (n < 0) return fail(MDM_EINVAL, "negative sample count");
+    if (n == 0) return 0;
+    if (!sig || !out) return fail(MDM_EINVAL, "null buffer");
+    Guard g(device);
+    const size_t ib = (size_t)n * (sig_f64 ? 16 : 8), ob = (size_t)n * 16;
+    Stage s;
+    int rc;
+    if ((rc = s.init()) || (rc = s.alloc(0, ib)) || (rc = s.alloc(1, ob)) || (rc = s.h2d(0, sig, ib))) return rc;
+    if ((rc = mdm_mix_dev(device, s.p[0], sig_f64, n, i0, dc, w, fs, (double *)s.p[1], s.st))) return rc;
+    if ((rc = s.d2h(out, 1, ob))) return rc;
+    return s.sync();
+}
+
+// ---------------------------------------------------------------- receive chain: burst ------
+static int burst_args(long n, int win, long preamble_len) {
+    if (win < 1 || win > BF_WIN_MAX) return fail(MDM_EINVAL, "smoothing window must be 1..1024 samples");
+    if (n < win) return fail(MDM_EINVAL, "capture shorter than the smoothing window");
+    if (preamble_len < 0) return fail(MDM_EINVAL, "negative preamble length");
+    if ((n + BF_TILE - 1) / BF_TILE > 0x7fffffffL) return fail(MDM_EINVAL, "capture too long");
+    return 0;
+}
+
+int mdm_burst_find_dev(int device, const void *d_sig, int sig_f64, long n, const double *dc, int win,
+                       long preamble_len, double *d_smooth, void *d_result, void *d_scratch, void *stream) {
+    if (int rc = burst_args(n, win, preamble_len)) return rc;
+    if (!d_sig || !d_result || !d_scratch) return fail(MDM_EINVAL, "null buffer");
+    Guard g(device);
+    hipStream_t st = (hipStream_t)stream;
+    const long tiles = (n + BF_TILE - 1) / BF_TILE, half = preamble_len / 2;
+    const double dr = dc ? dc[0] : 0.0, di = dc ? dc[1] : 0.0;
+    long long *res = (long long *)d_result;
+    unsigned long long *mx = (unsigned long long *)d_result + 1;
+    int4 *tl = (int4 *)d_scratch;
+    HIPCHK(hipMemsetAsync(d_result, 0, 16, st));
+    const dim3 grid((unsigned)tiles);
+    if (sig_f64) {
+        hipLaunchKernelGGL((k_bf_smooth<double>), grid, dim3(BLOCK), 0, st, (const double2 *)d_sig, n, dr, di, win,
+                           d_smooth, mx);
+        hipLaunchKernelGGL((k_bf_flags<double>), grid, dim3(BLOCK), 0, st, (const double2 *)d_sig, n, dr, di, win,
+                           half, mx, tl);
+    } else {
+        hipLaunchKernelGGL((k_bf_smooth<float>), grid, dim3(BLOCK), 0, st, (const float2 *)d_sig, n, (float)dr,
+                           (float)di, win, d_smooth, mx);
+        hipLaunchKernelGGL((k_bf_flags<float>), grid, dim3(BLOCK), 0, st, (const float2 *)d_sig, n, (float)dr,
+                           (float)di, win, half, mx, tl);
+    }
+    hipLaunchKernelGGL(k_bf_scan, dim3(1), dim3(BLOCK), 0, st, tl, tiles, n, preamble_len, half, res);
+    return launch_check("k_bf_scan");
+}
+
+int mdm_burst_find(int device, const void *sig, int sig_f64, long n, const double *dc, int win, long preamble_len,
+                   long long *burst_start, double *max_power, double *smooth) {
+    if (int rc = burst_args(n, win, preamble_len)) return rc;
+    if (!sig || !burst_start) return fail(MDM_EINVAL, "null buffer");
+    Guard g(device);
+    const size_t ib = (size_t)n * (sig_f64 ? 16 : 8), sb = (size_t)n * 8;
+    const size_t tb = (size_t)((n + BF_TILE - 1) / BF_TILE) * 16;
+    Stage s;
+    int rc;
+    if ((rc = s.init()) || (rc = s.alloc(0, ib)) || (rc = s.alloc(1, 16)) || (rc = s.alloc(2, tb)) ||
+        (smooth && (rc = s.alloc(3, sb))) || (rc = s.h2d(0, sig, ib)))
+        return rc;
+    if ((rc = mdm_burst_find_dev(device, s.p[0], sig_f64, n, dc, win, preamble_len, (double *)s.p[3], s.p[1], s.p[2],
+                                 s.st)))
+        return rc;
+    long long r[2];
+    if ((rc = s.d2h(r, 1, 16)) || (smooth && (rc = s.d2h(smooth, 3, sb))) || (rc = s.sync())) return rc;
+    *burst_start = r[0];
+    if (max_power) std::memcpy(max_power, &r[1], 8);
+    return 0;
+}
+
+// ---------------------------------------------------------------- receive chain: sync search --
+static int xcorr_args(long n_region, int n_w) {
+    if (n_w < 1 || n_w > XC_NW) return fail(MDM_EINVAL, "sync waveform must have 1..1024 taps");
+    if (n_region < n_w) return fail(MDM_EINVAL, "search region shorter than the sync waveform");
+    if ((n_region - n_w + XC_OPB) / XC_OPB > 0x7fffffffL) return fail(MDM_EINVAL, "search region too long");
+    return 0;
+}
+
+int mdm_xcorr_peak_dev(int device, const double *d_region, long n_region, const double *d_w, int n_w, double *d_corr,
+                       void *d_result, void *d_scratch, void *stream) {
+    if (int rc = xcorr_args(n_region, n_w)) return rc;
+    if (!d_region || !d_w || !d_result || !d_scratch) return fail(MDM_EINVAL, "null buffer");
+    Guard g(device);
+    hipStream_t st = (hipStream_t)stream;
+    const long n_out = n_region - n_w + 1, blocks = (n_out + XC_OPB - 1) / XC_OPB;
+    hipLaunchKernelGGL(k_xcorr, dim3((unsigned)blocks), dim3(BLOCK), 0, st, (const double2 *)d_region, n_region,
+                       (const double2 *)d_w, n_w, n_out, d_corr, (XcBest *)d_scratch);
+    hipLaunchKernelGGL(k_xcorr_final, dim3(1), dim3(BLOCK), 0, st, (const XcBest *)d_scratch, blocks,
+                       (unsigned long long *)d_result);
+    return launch_check("k_xcorr");
+}
+
+int mdm_xcorr_peak(int device, const double *region, long n_region, const double *w, int n_w, double *corr,
+                   long long *argmax, double *peak) {
+    if (int rc = xcorr_args(n_region, n_w)) return rc;
+    if (!region || !w || !argmax) return fail(MDM_EINVAL, "null buffer");
+    Guard g(device);
+    const long n_out = n_region - n_w + 1;
+    const size_t rb = (size_t)n_region * 16, wb = (size_t)n_w * 16, cb = (size_t)n_out * 8;
+    const size_t pb = (size_t)((n_out + XC_OPB - 1) / XC_OPB) * 16;
+    Stage s;
+    int rc;
+    if ((rc = s.init()) || (rc = s.alloc(0, rb)) || (rc = s.alloc(1, wb)) || (rc = s.alloc(2, 16)) ||
+        (rc = s.alloc(3, pb)) || (corr && (rc = s.alloc(4, cb))) || (rc = s.h2d(0, region, rb)) ||
+        (rc = s.h2d(1, w, wb)))
+        return rc;
+    if ((rc = mdm_xcorr_peak_dev(device, (const double *)s.p[0], n_region, (const double *)s.p[1], n_w,
+                                 (double *)s.p[4], s.p[2], s.p[3], s.st)))
+        return rc;
+    long long r[2];
+    if ((rc = s.d2h(r, 2, 16)) || (corr && (rc = s.d2h(corr, 4, cb))) || (rc = s.sync())) return rc;
+    if (peak) std::memcpy(peak, &r[0], 8);
+    *argmax = r[1];
+    return 0;
+}
+
+// ---------------------------------------------------------------- receive chain: carrier ------
+int mdm_carrier_dev(int device, const double *d_syms, int n_cand, long n, const double *d_phase, const double *d_freq,
+                    const double *d_alpha, const int32_t *d_kind, double *d_out, double *d_final, void *stream) {
+    if (n_cand < 0 || n < 0) return fail(MDM_EINVAL, "negative carrier batch or length");
+    if (n_cand == 0) return 0;
+    if (!d_phase || !d_freq || !d_alpha || !d_kind || !d_final || (n && (!d_syms || !d_out)))
+        return fail(MDM_EINVAL, "null buffer");
+    Guard g(device);
+    hipLaunchKernelGGL(k_carrier, dim3((unsigned)((n_cand + CR_BLOCK - 1) / CR_BLOCK)), dim3(CR_BLOCK), 0,
+                       (hipStream_t)stream, (const double2 *)d_syms, n_cand, n, d_phase, d_freq, d_alpha, d_kind,
+                       (double2 *)d_out, d_final);
+    return launch_check("k_carrier");
+}
+
+int mdm_carrier(int device, const double *syms, int n_cand, long n, const double *phase, const double *freq,
+                const double *alpha, const int32_t *kind, double *out, double *final_state) {
+    if (n_cand < 0 || n < 0) return fail(MDM_EINVAL, "negative carrier batch or length");
+    if (n_cand == 0) return 0;
+    if (!phase || !freq || !alpha || !kind || !final_state || (n && (!syms || !out)))
+        return fail(MDM_EINVAL, "null buffer");
+    for (int c = 0; c < n_cand; ++c)
+        if (kind[c] < MDM_CR_BPSK || kind[c] > MDM_CR_PSK8) return fail(MDM_EINVAL, "unknown carrier detector kind");
+    Guard g(device);
+    const size_t sb = (size_t)n_cand * (size_t)n * 16, pb = (size_t)n_cand * 8;
+    Stage s;
+    int rc;
+    if ((rc = s.init()) || (rc = s.alloc(0, sb)) || (rc = s.alloc(1, pb)) || (rc = s.alloc(2, pb)) ||
+        (rc = s.alloc(3, pb)) || (rc = s.alloc(4, pb / 2)) || (rc = s.alloc(5, sb)) || (rc = s.alloc(6, 2 * pb)) ||
+        (rc = s.h2d(0, syms, sb)) || (rc = s.h2d(1, phase, pb)) || (rc = s.h2d(2, freq, pb)) ||
+        (rc = s.h2d(3, alpha, pb)) || (rc = s.h2d(4, kind, pb / 2)))
+        return rc;
+    if ((rc = mdm_carrier_dev(device, (const double *)s.p[0], n_cand, n, (const double *)s.p[1],
+                              (const double *)s.p[2], (const double *)s.p[3], (const int32_t *)s.p[4],
+                              (double *)s.p[5], (double *)s.p[6], s.st)))
+        return rc;
+    if ((rc = s.d2h(out, 5, sb)) || (rc = s.d2h(final_state, 6, 2 * pb))) return rc;
     return s.sync();
 }
 

@@ -410,4 +410,399 @@ __global__ __launch_bounds__(BLOCK) void k_dequantize(const uint8_t *__restrict_
         sig[i] = make_float2(deq(raw[2 * i]), deq(raw[2 * i + 1]));
 }
 
+// ======================================================================================
+// Receive chain (sdr_modem.py:282-325, 528-579): mixer, burst detector, sync correlator,
+// carrier loops.  DESIGN.md "Receive chain".
+// ======================================================================================
+
+// non-negative f64 (or NaN) -> bits that order like the values, a NaN above +inf
+__device__ __forceinline__ unsigned long long ord_bits(double v) {
+    return (unsigned long long)__double_as_longlong(v) & 0x7fffffffffffffffULL;
+}
+
+// ---- _correct_freq (:282-285): out[i] = (sig[i] - dc) * exp(j * w * ((i0 + i) / fs)) -----------
+// np.exp of (+-0 + j theta) is (cos theta, sin theta); the product is numpy's complex128 one.
+template <typename T>
+__global__ __launch_bounds__(BLOCK) void k_mix(const typename C2<T>::t *__restrict__ sig, long n, long i0, int has_dc,
+                                               T dcr, T dci, double w, double fs, double2 *__restrict__ out) {
+    for (long i = gtid(); i < n; i += gstride()) {
+        T re = sig[i].x, im = sig[i].y;
+        if (has_dc) {
+            re = re - dcr;
+            im = im - dci;
+        }
+        const double th = w * ((double)(i0 + i) / fs);
+        double sn, cs, pr, pi;
+        sincos(th, &sn, &cs);
+        npm::cmul_np<double>((double)re, (double)im, cs, sn, pr, pi);
+        out[i] = make_double2(pr, pi);
+    }
+}
+
+// ---- power detection (:528-546) -------------------------------------------------------------
+// One workgroup = BF_TILE consecutive outputs of np.convolve(power, ones(win)/win, 'same'):
+//   smooth[i] = (1/win) * sum_{m = i - win/2}^{i - win/2 + win - 1} power[m]   (0 outside [0, n)).
+// The tile's window (BF_TILE + win - 1 <= 2047 samples) is summed into an exclusive prefix
+// array in LDS (8 consecutive samples per thread, wave scan, cross-wave carry); an output is
+// the difference of two prefix values.  Rounding: a prefix value carries <= ~20 eps of the
+// window's sum (<= 2047 max(power)), so after the 1/win an output is within ~50 eps
+// max(power) of the exact mean -- the reference's own dot product is no closer.
+constexpr int BF_TILE = 1024;
+constexpr int BF_WIN_MAX = 1024;
+constexpr int BF_PER = (BF_TILE + BF_WIN_MAX) / BLOCK;   // window samples per thread (8)
+
+template <typename T>
+__device__ __forceinline__ double bf_power(const typename C2<T>::t *__restrict__ sig, long m, long n, T dcr, T dci) {
+    if (m < 0 || m >= n) return 0.0;
+    const typename C2<T>::t v = sig[m];
+    const T a = npm::cabs_np<T>(v.x - dcr, v.y - dci);   // np.abs(rx) in the signal's precision
+    return (double)(a * a);                              // ** 2, then convolve's float64
+}
+
+// fills P[q] = sum of the window's first q samples, q <= BF_TILE + win - 1 (window sample q is
+// power[i0 - win/2 + q]); ends with a barrier
+template <typename T>
+__device__ __forceinline__ void bf_prefix(const typename C2<T>::t *__restrict__ sig, long n, T dcr, T dci, int win,
+                                          long i0, double *P, double *wsum) {
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const long m0 = i0 - win / 2 + (long)t * BF_PER;
+    const int span = BF_TILE + win - 1;
+    double e[BF_PER], s = 0.0;
+#pragma unroll
+    for (int j = 0; j < BF_PER; ++j) {
+        e[j] = s;
+        s += t * BF_PER + j < span ? bf_power<T>(sig, m0 + j, n, dcr, dci) : 0.0;
+    }
+    double inc = s;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const double v = __shfl_up(inc, o, 64);
+        if (lane >= o) inc += v;
+    }
+    if (lane == 63) wsum[wave] = inc;
+    __syncthreads();
+    double base = 0.0;
+    for (int k = 0; k < wave; ++k) base += wsum[k];
+    const double excl = base + (inc - s);
+#pragma unroll
+    for (int j = 0; j < BF_PER; ++j) P[t * BF_PER + j] = excl + e[j];
+    __syncthreads();
+}
+
+// launch 1: smoothed power (stored when asked for) and its maximum (bit pattern, atomicMax)
+template <typename T>
+__global__ __launch_bounds__(BLOCK) void k_bf_smooth(const typename C2<T>::t *__restrict__ sig, long n, T dcr, T dci,
+                                                     int win, double *__restrict__ smooth,
+                                                     unsigned long long *__restrict__ mx) {
+    __shared__ double P[BF_TILE + BF_WIN_MAX];
+    __shared__ double wsum[BLOCK / 64];
+    const long i0 = (long)blockIdx.x * BF_TILE;
+    bf_prefix<T>(sig, n, dcr, dci, win, i0, P, wsum);
+    const double inv = 1.0 / (double)win;
+    unsigned long long m = 0;
+    for (int j = threadIdx.x; j < BF_TILE; j += BLOCK) {
+        if (i0 + j >= n) break;
+        const double v = (P[j + win] - P[j]) * inv;
+        if (smooth) smooth[i0 + j] = v;
+        const unsigned long long b = ord_bits(v);
+        m = b > m ? b : m;
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const unsigned long long v = __shfl_xor(m, o, 64);
+        m = v > m ? v : m;
+    }
+    if ((threadIdx.x & 63) == 0 && m) atomicMax(mx, m);
+}
+
+// launch 2: flags = smooth > 0.3 * max, and per tile the first zero flag, the last zero flag
+// and the first start p+1 behind a zero at p whose next zero in the tile is >= half away
+// (int4: first, last, start, unused; tile-local, -1 = none).  Samples past n count as set.
+template <typename T>
+__global__ __launch_bounds__(BLOCK) void k_bf_flags(const typename C2<T>::t *__restrict__ sig, long n, T dcr, T dci,
+                                                    int win, long half, const unsigned long long *__restrict__ mx,
+                                                    int4 *__restrict__ tiles) {
+    __shared__ double P[BF_TILE + BF_WIN_MAX];
+    __shared__ double wsum[BLOCK / 64];
+    __shared__ int wlast[BLOCK / 64], rfirst[BLOCK / 64], rlast[BLOCK / 64], rstart[BLOCK / 64];
+    const long i0 = (long)blockIdx.x * BF_TILE;
+    bf_prefix<T>(sig, n, dcr, dci, win, i0, P, wsum);
+    const double inv = 1.0 / (double)win;
+    const double thr = __longlong_as_double((long long)*mx) * 0.3;
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    constexpr int PER = BF_TILE / BLOCK;   // 4 consecutive positions per thread
+    bool z[PER];
+    int first = BF_TILE, last = -1;
+#pragma unroll
+    for (int r = 0; r < PER; ++r) {
+        const int j = t * PER + r;
+        const double v = (P[j + win] - P[j]) * inv;
+        z[r] = i0 + j < n && !(v > thr);
+        if (z[r]) {
+            first = first < j ? first : j;
+            last = j;
+        }
+    }
+    // inclusive prefix maximum of `last` over the threads of the block
+    int inc = last;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const int v = __shfl_up(inc, o, 64);
+        if (lane >= o) inc = v > inc ? v : inc;
+    }
+    if (lane == 63) wlast[wave] = inc;
+    int prev = __shfl_up(inc, 1, 64);   // last zero before this thread's positions
+    if (lane == 0) prev = -1;
+    __syncthreads();
+    for (int k = 0; k < wave; ++k) prev = wlast[k] > prev ? wlast[k] : prev;
+    int start = BF_TILE + 1;
+#pragma unroll
+    for (int r = 0; r < PER; ++r) {
+        const int j = t * PER + r;
+        if (z[r]) {
+            if (prev >= 0 && (long)(j - prev - 1) >= half) start = start < prev + 1 ? start : prev + 1;
+            prev = j;
+        }
+    }
+    int lmax = last;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const int a = __shfl_xor(first, o, 64), b = __shfl_xor(lmax, o, 64), c = __shfl_xor(start, o, 64);
+        first = a < first ? a : first;
+        lmax = b > lmax ? b : lmax;
+        start = c < start ? c : start;
+    }
+    if (lane == 0) {
+        rfirst[wave] = first;
+        rlast[wave] = lmax;
+        rstart[wave] = start;
+    }
+    __syncthreads();
+    if (t == 0) {
+        for (int k = 1; k < BLOCK / 64; ++k) {
+            first = rfirst[k] < first ? rfirst[k] : first;
+            lmax = rlast[k] > lmax ? rlast[k] : lmax;
+            start = rstart[k] < start ? rstart[k] : start;
+        }
+        tiles[blockIdx.x] = make_int4(first < BF_TILE ? first : -1, lmax, start <= BF_TILE ? start : -1, 0);
+    }
+}
+
+// launch 3 (one workgroup): the first i < n - preamble_len whose next `half` flags are all
+// set.  Such an i is 0 or directly follows a zero flag, so it is the first p + 1 (p a zero
+// flag, or -1) whose following zero is >= half away: a prefix maximum over the tiles' last
+// zeros gives every tile the zero before it.
+__global__ __launch_bounds__(BLOCK) void k_bf_scan(const int4 *__restrict__ tiles, long n_tiles, long n, long pre,
+                                                   long half, long long *__restrict__ res) {
+    __shared__ long long sc[BLOCK];
+    __shared__ long long best[BLOCK];
+    const int t = threadIdx.x;
+    long long carry = -1, found = -1;
+    for (long c0 = 0; c0 < n_tiles; c0 += BLOCK) {
+        const long g = c0 + t;
+        int4 s = make_int4(-1, -1, -1, 0);
+        if (g < n_tiles) s = tiles[g];
+        const long long base = (long long)g * BF_TILE;
+        sc[t] = s.y >= 0 ? base + s.y : -1;
+        __syncthreads();
+        for (int o = 1; o < BLOCK; o <<= 1) {
+            const long long v = t >= o ? sc[t - o] : -1;
+            __syncthreads();
+            sc[t] = v > sc[t] ? v : sc[t];
+            __syncthreads();
+        }
+        long long prev = t ? sc[t - 1] : -1;
+        prev = carry > prev ? carry : prev;
+        long long cand = 0x7fffffffffffffffLL;
+        if (s.x >= 0) {
+            if (base + s.x - prev - 1 >= half) cand = prev + 1;
+            else if (s.z >= 0) cand = base + s.z;
+        }
+        best[t] = cand;
+        __syncthreads();
+        for (int o = BLOCK / 2; o > 0; o >>= 1) {
+            if (t < o) best[t] = best[t + o] < best[t] ? best[t + o] : best[t];
+            __syncthreads();
+        }
+        const long long b = best[0], last = sc[BLOCK - 1];
+        __syncthreads();
+        if (b != 0x7fffffffffffffffLL) {
+            found = b;
+            break;
+        }
+        carry = last > carry ? last : carry;
+    }
+    if (found < 0) found = carry + 1;   // the run behind the last zero reaches the end
+    if (t == 0) res[0] = found < n - pre ? found : -1;
+}
+
+// ---- sync search (:568-579): corr[i] = | sum_k region[i + k] * conj(w[k]) | and its argmax ----
+// One workgroup = XC_OPB = 1024 consecutive outputs, XC_T = 4 per thread.  The taps (<= 1024,
+// 16 KiB) and the window region[i0 .. i0 + 1024 + n_w - 1) (32 KiB) are staged once in LDS;
+// the window is stored phase-major (sample q at plane q % 4, slot q / 4), so the wave's read
+// of sample 4 t + c hits consecutive 16-B slots: a conflict-free ds_read_b128.  Per step of
+// four taps a thread reads 4 new samples and 4 taps (wave-uniform, broadcast) for 16 complex
+// MACs = 64 f64 FMAs: the loop is FMA-bound (the LDS is busy about half of the time).
+// Per output the terms are added in ascending k with fma, real part rr*wr then ri*wi.
+constexpr int XC_T = 4;
+constexpr int XC_OPB = BLOCK * XC_T;
+constexpr int XC_NW = 1024;
+constexpr int XC_PL = (XC_OPB + XC_NW) / 4 + 1;   // slots per plane
+
+struct XcBest {
+    unsigned long long v;   // ord_bits of the value
+    long long i;            // -1: none
+};
+__device__ __forceinline__ XcBest xc_better(XcBest a, XcBest b) {   // the larger value, the lower index on ties
+    if (b.i < 0) return a;
+    if (a.i < 0) return b;
+    if (a.v != b.v) return a.v > b.v ? a : b;
+    return a.i < b.i ? a : b;
+}
+__device__ __forceinline__ XcBest xc_block_best(XcBest m, XcBest *sh) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        XcBest q;
+        q.v = __shfl_xor(m.v, o, 64);
+        q.i = __shfl_xor(m.i, o, 64);
+        m = xc_better(m, q);
+    }
+    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = m;
+    __syncthreads();
+    for (int k = 0; k < BLOCK / 64; ++k) m = k ? xc_better(m, sh[k]) : sh[0];
+    return m;
+}
+
+__global__ __launch_bounds__(BLOCK) void k_xcorr(const double2 *__restrict__ region, long n_region,
+                                                 const double2 *__restrict__ w, int n_w, long n_out,
+                                                 double *__restrict__ corr, XcBest *__restrict__ part) {
+    __shared__ double2 ws[XC_NW];
+    __shared__ double2 xs[4 * XC_PL];
+    __shared__ XcBest sh[BLOCK / 64];
+    const int t = threadIdx.x;
+    const long i0 = (long)blockIdx.x * XC_OPB;
+    for (int i = t; i < XC_NW; i += BLOCK) ws[i] = i < n_w ? w[i] : make_double2(0.0, 0.0);
+    for (int q = t; q < 4 * XC_PL; q += BLOCK) {
+        const long m = i0 + q;
+        xs[(q & 3) * XC_PL + (q >> 2)] = m < n_region ? region[m] : make_double2(0.0, 0.0);
+    }
+    __syncthreads();
+    double ar[XC_T], ai[XC_T];
+#pragma unroll
+    for (int o = 0; o < XC_T; ++o) ar[o] = ai[o] = 0.0;
+    double2 a[7];   // samples 4 t + kk + 0..6
+    a[0] = xs[0 * XC_PL + t];
+    a[1] = xs[1 * XC_PL + t];
+    a[2] = xs[2 * XC_PL + t];
+    const int n_w4 = n_w & ~3;
+    for (int kk = 0; kk < n_w4; kk += 4) {
+        const int s = t + (kk >> 2);
+        a[3] = xs[3 * XC_PL + s];
+        a[4] = xs[0 * XC_PL + s + 1];
+        a[5] = xs[1 * XC_PL + s + 1];
+        a[6] = xs[2 * XC_PL + s + 1];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const double2 c = ws[kk + u];
+#pragma unroll
+            for (int o = 0; o < XC_T; ++o) {
+                const double2 x = a[o + u];
+                ar[o] = fma(x.x, c.x, ar[o]);
+                ar[o] = fma(x.y, c.y, ar[o]);
+                ai[o] = fma(x.y, c.x, ai[o]);
+                ai[o] = fma(-x.x, c.y, ai[o]);
+            }
+        }
+        a[0] = a[4];
+        a[1] = a[5];
+        a[2] = a[6];
+    }
+    for (int k = n_w4; k < n_w; ++k) {   // the last n_w % 4 taps
+        const double2 c = ws[k];
+#pragma unroll
+        for (int o = 0; o < XC_T; ++o) {
+            const int q = XC_T * t + o + k;
+            const double2 x = xs[(q & 3) * XC_PL + (q >> 2)];
+            ar[o] = fma(x.x, c.x, ar[o]);
+            ar[o] = fma(x.y, c.y, ar[o]);
+            ai[o] = fma(x.y, c.x, ai[o]);
+            ai[o] = fma(-x.x, c.y, ai[o]);
+        }
+    }
+    XcBest m;
+    m.v = 0;
+    m.i = -1;
+#pragma unroll
+    for (int o = 0; o < XC_T; ++o) {
+        const long i = i0 + XC_T * t + o;
+        if (i < n_out) {
+            const double v = npm::cabs_np<double>(ar[o], ai[o]);
+            if (corr) corr[i] = v;
+            XcBest q;
+            q.v = ord_bits(v);
+            q.i = i;
+            m = xc_better(m, q);
+        }
+    }
+    m = xc_block_best(m, sh);
+    if (t == 0) part[blockIdx.x] = m;
+}
+
+// second stage: res[0] = peak value (f64), res[1] = its first index (int64)
+__global__ __launch_bounds__(BLOCK) void k_xcorr_final(const XcBest *__restrict__ part, long n_part,
+                                                       unsigned long long *__restrict__ res) {
+    __shared__ XcBest sh[BLOCK / 64];
+    XcBest m;
+    m.v = 0;
+    m.i = -1;
+    for (long p = threadIdx.x; p < n_part; p += BLOCK) m = xc_better(m, part[p]);
+    m = xc_block_best(m, sh);
+    if (threadIdx.x == 0) {
+        res[0] = m.v;
+        res[1] = (unsigned long long)m.i;
+    }
+}
+
+// ---- carrier loops (:287-325): one lane per candidate stream ---------------------------------
+// Sequential in i and latency-bound (a sincos and, for 8PSK, an atan2 and a sin per symbol on
+// the critical path); the batch is what the GPU adds.  np.exp(-1j * phase) = (cos(-phase),
+// sin(-phase)); np.sign(0) = 0, np.sign(NaN) = NaN; np.round = rint.
+constexpr int CR_BLOCK = 64;
+__device__ __forceinline__ double np_sign(double x) { return x > 0.0 ? 1.0 : (x < 0.0 ? -1.0 : (x == 0.0 ? 0.0 : x)); }
+
+__global__ __launch_bounds__(CR_BLOCK) void k_carrier(const double2 *__restrict__ syms, int n_cand, long n,
+                                                      const double *__restrict__ ph0, const double *__restrict__ fr0,
+                                                      const double *__restrict__ al, const int *__restrict__ kind,
+                                                      double2 *__restrict__ out, double *__restrict__ fin) {
+    const int c = blockIdx.x * CR_BLOCK + threadIdx.x;
+    if (c >= n_cand) return;
+    double phase = ph0[c], freq = fr0[c];
+    const double alpha = al[c], beta = alpha * 0.1;
+    const int kd = kind[c];
+    const double2 *s = syms + (long)c * n;
+    double2 *o = out + (long)c * n;
+    for (long i = 0; i < n; ++i) {
+        const double2 v = s[i];
+        double sn, cs, re, im, err;
+        sincos(phase, &sn, &cs);
+        npm::cmul_np<double>(v.x, v.y, cs, -sn, re, im);
+        o[i] = make_double2(re, im);
+        if (kd == 0) {            // MDM_CR_BPSK
+            err = im * np_sign(re);
+        } else if (kd == 1) {     // MDM_CR_QUAD
+            err = np_sign(re) * im - np_sign(im) * re;
+        } else if (kd == 2) {     // MDM_CR_PSK8
+            const double ps = atan2(im, re);
+            const double nearest = rint(ps / 0.7853981633974483) * 0.7853981633974483;
+            err = sin(ps - nearest);
+        } else {
+            err = (double)NAN;    // unknown kind (the host entry points reject it)
+        }
+        freq = freq + beta * err;
+        phase = phase + (alpha * err + freq);
+    }
+    fin[2 * c] = phase;
+    fin[2 * c + 1] = freq;
+}
+
 }  // namespace mdm

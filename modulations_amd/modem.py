@@ -2,10 +2,12 @@
 mappers, hard-decision demodulators, RRC pulse shaping / matched filtering
 and int8/uint8 IQ sample format, behind the reference's own names.
 
-  SDRModem            sdr_modem.py:17-342 (the modem part: mappers, demods,
+  SDRModem            sdr_modem.py:17-385, 523-664 (mappers, demods,
                       _rrc_filter, _upsample_filter, modulate/demodulate,
-                      _save_iq/_load_iq; radio I/O, sync and carrier recovery
-                      are out of scope)
+                      _save_iq/_load_iq, build_frame and the burst-receive
+                      chain: _estimate_freq_offset, _correct_freq, both carrier
+                      loops, _process_received; the radio I/O of transmit /
+                      receive / receive_and_transmit is out of scope)
   Modulator,          modulators.py:19-199 (natural-label mappers, argmin QAM
   rrcosfilter         demods, upfirdn pulse shaping, matched filter)
   bpsk_mod ...        test_sdr_with_coding.py:25-128, 228-240 (the harness
@@ -187,6 +189,180 @@ def iq_dequantize_device(raw, out=None, stream=None):
     return out
 
 
+# ---- burst-receive chain (include/modem.h: mixer, burst detector, sync search, carrier loops) ----
+CR_BPSK, CR_QUAD, CR_PSK8 = 0, 1, 2
+XCORR_MAX_TAPS = 1024      # sync waveform taps of mdm_xcorr_peak
+BURST_MAX_WIN = 1024       # smoothing window of mdm_burst_find
+_RX_TILE = 1024            # outputs per workgroup: the scratch buffers hold 16 bytes per tile
+
+
+def _dc(dc):
+    if dc is None:
+        return None
+    z = complex(dc)
+    return np.array([z.real, z.imag], np.float64)
+
+
+def _check_burst(n, win, preamble_len):
+    if not 1 <= win <= BURST_MAX_WIN:
+        raise ValueError(f"smoothing window must be 1..{BURST_MAX_WIN} samples")
+    if n < win:
+        raise ValueError("capture shorter than the smoothing window")
+    if preamble_len < 0:
+        raise ValueError("negative preamble length")
+
+
+def _check_xcorr(n_region, n_w):
+    if not 1 <= n_w <= XCORR_MAX_TAPS:
+        raise ValueError(f"sync waveform must have 1..{XCORR_MAX_TAPS} taps")
+    if n_region < n_w:
+        raise ValueError("search region shorter than the sync waveform")
+
+
+def _carrier_params(n_cand, init_phase, init_freq, alpha, kind):
+    """Per-candidate parameter arrays; scalars apply to every candidate."""
+    out = []
+    for name, v, dt in (("init_phase", init_phase, np.float64), ("init_freq", init_freq, np.float64),
+                        ("alpha", alpha, np.float64), ("kind", kind, np.int32)):
+        a = np.asarray(v)
+        if a.ndim == 0:
+            a = np.full(n_cand, a)
+        if a.shape != (n_cand,):
+            raise ValueError(f"{name} has shape {a.shape}, expected ({n_cand},) for {n_cand} candidate streams")
+        out.append(np.ascontiguousarray(a.astype(dt)))
+    if out[3].size and not np.all((out[3] >= CR_BPSK) & (out[3] <= CR_PSK8)):
+        raise ValueError("unknown carrier detector kind")
+    return out
+
+
+def mix(sig, w, fs, dc=None, i0=0, device=0):
+    """(sig - dc) * exp(1j * w * (i0 + arange(n)) / fs), complex128 (mdm_mix, _correct_freq)."""
+    s = _syms_c(sig)
+    out = np.empty(s.size, np.complex128)
+    if s.size:
+        _n.modem_check(_n.modem_lib().mdm_mix(device, _n.ptr(s), int(s.dtype == np.complex128), s.size,
+                                              int(i0), _n.ptr(_dc(dc)), float(w), float(fs), _n.ptr(out)))
+    return out
+
+
+def burst_find(sig, preamble_len, win=1000, dc=None, want_smooth=False, device=0):
+    """(burst_start or -1, max smoothed power, smoothed power or None) of mdm_burst_find.
+    dc: np.mean(sig), formed by the caller on the host."""
+    s = _syms_c(sig)
+    _check_burst(s.size, win, preamble_len)
+    start, mx = np.zeros(1, np.int64), np.zeros(1, np.float64)
+    smooth = np.empty(s.size, np.float64) if want_smooth else None
+    _n.modem_check(_n.modem_lib().mdm_burst_find(device, _n.ptr(s), int(s.dtype == np.complex128), s.size,
+                                                 _n.ptr(_dc(dc)), int(win), int(preamble_len), _n.ptr(start),
+                                                 _n.ptr(mx), _n.ptr(smooth)))
+    return int(start[0]), float(mx[0]), smooth
+
+
+def xcorr_peak(region, wave, want_corr=False, device=0):
+    """(argmax, peak, corr or None) of |correlate(region, wave, 'valid')| (mdm_xcorr_peak)."""
+    r = np.ascontiguousarray(np.asarray(region).ravel().astype(np.complex128, copy=False))
+    h = np.ascontiguousarray(np.asarray(wave).ravel().astype(np.complex128, copy=False))
+    _check_xcorr(r.size, h.size)
+    idx, peak = np.zeros(1, np.int64), np.zeros(1, np.float64)
+    corr = np.empty(r.size - h.size + 1, np.float64) if want_corr else None
+    _n.modem_check(_n.modem_lib().mdm_xcorr_peak(device, _n.ptr(r), r.size, _n.ptr(h), h.size, _n.ptr(corr),
+                                                 _n.ptr(idx), _n.ptr(peak)))
+    return int(idx[0]), float(peak[0]), corr
+
+
+def carrier_recovery(syms, init_phase, init_freq, alpha, kind, device=0):
+    """The carrier loop over every row of syms [C, n] (complex128): (out [C, n],
+    final [C, 2] = phase, freq).  Parameters per row, or scalars (mdm_carrier)."""
+    s = np.asarray(syms)
+    if s.ndim != 2:
+        raise ValueError(f"syms has shape {s.shape}, expected (candidates, symbols)")
+    s = np.ascontiguousarray(s.astype(np.complex128, copy=False))
+    ph, fr, al, kd = _carrier_params(s.shape[0], init_phase, init_freq, alpha, kind)
+    out = np.empty(s.shape, np.complex128)
+    fin = np.empty((s.shape[0], 2), np.float64)
+    if s.shape[0]:
+        _n.modem_check(_n.modem_lib().mdm_carrier(device, _n.ptr(s), s.shape[0], s.shape[1], _n.ptr(ph), _n.ptr(fr),
+                                                  _n.ptr(al), _n.ptr(kd), _n.ptr(out), _n.ptr(fin)))
+    return out, fin
+
+
+def mix_device(sig, w, fs, dc=None, i0=0, out=None, stream=None):
+    import torch
+    if out is None:
+        out = torch.empty(sig.numel(), dtype=torch.complex128, device=sig.device)
+    _n.modem_check(_n.modem_lib().mdm_mix_dev(sig.device.index or 0, _n.ptr(sig), int(sig.dtype == torch.complex128),
+                                              sig.numel(), int(i0), _n.ptr(_dc(dc)), float(w), float(fs),
+                                              _n.ptr(out), _n.stream_ptr(stream)))
+    return out
+
+
+def _rx_scratch(n_out, scratch, device):
+    import torch
+    if scratch is None:
+        scratch = torch.empty(2 * -(-n_out // _RX_TILE), dtype=torch.int64, device=device)
+    return scratch
+
+
+def burst_find_device(sig, preamble_len, win=1000, dc=None, smooth=None, result=None, scratch=None, stream=None):
+    """Stream-ordered; returns the int64[2] result record (burst_result decodes it)."""
+    import torch
+    _check_burst(sig.numel(), win, preamble_len)
+    if result is None:
+        result = torch.empty(2, dtype=torch.int64, device=sig.device)
+    scratch = _rx_scratch(sig.numel(), scratch, sig.device)
+    _n.modem_check(_n.modem_lib().mdm_burst_find_dev(sig.device.index or 0, _n.ptr(sig),
+                                                     int(sig.dtype == torch.complex128), sig.numel(), _n.ptr(_dc(dc)),
+                                                     int(win), int(preamble_len), _n.ptr(smooth), _n.ptr(result),
+                                                     _n.ptr(scratch), _n.stream_ptr(stream)))
+    return result
+
+
+def burst_result(result):
+    """(burst_start, max smoothed power) of a burst_find_device record (synchronises)."""
+    r = result.cpu().numpy()
+    return int(r[0]), float(r[1:].view(np.float64)[0])
+
+
+def xcorr_peak_device(region, wave, corr=None, result=None, scratch=None, stream=None):
+    """Stream-ordered; returns the int64[2] result record (xcorr_result decodes it)."""
+    import torch
+    _check_xcorr(region.numel(), wave.numel())
+    if region.dtype != torch.complex128 or wave.dtype != torch.complex128:
+        raise ValueError("xcorr_peak_device takes complex128 tensors")
+    if result is None:
+        result = torch.empty(2, dtype=torch.int64, device=region.device)
+    scratch = _rx_scratch(region.numel() - wave.numel() + 1, scratch, region.device)
+    _n.modem_check(_n.modem_lib().mdm_xcorr_peak_dev(region.device.index or 0, _n.ptr(region), region.numel(),
+                                                     _n.ptr(wave), wave.numel(), _n.ptr(corr), _n.ptr(result),
+                                                     _n.ptr(scratch), _n.stream_ptr(stream)))
+    return result
+
+
+def xcorr_result(result):
+    """(argmax, peak) of an xcorr_peak_device record (synchronises)."""
+    r = result.cpu().numpy()
+    return int(r[1]), float(r[:1].view(np.float64)[0])
+
+
+def carrier_recovery_device(syms, init_phase, init_freq, alpha, kind, out=None, final=None, stream=None):
+    """syms: contiguous complex128 [C, n] on the GPU; parameters are host values
+    (scalars or [C]), uploaded here.  Returns (out [C, n], final [C, 2])."""
+    import torch
+    if syms.dim() != 2 or syms.dtype != torch.complex128 or not syms.is_contiguous():
+        raise ValueError("syms must be a contiguous complex128 tensor of shape (candidates, symbols)")
+    C, n = syms.shape
+    ph, fr, al, kd = (torch.from_numpy(a).to(syms.device) for a in _carrier_params(C, init_phase, init_freq, alpha, kind))
+    if out is None:
+        out = torch.empty((C, n), dtype=torch.complex128, device=syms.device)
+    if final is None:
+        final = torch.empty((C, 2), dtype=torch.float64, device=syms.device)
+    if C:
+        _n.modem_check(_n.modem_lib().mdm_carrier_dev(syms.device.index or 0, _n.ptr(syms), C, n, _n.ptr(ph),
+                                                      _n.ptr(fr), _n.ptr(al), _n.ptr(kd), _n.ptr(out), _n.ptr(final),
+                                                      _n.stream_ptr(stream)))
+    return out, final
+
+
 # ---------------------------------------------------------------- filter design (host) --------
 def _rrc_taps(sps, alpha=0.35, ntaps=101):
     """sdr_modem.py:77-91 / test_sdr_with_coding.py:110-123: the same scalar
@@ -334,7 +510,8 @@ MODULATIONS = {
 
 
 class SDRModem:
-    """sdr_modem.py:17-342, modem part (mapping, hard demod, RRC shaping, IQ files)."""
+    """sdr_modem.py:17-385, 523-664: mapping, hard demod, RRC shaping, IQ files,
+    frame building and the burst-receive chain."""
 
     MODULATIONS = {
         'BPSK':   {'bps': 1, 'order': 2,   'alpha': 0.02,  'n_rot': 2, 'rot_step': np.pi},
@@ -432,6 +609,163 @@ class SDRModem:
 
     def _load_iq(self, filename: str) -> np.ndarray:                                       # :337-342
         return load_iq(filename, self.device)
+
+    # ---- burst-receive chain (:270-325, 346-385, 523-664) ----
+    def _estimate_freq_offset(self, sig: np.ndarray) -> float:                             # :270-280
+        """Host numpy, exactly the reference's expressions: one <= 65 536-point FFT
+        of a preamble slice, off the hot path.  It stays on the host because an FFT
+        on the GPU cannot be made bit-stable against numpy's pocketfft, and the
+        estimate feeds every later step."""
+        N = min(len(sig), 2 ** 16)
+        sig = sig[:N]
+        win = np.hanning(N)
+        fft = np.fft.fft(sig * win)
+        freqs = np.fft.fftfreq(N, 1 / self.fs)
+        mag = np.abs(fft)
+        mag[:N // 100] = 0
+        mag[-N // 100:] = 0
+        return freqs[np.argmax(mag)]
+
+    def _correct_freq(self, sig: np.ndarray, f_offset: float) -> np.ndarray:               # :282-285
+        return mix(sig, (-1j * 2 * np.pi * f_offset).imag, self.fs, device=self.device)
+
+    def _carrier_recovery_bpsk(self, syms: np.ndarray, alpha: float = 0.03):               # :287-300
+        """(out, phase, freq).  The loop runs in complex128 / f64 whatever the
+        input's dtype (the reference's arithmetic follows a complex64 input's)."""
+        out, fin = carrier_recovery(np.asarray(syms).reshape(1, -1), 0.0, 0.0, alpha, CR_BPSK, self.device)
+        return out[0], fin[0, 0], fin[0, 1]
+
+    @staticmethod
+    def _detector(modulation):
+        if modulation == 'BPSK':
+            return CR_BPSK
+        return CR_QUAD if modulation in ('QPSK', '16QAM', '64QAM', '256QAM') else CR_PSK8   # else: 8PSK (:317)
+
+    def _carrier_recovery_data(self, syms: np.ndarray, init_phase: float, init_freq: float, modulation: str,
+                               alpha: float) -> np.ndarray:                                # :302-325
+        return carrier_recovery(np.asarray(syms).reshape(1, -1), init_phase, init_freq, alpha,
+                                self._detector(modulation), self.device)[0][0]
+
+    def _sync_bits_for(self, modulation):                                                  # :364-368, :561-565
+        if self.MODULATIONS[modulation]['order'] >= 64:
+            return np.array([1, 0, 1, 0, 1, 0, 1, 0, 1, 1, 0, 0, 1, 1, 0, 0] * 15)
+        return self.sync_bits
+
+    def build_frame(self, data_bits: np.ndarray, modulation: str = 'QPSK', n_repeats: int = 20) -> np.ndarray:
+        """:346-385: pad | CW preamble | RRC-shaped (sync, data) | pad, tiled."""
+        preamble = np.ones(int(0.01 * self.fs), dtype=np.complex64)
+        sync_syms = self._bpsk_mod(self._sync_bits_for(modulation))
+        data_syms = self.modulate(data_bits, modulation)
+        frame_wave = self._upsample_filter(np.concatenate([sync_syms, data_syms]))
+        full_sig = np.concatenate([preamble, frame_wave])
+        pad = np.zeros(int(0.02 * self.fs), dtype=np.complex64)
+        return np.tile(np.concatenate([pad, full_sig, pad]), n_repeats)
+
+    def _process_received(self, rx_raw: np.ndarray, modulation: str, n_expected_bits: int):   # :523-664
+        """(bits, stats) of a captured burst, with the reference's stats keys and
+        error strings.  The capture is uploaded once; DC removal + power detection,
+        frequency correction, matched filter, sync search and both carrier loops
+        (every timing offset and sync rotation in one call each) run on the GPU
+        without leaving it.  On the host: np.mean of the capture, the preamble FFT
+        (_estimate_freq_offset), and the candidate choice and normalisation of
+        :617-651 on the few hundred recovered symbols, in the reference's own
+        expressions.  The demodulate() calls the reference makes inside its
+        rotation loop and discards are not made."""
+        import torch
+        x = _syms_c(rx_raw)
+        stats = {'success': False, 'n_samples': len(x)}
+        dev = torch.device('cuda', self.device)
+        mean = np.mean(x)                                   # :529, the signal's precision
+        preamble_len = int(0.01 * self.fs)
+        d_x = torch.from_numpy(x).to(dev)
+        burst_start, _ = burst_result(burst_find_device(d_x, preamble_len, 1000, dc=mean))
+        if burst_start < 0:
+            stats['error'] = 'Could not find burst'
+            return None, stats
+        stats['burst_start'] = burst_start
+
+        preamble_rx = x[burst_start:burst_start + preamble_len] - mean
+        f_offset = self._estimate_freq_offset(preamble_rx)
+        stats['freq_offset'] = f_offset
+        d_corr = mix_device(d_x, (-1j * 2 * np.pi * f_offset).imag, self.fs, dc=mean)
+        L = len(self.rrc_taps)
+        d_filt = fir_device(d_corr, self.rrc_taps, 1, 1, (min(len(x), L) - 1) // 2, max(len(x), L))
+
+        sync_bits = self._sync_bits_for(modulation)
+        sync_syms = self._bpsk_mod(sync_bits)
+        d_wave = torch.from_numpy(self._upsample_filter(sync_syms)).to(dev)
+        search_start = burst_start + preamble_len - 100
+        search_end = min(d_filt.numel(), burst_start + int(0.5 * self.fs))
+        peak_idx, peak = xcorr_result(xcorr_peak_device(d_filt[search_start:search_end], d_wave))
+        sync_start = search_start + peak_idx
+        stats['sync_peak'] = np.float64(peak)
+        stats['sync_start'] = sync_start
+
+        mod_cfg = self.MODULATIONS[modulation]
+        bps = mod_cfg['bps']
+        n_sync = len(sync_syms)
+        n_data_syms = (n_expected_bits + bps - 1) // bps
+        total_syms = n_sync + n_data_syms
+        frame_samples = total_syms * self.sps + self.sps * 4
+        if sync_start + frame_samples > d_filt.numel():
+            stats['error'] = 'Frame past buffer'
+            return None, stats
+        d_frame = d_filt[sync_start:sync_start + frame_samples]
+
+        # every timing offset through the sync loop in one call
+        offsets = [o for o in range(self.sps) if d_frame[o::self.sps].numel() >= total_syms]
+        if not offsets:
+            stats['error'] = 'Could not decode'
+            return None, stats
+        d_syms = torch.stack([d_frame[o::self.sps][:total_syms] for o in offsets])
+        d_sync, d_fin = carrier_recovery_device(d_syms[:, :n_sync].contiguous(), 0.0, 0.0, 0.03, CR_BPSK)
+        sync_rec_all, fin = d_sync.cpu().numpy(), d_fin.cpu().numpy()
+        tests = []
+        for k in range(len(offsets)):
+            sync_rec = sync_rec_all[k]
+            pwr = np.mean(np.abs(sync_rec) ** 2)
+            if pwr > 0:
+                sync_rec = sync_rec / np.sqrt(pwr)
+            for sync_rot in range(2):
+                tests.append(sync_rec * np.exp(1j * sync_rot * np.pi))
+        sync_rx = hard_demod(np.concatenate(tests), GT0, 1, device=self.device).astype(int).reshape(len(tests), n_sync)
+
+        # every (offset, rotation) that passes the sync check through the data loop in one call
+        cand = []
+        for k in range(len(offsets)):
+            for sync_rot in range(2):
+                sync_ber = np.mean(sync_rx[2 * k + sync_rot] != sync_bits)
+                if sync_ber > 0.2:
+                    continue
+                cand.append((k, sync_ber, fin[k, 0] + sync_rot * np.pi, fin[k, 1]))
+        if not cand:
+            stats['error'] = 'Could not decode'
+            return None, stats
+        rows = torch.tensor([c[0] for c in cand], device=dev)
+        d_data, _ = carrier_recovery_device(d_syms[rows, n_sync:].contiguous(), [c[2] for c in cand],
+                                            [c[3] for c in cand], mod_cfg['alpha'], self._detector(modulation))
+        data_all = d_data.cpu().numpy()
+
+        best_data_rx = None
+        best_sync_ber = 1.0
+        for j, (_, sync_ber, _, _) in enumerate(cand):
+            data_rec = data_all[j]
+            pwr = np.mean(np.abs(data_rec) ** 2)
+            if pwr > 0:
+                data_rec = data_rec / np.sqrt(pwr)
+            for rot in range(mod_cfg['n_rot']):
+                if sync_ber < best_sync_ber:               # holds at the first rotation only (:649-651)
+                    best_sync_ber = sync_ber
+                    best_data_rx = data_rec * np.exp(1j * rot * mod_cfg['rot_step'])
+        if best_data_rx is None:
+            stats['error'] = 'Could not decode'
+            return None, stats
+
+        data_bits_rx = self.demodulate(best_data_rx, modulation)
+        stats['success'] = True
+        stats['sync_ber'] = best_sync_ber
+        stats['rx_symbols'] = best_data_rx
+        return data_bits_rx[:n_expected_bits], stats
 
 
 # ---------------------------------------------------------------- natural family -------------

@@ -4,7 +4,9 @@ MI355X, device-resident data, against the HBM roofline.
 
 Every kernel here is a byte-moving pass, so each line reports algorithmic
 bytes (inputs read once + outputs written once) / kernel time, timed with HIP
-events on the stream the kernels run on.  One JSON line per kernel on stdout.
+events on the stream the kernels run on.  The last row is the receive chain's
+sync correlator, which is compute-bound: it reports complex f64 GMAC/s.  One
+JSON line per kernel on stdout.
 
   python tools/bench_modem.py [--msym 32] [--reps 10]
 """
@@ -98,6 +100,21 @@ def main():
     back = torch.empty(nin, dtype=torch.complex64, device=dev)
     ms = timed(lambda: MM.iq_dequantize_device(iq.view(torch.uint8), out=back, stream=st), a.reps, st)
     report("k_dequantize", ms, 2 * nin + 8 * nin, nin, "samples_per_s")
+    del x, y, z, iq, back, syms
+
+    # sync search: 1e6-sample region against a 640-tap complex waveform (sdr_modem.py:568-579 at
+    # fs = 2 MHz); compute-bound, so the figure is complex f64 MACs per second, not bytes
+    nr, nw = 1_000_000, 640
+    region = torch.randn(nr, dtype=torch.complex128, device=dev, generator=g)
+    wave = torch.randn(nw, dtype=torch.complex128, device=dev, generator=g)
+    result = torch.empty(2, dtype=torch.int64, device=dev)
+    scratch = torch.empty(2 * -(-(nr - nw + 1) // 1024), dtype=torch.int64, device=dev)
+    ms = timed(lambda: MM.xcorr_peak_device(region, wave, result=result, scratch=scratch, stream=st), a.reps, st)
+    macs = (nr - nw + 1) * nw
+    r = {"kernel": "k_xcorr 1e6 x 640 taps (peak only)", "ms": round(ms, 4), "GMAC_per_s": round(macs / ms / 1e6, 1),
+         "f64_TFLOPs": round(8 * macs / ms / 1e9, 2), "complex_macs": macs}
+    res.append(r)
+    print(json.dumps(r), flush=True)
 
 
 if __name__ == "__main__":
