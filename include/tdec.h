@@ -126,6 +126,35 @@ int tdec_decode_batch_dev(tdec_t *h, int B, const float *d_llr, long llr_stride,
  * placement.  No-op before the first such launch; returns after ~2 s at most. */
 int tdec_tail_gate(tdec_t *h, void *stream);
 
+/* ---- early termination (no reference counterpart) ----
+ * The same decodes with a hard-decision-aided stopping rule per codeword: the
+ * iterations at scaling 0.7 run as in the reference; after each of them the
+ * decisions ((f64(Lc) + La) + Le1) < 0 of all 2N bits are compared with the
+ * previous iteration's (before the first: Lc < 0), and once none changed the
+ * next iteration is the final one (scaling 1.0).  n_iter (nullable, int32[B])
+ * receives the iterations run, in 2..iterations (1 when iterations = 1).  A
+ * row's bits and lfinal are exactly those of the plain entry point on a handle
+ * created with iterations = n_iter[row].
+ * These calls run on the frame decoder (one codeword per workgroup) for every
+ * B, in stream-ordered launches of at most tdec_es_capacity() codewords; they
+ * return TDEC_EUNSUPPORTED where it is unavailable (TDEC_FRAME=0 in the
+ * environment, or a block whose LDS plan does not fit).  The first call sizes
+ * the frame workspace if tdec_reserve has not; later calls never allocate
+ * (tdec_decode_batch_es_dev also sizes the handle's plane buffer for one
+ * launch on first use). */
+int tdec_decode_batch_es(tdec_t *h, int B, const float *llr, long llr_stride, int32_t *bits, double *lfinal,
+                         int32_t *n_iter);
+int tdec_decode_planes_es_dev(tdec_t *h, int B, const float *d_planes, int32_t *d_bits, double *d_lfinal,
+                              int32_t *d_n_iter, void *stream);
+int tdec_decode_batch_es_dev(tdec_t *h, int B, const float *d_llr, long llr_stride, int32_t *d_bits,
+                             double *d_lfinal, int32_t *d_n_iter, void *stream);
+/* Codewords one early-stop launch takes with the handle's current workspace (a
+ * multiple of 64; 0 before it is sized), or a negative TDEC_E* code. */
+int tdec_es_capacity(tdec_t *h);
+/* 1 when the early-stop entry points can serve blocks of n_couples couples in
+ * this process (host only: no handle, no device call), else 0. */
+int tdec_early_stop_available(int n_couples);
+
 /* Soft demapper: compute_llr (test_sdr_with_coding.py:200-225) over any
  * labelled constellation (label i = bits MSB first).  syms: n_sym complex
  * values (f32 pairs, or f64 pairs when sym_f64); cons: M points (host memory,

@@ -31,6 +31,8 @@ EXPORTS = (
     "tdec_reserve_fused", "tdec_fused_available", "tdec_demap_decode_dev", "tdec_selftest", "tdec_selftest_trans",
     "tdec_host_alloc", "tdec_host_free", "tdec_encode_host", "tdec_siso_batch_f64", "tdec_siso_staging",
     "tdec_siso_staged", "tdec_siso_stats",
+    "tdec_decode_batch_es", "tdec_decode_planes_es_dev", "tdec_decode_batch_es_dev", "tdec_es_capacity",
+    "tdec_early_stop_available",
 )
 
 _lib = None
@@ -68,6 +70,15 @@ def _declare(L):
     L.tdec_depuncture_dev.argtypes = [_vp, C.c_int, _vp, C.c_long, _vp, _vp]
     L.tdec_decode_planes_dev.argtypes = [_vp, C.c_int, _vp, _vp, _vp, _vp]
     L.tdec_decode_batch_dev.argtypes = [_vp, C.c_int, _vp, C.c_long, _vp, _vp, _vp]
+    if hasattr(L, "tdec_decode_batch_es"):   # (A/B tools also load older builds without early stop)
+        L.tdec_decode_batch_es.argtypes = [_vp, C.c_int, _vp, C.c_long, _vp, _vp, _vp]
+        L.tdec_decode_planes_es_dev.argtypes = [_vp, C.c_int, _vp, _vp, _vp, _vp, _vp]
+        L.tdec_decode_batch_es_dev.argtypes = [_vp, C.c_int, _vp, C.c_long, _vp, _vp, _vp, _vp]
+        L.tdec_es_capacity.argtypes = [_vp]
+        L.tdec_early_stop_available.argtypes = [C.c_int]
+        for f in (L.tdec_decode_batch_es, L.tdec_decode_planes_es_dev, L.tdec_decode_batch_es_dev, L.tdec_es_capacity,
+                  L.tdec_early_stop_available):
+            f.restype = C.c_int
     if hasattr(L, "tdec_tail_gate"):   # (A/B tools also load older builds without it)
         L.tdec_tail_gate.argtypes = [_vp, _vp]
     L.tdec_demap_dev.argtypes = [C.c_int, _vp, C.c_int, C.c_long, _vp, C.c_int, C.c_int, C.c_int, C.c_double,

@@ -14,8 +14,8 @@ only those int64 counters are all-reduced.  Finished points are written to
 --out after every point, and a rerun skips them (checkpoint / resume, SURVEY
 §5).  The file records the sweep's configuration and the generator version;
 a rerun into it with any other configuration (modulation, block size, rate,
-algorithm, iterations, interleaver, codewords per point, base seed) or
-generator is refused instead of mixing two data streams, and each point's
+algorithm, iterations, interleaver, codewords per point, base seed, early
+stop) or generator is refused instead of mixing two data streams, and each point's
 generator key is derived from its Eb/N0 value (not its index in --ebn0), so a
 resumed sweep over a different grid regenerates exactly the same data.
 """
@@ -47,6 +47,8 @@ def sweep_config(a, inv_perm=None):
     cfg = {"generator": GENERATOR, "mod": a.mod, "n_couples": int(a.n), "rate": a.rate, "algo": a.algo,
            "iterations": int(a.iterations), "interleaver": a.interleaver, "codewords": int(a.codewords),
            "seed": int(a.seed)}
+    if getattr(a, "early_stop", False):   # (absent without the flag: files of earlier sweeps keep resuming)
+        cfg["early_stop"] = True
     if inv_perm is not None:
         cfg["inv_perm_digest"] = interleaver_digest(inv_perm)
     return cfg
@@ -84,14 +86,15 @@ def parse_points(spec):
     return [float(x) for x in spec.split(",")]
 
 
-def run_point(pipe, codec, mod, ebn0, start, count, batch, seed, device, times=None):
+def run_point(pipe, codec, mod, ebn0, start, count, batch, seed, device, times=None, iter_hist=None):
     """Bit errors, frame errors and codewords of global codewords
     [start, start + count) at one Eb/N0 point.  The data of codeword g is a
     counter-based stream of (seed, g) (workload.make_symbols), so the counters
     do not depend on the batch size or on how the job is sharded.  times (a list,
     optional): per batch, (demap + decode ms, decode ms) from HIP events on the
     pipeline's stream -- the bench's timed step, without the generator and the
-    error counting."""
+    error counting.  iter_hist (an int64 [iterations + 1] device tensor, optional;
+    early-stop pipelines): entry i gains the codewords that ran i iterations."""
     import torch
     from . import sharding as S
     from .workload import count_errors, make_symbols
@@ -104,6 +107,8 @@ def run_point(pipe, codec, mod, ebn0, start, count, batch, seed, device, times=N
         bits = pipe.run(syms, n0, events=e3[1:])[:n]
         ev.append(e3)
         e = count_errors(codec, bits, seed, cw0=start + off)
+        if iter_hist is not None:
+            iter_hist += torch.bincount(pipe.n_iter[:n], minlength=iter_hist.numel())[:iter_hist.numel()]
         cnt += torch.stack([e.sum(dtype=torch.int64), (e > 0).sum(), torch.tensor(n, device=device)]).to(torch.int64)
     if times is not None:
         torch.cuda.synchronize()
@@ -129,6 +134,9 @@ def main(argv=None):
     ap.add_argument("--batch", type=int, default=262144)
     ap.add_argument("--seed", type=int, default=2025)
     ap.add_argument("--interleaver", default="reference")
+    ap.add_argument("--early-stop", action="store_true",
+                    help="stop each codeword once its hard decisions repeat (--iterations is the cap); "
+                         "records mean_iters and iter_hist per point")
     ap.add_argument("--out", default=None)
     ap.add_argument("--dist-backend", default="nccl", help="nccl (= RCCL) on the node; gloo to rehearse")
     ap.add_argument("--all-on-device0", action="store_true", help="every rank on GPU 0 (rehearsal on a 1-GPU box)")
@@ -141,7 +149,11 @@ def main(argv=None):
     if a.all_on_device0 and world > 1 and a.dist_backend == "nccl":
         ap.error("--all-on-device0 puts several ranks on one GPU, which RCCL cannot do: add --dist-backend gloo")
     # the codec touches no GPU until its first call: its inv_perm keys the sweep
-    host_codec = M.DVBRCS2_Turbo(a.n, a.rate, a.iterations, algo=a.algo, interleaver=a.interleaver)
+    try:
+        host_codec = M.DVBRCS2_Turbo(a.n, a.rate, a.iterations, algo=a.algo, interleaver=a.interleaver,
+                                     early_stop=a.early_stop)
+    except ValueError as e:
+        ap.error(str(e))
     cfg = sweep_config(a, host_codec.inv_perm)
     try:
         done = load_resume(a.out, cfg)
@@ -158,7 +170,7 @@ def main(argv=None):
             dist.init_process_group(a.dist_backend, timeout=to)
     device = torch.device("cuda", dev_idx)
     codec = M.DVBRCS2_Turbo(a.n, a.rate, a.iterations, algo=a.algo, interleaver=a.interleaver,
-                            device=device.index)
+                            device=device.index, early_stop=a.early_stop)
     if world > 1:   # every rank must decode with the same de-interleaver
         S.check_same_interleaver(codec.inv_perm, dist, device if a.dist_backend == "nccl" else "cpu")
     pipe = DevicePipeline(codec, a.mod, a.batch, device)
@@ -172,12 +184,15 @@ def main(argv=None):
         start, count = S.shard_range(a.codewords, world, rank)
         t0 = time.time()
         times = []
-        cnt = run_point(pipe, codec, a.mod, e, start, count, a.batch, ebn0_seed(a.seed, e), device, times)
+        hist = torch.zeros(a.iterations + 1, dtype=torch.int64, device=device) if a.early_stop else None
+        cnt = run_point(pipe, codec, a.mod, e, start, count, a.batch, ebn0_seed(a.seed, e), device, times, hist)
+        if hist is not None:
+            cnt = torch.cat([cnt, hist])   # one reduction for the error counters and the histogram
         if world > 1 and a.dist_backend != "nccl":
             cnt = cnt.cpu()
         S.reduce_counters(cnt, dist if world > 1 else None)
         torch.cuda.synchronize()
-        be, fe, ncw = (int(x) for x in cnt.tolist())
+        be, fe, ncw = (int(x) for x in cnt[:3].tolist())
         dt = time.time() - t0
         rec = {"ebn0_db": e, "mod": a.mod, "n_couples": a.n, "rate": a.rate, "algo": a.algo,
                "interleaver": a.interleaver, "codewords": ncw,
@@ -187,6 +202,11 @@ def main(argv=None):
                "step_ms": sum(t[0] for t in times), "decode_ms": sum(t[1] for t in times),
                "step_codewords_per_s": count / max(1e-9, sum(t[0] for t in times) * 1e-3),
                "decode_codewords_per_s": count / max(1e-9, sum(t[1] for t in times) * 1e-3)}
+        if a.early_stop:
+            h = [int(x) for x in cnt[3:].tolist()]
+            rec["early_stop"] = True
+            rec["iter_hist"] = h   # iter_hist[i]: codewords that ran i iterations
+            rec["mean_iters"] = sum(i * c for i, c in enumerate(h)) / max(1, ncw)
         results.append(rec)
         if rank == 0:
             print(json.dumps(rec), flush=True)

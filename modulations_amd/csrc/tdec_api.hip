@@ -375,6 +375,7 @@ struct tdec_ctx {
     DevBuf planes_own;                 // planes for tdec_decode_batch(_dev)
     int cap_batch = 0;
     DevBuf h_llr, h_bits, h_lf, h_misc; // staging for the host-pointer API
+    DevBuf h_nit;                      //   and the early-stop calls' iteration counts
     PinBuf pin;                        // page-locked staging of the small host-pointer calls
     PinBuf pin_siso;                   // the caller-filled SISO staging (tdec_siso_staging), never regrown behind its views
     PinBuf pin_flags;                  //   its per-row completion flags (fine-grained: coherent while a kernel runs)
@@ -691,6 +692,7 @@ void tdec_destroy(tdec_t *h) {
     h->h_bits.release();
     h->h_lf.release();
     h->h_misc.release();
+    h->h_nit.release();
     h->pin.release();
     h->pin_siso.release();
     h->pin_flags.release();
@@ -933,7 +935,11 @@ static int frame_lds_attr(int device) {
                          (const void *)k_turbo_decode_frame<false, 0, 2>, (const void *)k_turbo_decode_frame<true, 0, 2>,
                          (const void *)k_turbo_decode_frame<false, 1, 2>, (const void *)k_turbo_decode_frame<true, 1, 2>,
                          (const void *)k_siso_frame<float, 0, 2>, (const void *)k_siso_frame<double, 0, 2>,
-                         (const void *)k_siso_frame<float, 1, 2>, (const void *)k_siso_frame<double, 1, 2>};
+                         (const void *)k_siso_frame<float, 1, 2>, (const void *)k_siso_frame<double, 1, 2>,
+                         (const void *)k_turbo_decode_frame_es<false, 0, 1>, (const void *)k_turbo_decode_frame_es<true, 0, 1>,
+                         (const void *)k_turbo_decode_frame_es<false, 1, 1>, (const void *)k_turbo_decode_frame_es<true, 1, 1>,
+                         (const void *)k_turbo_decode_frame_es<false, 0, 2>, (const void *)k_turbo_decode_frame_es<true, 0, 2>,
+                         (const void *)k_turbo_decode_frame_es<false, 1, 2>, (const void *)k_turbo_decode_frame_es<true, 1, 2>};
     for (const void *f : fns) {
         const hipError_t r = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, FR_LDS_MAX);
         if (r != hipSuccess) return fail(TDEC_EHIP, std::string("hipFuncSetAttribute (frame decoder LDS): ") + hipGetErrorString(r));
@@ -1085,6 +1091,99 @@ int tdec_decode_batch_dev(tdec_t *h, int B, const float *d_llr, long llr_stride,
     return rc;
 }
 
+// ---- early stop: the frame decoder with per-codeword termination --------------
+// Every batch size runs on the frame kernel, in launches of at most es_rows() codewords
+// (whole 64-codeword tiles, so a chunk of a caller's plane buffer starts at a tile):
+// the rows the small-batch workspace holds (Le1, and Le2 where it lives in global
+// scratch).  The first call on a handle whose workspace holds less than one tile sizes
+// it (ES_ROWS_DEFAULT rows at most); tdec_reserve for a small batch sizes it too.
+constexpr int ES_ROWS_DEFAULT = 8192;
+static int es_available(const tdec_t *h) {
+    if (use_frame_decoder(h)) return 0;
+    const char *e = getenv("TDEC_FRAME");
+    return fail(TDEC_EUNSUPPORTED, e && e[0] == '0' ? "early stop runs on the frame decoder, which TDEC_FRAME=0 disables"
+                                                    : "early stop runs on the frame decoder, whose LDS plan does not fit this block size");
+}
+static int es_rows(const tdec_t *h) {
+    const size_t row = (frame_le2_global(h->N) ? 2 : 1) * (size_t)h->N * sizeof(double2);
+    return (int)(std::min<size_t>(h->ll_ws.cap / row, 1 << 30) / WAVE * WAVE);
+}
+static int ensure_es(tdec_t *h, int B) {
+    if (es_rows(h) >= WAVE) return 0;
+    quiesce(h);   // regrowth frees
+    const size_t rows = (size_t)(std::min(std::max(B, WAVE), ES_ROWS_DEFAULT) + WAVE - 1) / WAVE * WAVE;
+    return h->ll_ws.ensure(rows * (frame_le2_global(h->N) ? 2 : 1) * h->N * sizeof(double2));
+}
+
+int tdec_es_capacity(tdec_t *h) {
+    if (!h) return fail(TDEC_EINVAL, "null handle");
+    if (int rc = es_available(h)) return rc;
+    return es_rows(h);
+}
+
+int tdec_early_stop_available(int n_couples) {
+    const char *e = getenv("TDEC_FRAME");
+    return !(e && e[0] == '0') && n_couples > 0 && frame_fits(n_couples, true);
+}
+
+int tdec_decode_planes_es_dev(tdec_t *h, int B, const float *d_planes, int32_t *d_bits, double *d_lfinal,
+                              int32_t *d_n_iter, void *stream) {
+    if (!h || B < 0) return fail(TDEC_EINVAL, "bad decode arguments");
+    if (B == 0) return 0;
+    if (!d_planes || !d_bits) return fail(TDEC_EINVAL, "bad decode arguments");
+    if (int rc = es_available(h)) return rc;
+    Guard g(h->device);
+    hipStream_t st = (hipStream_t)stream;
+    if (int rc = ensure_es(h, B)) return rc;
+    if (int rc = frame_lds_attr(h->device)) return rc;
+    if (int rc = order_on(h, st)) return rc;
+    const int C = es_rows(h), N = h->N;
+    const bool lg = frame_le2_global(N), w1 = fr_wpd(N, false) == 1;
+    const auto kern = h->algo ? (lg ? (w1 ? k_turbo_decode_frame_es<true, 1, 1> : k_turbo_decode_frame_es<true, 1, 2>)
+                                    : (w1 ? k_turbo_decode_frame_es<false, 1, 1> : k_turbo_decode_frame_es<false, 1, 2>))
+                              : (lg ? (w1 ? k_turbo_decode_frame_es<true, 0, 1> : k_turbo_decode_frame_es<true, 0, 2>)
+                                    : (w1 ? k_turbo_decode_frame_es<false, 0, 1> : k_turbo_decode_frame_es<false, 0, 2>));
+    // chunks of C rows (whole tiles) reuse the workspace one after the other on the stream
+    for (long r0 = 0; r0 < B; r0 += C) {
+        const int n = (int)std::min<long>(C, B - r0);
+        FrArgs a{n, N, h->iters, d_planes + (r0 / WAVE) * tile_floats(N), (double2 *)h->ll_ws.p, d_bits + r0 * 2 * N,
+                 d_lfinal ? d_lfinal + r0 * 2 * N : nullptr, h->n_used, lg ? (double2 *)h->ll_ws.p + (size_t)n * N : nullptr};
+        hipLaunchKernelGGL(kern, dim3((unsigned)n), dim3(FR_BLOCK), fr_lds(N, true, lg).total, st, a,
+                           (const int *)h->d_perm, (const int *)h->d_inv, (const int *)h->d_ford,
+                           d_n_iter ? d_n_iter + r0 : nullptr);
+        HIPCHK(hipGetLastError());
+    }
+    return mark_used(h, st);
+}
+
+int tdec_decode_batch_es_dev(tdec_t *h, int B, const float *d_llr, long llr_stride, int32_t *d_bits, double *d_lfinal,
+                             int32_t *d_n_iter, void *stream) {
+    if (!h || B < 0) return fail(TDEC_EINVAL, "bad decode arguments");
+    if (B == 0) return 0;
+    if (!d_llr || !d_bits) return fail(TDEC_EINVAL, "bad decode arguments");
+    if (llr_stride < h->llr_len) return fail(TDEC_ESHORT, "llr rows shorter than the de-puncture walk");
+    if (int rc = es_available(h)) return rc;
+    Guard g(h->device);
+    if (int rc = ensure_es(h, B)) return rc;
+    // the handle's own planes hold one chunk (sized on first use, like the workspace)
+    const int C = std::min(B, es_rows(h));
+    if (tdec_planes_bytes(h, C) > h->planes_own.cap) {
+        quiesce(h);
+        if (int rc = h->planes_own.ensure(tdec_planes_bytes(h, C))) return rc;
+    }
+    if (int rc = order_on(h, (hipStream_t)stream)) return rc;
+    for (long r0 = 0; r0 < B; r0 += C) {
+        const int n = (int)std::min<long>(C, B - r0);
+        int rc = tdec_depuncture_dev(h, n, d_llr + r0 * llr_stride, llr_stride, (float *)h->planes_own.p, stream);
+        if (!rc)
+            rc = tdec_decode_planes_es_dev(h, n, (const float *)h->planes_own.p, d_bits + r0 * 2 * h->N,
+                                           d_lfinal ? d_lfinal + r0 * 2 * h->N : nullptr,
+                                           d_n_iter ? d_n_iter + r0 : nullptr, stream);
+        if (rc) return rc;
+    }
+    return 0;
+}
+
 // Zero-copy single calls: a small host-pointer call of at most ZC_MAX_ROWS rows lets the kernels read their
 // inputs from, and write their outputs to, the page-locked staging buffer itself
 // instead of a DMA each way.  Measured (profiles/r04y/, r04z/): bcjr_max_log_map
@@ -1234,6 +1333,71 @@ int tdec_decode_batch(tdec_t *h, int B, const float *llr, long llr_stride, int32
     HIPCHK(hipStreamSynchronize(ds));
     HIPCHK(hipStreamSynchronize(us));
     HIPCHK(hipStreamSynchronize(h->stream));
+    return 0;
+}
+
+// tdec_decode_batch with early stop.  Up to ZC_MAX_ROWS rows take tdec_decode_batch's
+// zero-copy route (the kernels read the LLR rows from, and write bits / L_final /
+// n_iter into, the page-locked staging); larger batches go through device staging in
+// chunks of ES_ROWS_DEFAULT rows (TDEC_HOST_CHUNK overrides it), one after the other
+// on the handle's stream.
+int tdec_decode_batch_es(tdec_t *h, int B, const float *llr, long llr_stride, int32_t *bits, double *lfinal,
+                         int32_t *n_iter) {
+    if (!h || B < 0) return fail(TDEC_EINVAL, "bad decode arguments");
+    if (llr_stride < h->llr_len) return fail(TDEC_ESHORT, "llr rows shorter than the de-puncture walk");
+    if (B == 0) return 0;
+    if (!llr || !bits) return fail(TDEC_EINVAL, "bad decode arguments");
+    if (int rc = es_available(h)) return rc;
+    Guard g(h->device);
+    quiesce(h);
+    const size_t row_b = (size_t)2 * h->N;
+    DrainOnExit drain{h->stream, nullptr};
+    if (zero_copy(B)) {
+        const size_t in_b = (size_t)B * llr_stride * sizeof(float), bits_b = B * row_b * sizeof(int32_t),
+                     lf_b = lfinal ? B * row_b * sizeof(double) : 0, ni_b = (size_t)B * sizeof(int32_t);
+        auto up256 = [](size_t x) { return (x + 255) / 256 * 256; };
+        const size_t o_bits = up256(in_b), o_lf = up256(o_bits + bits_b), o_ni = up256(o_lf + lf_b), pin_b = o_ni + ni_b;
+        if (int rc = h->pin.ensure(pin_b)) return rc;
+        if (h->pin.dev) {
+            char *pin = (char *)h->pin.p, *dp = (char *)h->pin.dev;
+            std::memcpy(pin, llr, in_b);
+            if (int rc = tdec_decode_batch_es_dev(h, B, (const float *)dp, llr_stride, (int32_t *)(dp + o_bits),
+                                                  lfinal ? (double *)(dp + o_lf) : nullptr, (int32_t *)(dp + o_ni), h->stream))
+                return rc;
+            HIPCHK(hipStreamSynchronize(h->stream));
+            drain.disarm();
+            mark_idle(h);
+            std::memcpy(bits, pin + o_bits, bits_b);
+            if (lfinal) std::memcpy(lfinal, pin + o_lf, lf_b);
+            if (n_iter) std::memcpy(n_iter, pin + o_ni, ni_b);
+            return 0;
+        }
+    }
+    long chunk = ES_ROWS_DEFAULT;
+    if (const char *pc = getenv("TDEC_HOST_CHUNK")) chunk = std::max(1L, atol(pc));
+    const int C = (int)std::min<long>(B, chunk);
+    int rc = h->h_llr.ensure((size_t)C * llr_stride * sizeof(float));
+    if (!rc) rc = h->h_bits.ensure(C * row_b * sizeof(int32_t));
+    if (!rc && lfinal) rc = h->h_lf.ensure(C * row_b * sizeof(double));
+    if (!rc) rc = h->h_nit.ensure((size_t)C * sizeof(int32_t));
+    if (rc) return rc;
+    for (long r0 = 0; r0 < B; r0 += C) {
+        const size_t n = (size_t)std::min<long>(C, B - r0);
+        HIPCHK(hipMemcpyAsync(h->h_llr.p, llr + r0 * llr_stride, n * llr_stride * sizeof(float), hipMemcpyHostToDevice,
+                              h->stream));
+        if ((rc = tdec_decode_batch_es_dev(h, (int)n, (const float *)h->h_llr.p, llr_stride, (int32_t *)h->h_bits.p,
+                                           lfinal ? (double *)h->h_lf.p : nullptr, (int32_t *)h->h_nit.p, h->stream)))
+            return rc;
+        HIPCHK(hipMemcpyAsync(bits + r0 * row_b, h->h_bits.p, n * row_b * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+        if (lfinal)
+            HIPCHK(hipMemcpyAsync(lfinal + r0 * row_b, h->h_lf.p, n * row_b * sizeof(double), hipMemcpyDeviceToHost,
+                                  h->stream));
+        if (n_iter)
+            HIPCHK(hipMemcpyAsync(n_iter + r0, h->h_nit.p, n * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+    }
+    HIPCHK(hipStreamSynchronize(h->stream));
+    drain.disarm();
+    mark_idle(h);
     return 0;
 }
 

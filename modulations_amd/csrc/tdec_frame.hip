@@ -791,12 +791,21 @@ struct FrArgs {
 // LG: Le2 in global scratch (N > 805; see fr_lds).  WPD: waves per recursion
 // direction (1: one wave, segments and rounds inside it, no cross-wave barriers;
 // 2: fr_recursion_x), chosen per call by N (tdec_api.hip fr_wpd).
-template <bool LG, int ALGO = 0, int WPD = FR_WPD_MAX>
-__global__ __launch_bounds__(FR_BLOCK) void k_turbo_decode_frame(FrArgs p, const int *__restrict__ perm,
-                                                                 const int *__restrict__ inv,
-                                                                 const int *__restrict__ ord) {
-    extern __shared__ float4 fr_sm[];
-    lds_b *sm = (lds_b *)fr_sm;
+//
+// ES (early stop): hard-decision-aided termination.  The iterations at
+// sf = 0.7 do not depend on the total count, so after SISO 2 of each of them the
+// workgroup forms the decisions the reference's hard-decision expression would give
+// (D_t = ((f64(Lc) + La_t) + Le1_t) < 0, La_t = Le2_t[inv_perm]; D_0 = Lc < 0),
+// each thread for its own pos[j] positions against the bits it kept from the previous
+// iteration; when no thread saw a change the next iteration is the final one
+// (sf = 1.0).  The row's outputs are then those of a fixed decode with iterations =
+// n_iter, bit for bit.  Le1 is stored every iteration (by the thread that reads it
+// back); the workgroup-wide OR goes through two alternating words in the spare bytes
+// of the round-control block (no LDS beyond fr_lds: 88 bytes are left at N = 805).
+template <bool LG, int ALGO, int WPD, bool ES>
+__device__ __forceinline__ void fr_decode(lds_b *sm, const FrArgs p, const int *__restrict__ perm,
+                                          const int *__restrict__ inv, const int *__restrict__ ord,
+                                          int32_t *__restrict__ n_iter) {
     const int N = p.N, tid = threadIdx.x;
     const long cw = blockIdx.x;
     const FrLds Lo = fr_lds(N, true, LG);
@@ -828,17 +837,60 @@ __global__ __launch_bounds__(FR_BLOCK) void k_turbo_decode_frame(FrArgs p, const
     }
     __syncthreads();   // (a workgroup barrier orders the workgroup's global accesses too: one CU, one L1)
     double2 *le1 = p.le1 + cw * N;
-    for (int it = 0; it < p.iters; ++it) {
-        const double sf = it < p.iters - 1 ? 0.7 : 1.0;   // :496
-        const bool last = it == p.iters - 1;
+    int n_it = p.iters;        // ES: lowered to it + 2 once the decisions have settled
+    unsigned dprev = 0;        // ES: this thread's decisions of the previous iteration, bits 2j (A), 2j + 1 (B)
+    volatile __attribute__((address_space(3))) unsigned *es_flag =
+        (volatile __attribute__((address_space(3))) unsigned *)(sm + Lo.ev + 2 * FR_NSEG_MAX * 64 + 48);
+    if constexpr (ES) {
+#pragma unroll
+        for (int j = 0; j < FR_J; ++j)
+            if (pos[j] >= 0) dprev |= (xr[j].x < 0.0f ? 1u : 0u) << (2 * j) | (xr[j].y < 0.0f ? 2u : 0u) << (2 * j);
+    }
+    for (int it = 0; it < (ES ? n_it : p.iters); ++it) {
+        const bool last = it == (ES ? n_it : p.iters) - 1;
+        const double sf = last ? 1.0 : 0.7;   // :496
+        const bool st1 = ES || last;          // ES reads Le1 back after every iteration
+        if constexpr (ES) {
+            // this iteration's word; its last readers (iteration it - 2) are barriers behind
+            if (tid == 0 && !last) es_flag[it & 1] = 0u;
+        }
         if constexpr (LG) {
-            fr_siso<ALGO, WPD>(FrIn1T<const double2 *>{le2g, sinv}, FrOut1{sm + Lo.p1, last ? le1 : nullptr, p.n_used}, pos,
+            fr_siso<ALGO, WPD>(FrIn1T<const double2 *>{le2g, sinv}, FrOut1{sm + Lo.p1, st1 ? le1 : nullptr, p.n_used}, pos,
                           xr, sm, Lo, N, sf);
             fr_siso<ALGO, WPD>(FrIn2{sm + Lo.p1, sperm}, FrOut2T<double2 *>{le2g}, pos, zr, sm, Lo, N, sf);
         } else {
-            fr_siso<ALGO, WPD>(FrIn1{le2s, sinv}, FrOut1{sm + Lo.p1, last ? le1 : nullptr, p.n_used}, pos, xr, sm, Lo, N, sf);
+            fr_siso<ALGO, WPD>(FrIn1{le2s, sinv}, FrOut1{sm + Lo.p1, st1 ? le1 : nullptr, p.n_used}, pos, xr, sm, Lo, N, sf);
             fr_siso<ALGO, WPD>(FrIn2{sm + Lo.p1, sperm}, FrOut2T<lds_d2 *>{le2s}, pos, zr, sm, Lo, N, sf);
         }
+        if constexpr (ES) {
+            if (!last) {   // workgroup-uniform
+                unsigned d = 0;
+#pragma unroll
+                for (int j = 0; j < FR_J; ++j) {
+                    const int k = pos[j];
+                    if (k < 0) continue;
+                    double lax, lay;
+                    if constexpr (LG) {
+                        const double2 la = le2g[sinv[k]];
+                        lax = la.x, lay = la.y;
+                    } else {
+                        const d2v la = le2s[sinv[k]];
+                        lax = la.x, lay = la.y;
+                    }
+                    const double2 le = le1[k];   // this thread's own store of this iteration
+                    const double fa = ((double)xr[j].x + lax) + le.x;
+                    const double fb = ((double)xr[j].y + lay) + le.y;
+                    d |= (fa < 0.0 ? 1u : 0u) << (2 * j) | (fb < 0.0 ? 2u : 0u) << (2 * j);
+                }
+                if (d != dprev) es_flag[it & 1] = 1u;
+                dprev = d;
+                __syncthreads();
+                if (es_flag[it & 1] == 0u) n_it = it + 2;   // settled: one more, final, iteration
+            }
+        }
+    }
+    if constexpr (ES) {
+        if (n_iter && tid == 0) n_iter[cw] = n_it;
     }
     // hard decision (:526-537): L = (Lc + La) + Le1, La = Le2[inv_perm]
 #pragma unroll
@@ -860,6 +912,25 @@ __global__ __launch_bounds__(FR_BLOCK) void k_turbo_decode_frame(FrArgs p, const
         *reinterpret_cast<int2 *>(p.bits + cw * 2 * N + 2 * k) = make_int2(fa < 0.0 ? 1 : 0, fb < 0.0 ? 1 : 0);
         if (p.lfinal) *reinterpret_cast<double2 *>(p.lfinal + cw * 2 * N + 2 * k) = make_double2(fa, fb);
     }
+}
+
+template <bool LG, int ALGO = 0, int WPD = FR_WPD_MAX>
+__global__ __launch_bounds__(FR_BLOCK) void k_turbo_decode_frame(FrArgs p, const int *__restrict__ perm,
+                                                                 const int *__restrict__ inv,
+                                                                 const int *__restrict__ ord) {
+    extern __shared__ float4 fr_sm[];
+    fr_decode<LG, ALGO, WPD, false>((lds_b *)fr_sm, p, perm, inv, ord, nullptr);
+}
+
+// The early-stop decoder: the same decode, ending each codeword one final iteration
+// after its decisions settle; n_iter (nullable): [B] iterations run per codeword.
+template <bool LG, int ALGO = 0, int WPD = FR_WPD_MAX>
+__global__ __launch_bounds__(FR_BLOCK) void k_turbo_decode_frame_es(FrArgs p, const int *__restrict__ perm,
+                                                                    const int *__restrict__ inv,
+                                                                    const int *__restrict__ ord,
+                                                                    int32_t *__restrict__ n_iter) {
+    extern __shared__ float4 fr_sm[];
+    fr_decode<LG, ALGO, WPD, true>((lds_b *)fr_sm, p, perm, inv, ord, n_iter);
 }
 
 // bcjr_max_log_map (:116-281) on [B][N] rows, one row per workgroup.

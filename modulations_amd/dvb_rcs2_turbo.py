@@ -16,7 +16,8 @@ Same names, argument meaning, dtypes and error behaviour as the reference:
 
 Additions: ``decode_batch`` (B codewords in one launch), ``decode_device``
 (torch tensors already on the GPU, stream-ordered), ``algo='log-map'``,
-``inv_perm=`` / ``interleaver=`` to pin the de-interleaver.
+``inv_perm=`` / ``interleaver=`` to pin the de-interleaver, ``early_stop=True``
+(per-codeword early termination with iteration counts).
 
 Every decode / SISO runs in the HIP library (modulations_amd/lib/libtdec.so);
 there is no host fallback.  ``encode`` is host-side numpy (it is not on the hot
@@ -132,10 +133,17 @@ class DVBRCS2_Turbo:
       interleaver 'reference' (default; the reference's non-bijective perm) or
                  'valid-perm' (a true permutation: never used for parity)
       device     HIP device ordinal
+      early_stop False (default: every decode runs all `iterations`), or True: a
+                 codeword stops one final iteration after its hard decisions
+                 repeat (tdec_decode_*_es).  `iterations` is then the
+                 cap; each row's result is exactly that of a fixed decode with
+                 iterations = its count (decode_batch(return_iters=True),
+                 decode_device(n_iter=)).  Runs on the frame decoder: ValueError
+                 where that is unavailable (TDEC_FRAME=0).
     """
 
     def __init__(self, N_couples, code_rate, iterations=8, *, algo="max-log", inv_perm="numpy",
-                 interleaver="reference", device=None):
+                 interleaver="reference", device=None, early_stop=False):
         self.N = N_couples
         self.k_info = N_couples * 2
         self.iterations = iterations
@@ -159,8 +167,18 @@ class DVBRCS2_Turbo:
          self.G_matrix) = _std_tables()
         self.n_coded = _t.coded_size(self.N, self.punct)
         self.device = _default_device() if device is None else device
+        self.early_stop = bool(early_stop)
+        if self.early_stop:
+            self._require_early_stop()
         self._h = None
         self._circ = None
+
+    def _require_early_stop(self):
+        """ValueError where the early-stop entry points cannot serve this codec (a
+        host-side question: asked before any device work)."""
+        if not _n.lib().tdec_early_stop_available(int(self.N)):
+            raise ValueError(f"early_stop=True needs the frame decoder, which is unavailable for N = {self.N} "
+                             "in this process (TDEC_FRAME=0, or the block does not fit its LDS plan)")
 
     # -- device handle (created lazily so a codec can be built without a GPU) --
     @property
@@ -209,11 +227,13 @@ class DVBRCS2_Turbo:
             raise ValueError("decode() takes one codeword; use decode_batch for [B, n] input")
         return self.decode_batch(llr[None, :])[0]
 
-    def decode_batch(self, llr, return_lfinal=False, out=None):
+    def decode_batch(self, llr, return_lfinal=False, out=None, return_iters=False):
         """Decode B codewords: llr [B, >= n_llr] -> int32 [B, 2N]
         (and L_final f64 [B, 2N] = Lc + La + Le1, :529-530, when asked).
         out: optional C-contiguous int32 [B, 2N] array for the bits (e.g. a
-        host_buffer(), which the copies reach without runtime staging)."""
+        host_buffer(), which the copies reach without runtime staging).
+        return_iters: append the int32 [B] iterations run per codeword (with
+        early_stop; `iterations` for every row without)."""
         llr = np.ascontiguousarray(np.asarray(llr, dtype=np.float32))
         if llr.ndim != 2:
             raise ValueError("decode_batch takes a [B, n] array")
@@ -228,9 +248,14 @@ class DVBRCS2_Turbo:
         else:
             bits = np.zeros((B, self.k_info), np.int32)
         lf = np.zeros((B, self.k_info)) if return_lfinal else None
-        if B:
+        iters = np.full(B, self.iterations, np.int32) if return_iters else None
+        if B and self.early_stop:
+            self._require_early_stop()
+            h.call("tdec_decode_batch_es", B, _n.ptr(llr), llr.shape[1], _n.ptr(bits), _n.ptr(lf), _n.ptr(iters))
+        elif B:
             h.call("tdec_decode_batch", B, _n.ptr(llr), llr.shape[1], _n.ptr(bits), _n.ptr(lf))
-        return (bits, lf) if return_lfinal else bits
+        res = (bits,) + ((lf,) if return_lfinal else ()) + ((iters,) if return_iters else ())
+        return res if len(res) > 1 else bits
 
     @staticmethod
     def host_buffer(shape, dtype=np.float32):
@@ -269,25 +294,50 @@ class DVBRCS2_Turbo:
         import torch
         return torch.cuda.current_stream(self.device).cuda_stream
 
-    def decode_device(self, llr, bits=None, lfinal=None, stream=None):
+    def early_stop_capacity(self):
+        """Codewords one early-stop launch takes with the handle's current workspace
+        (tdec_es_capacity: a multiple of 64, 0 before the workspace is sized);
+        larger batches run as several stream-ordered launches."""
+        rc = _n.lib().tdec_es_capacity(self.handle.h)
+        if rc < 0:
+            _n.check(rc)
+        return rc
+
+    def _n_iter_check(self, n_iter, B):
+        import torch
+        if n_iter is not None:
+            if not self.early_stop:
+                raise ValueError("n_iter is filled by early_stop=True codecs only")
+            self._dev_check(n_iter, "n_iter", torch.int32, (B,))
+
+    def decode_device(self, llr, bits=None, lfinal=None, stream=None, n_iter=None):
         """llr: float32 [B, n] device tensor (rows contiguous) -> int32 [B, 2N] device tensor.
-        Stream-ordered on `stream` (default: torch's current stream)."""
+        Stream-ordered on `stream` (default: torch's current stream).
+        n_iter (early_stop codecs): int32 [B] device tensor for the iterations run."""
         import torch
         self._dev_check(llr, "llr", torch.float32, rows_contig=True)
         B = llr.shape[0]
         if B and llr.shape[1] < self.handle.llr_len:
             raise IndexError(f"index {llr.shape[1]} is out of bounds for axis 0 with size {llr.shape[1]}")
-        self.reserve(B)
+        self._n_iter_check(n_iter, B)
+        if self.early_stop:
+            self._require_early_stop()   # (the early-stop calls size their own workspace)
+        else:
+            self.reserve(B)
         if bits is None:
             bits = torch.empty((B, self.k_info), dtype=torch.int32, device=llr.device)
         self._dev_check(bits, "bits", torch.int32, (B, self.k_info))
         if lfinal is not None:
             self._dev_check(lfinal, "lfinal", torch.float64, (B, self.k_info))
+        if self.early_stop:
+            self.handle.call("tdec_decode_batch_es_dev", B, _n.ptr(llr), llr.stride(0) if B > 1 else llr.shape[1],
+                             _n.ptr(bits), _n.ptr(lfinal), _n.ptr(n_iter), self._stream(stream))
+            return bits
         self.handle.call("tdec_decode_batch_dev", B, _n.ptr(llr), llr.stride(0) if B > 1 else llr.shape[1],
                          _n.ptr(bits), _n.ptr(lfinal), self._stream(stream))
         return bits
 
-    def decode_planes_device(self, planes, B, bits, lfinal=None, stream=None):
+    def decode_planes_device(self, planes, B, bits, lfinal=None, stream=None, n_iter=None):
         import torch
         if planes.numel() * planes.element_size() < self.planes_bytes(B):
             raise ValueError("planes buffer smaller than planes_bytes(B)")
@@ -295,6 +345,12 @@ class DVBRCS2_Turbo:
         self._dev_check(bits, "bits", torch.int32, (B, self.k_info))
         if lfinal is not None:
             self._dev_check(lfinal, "lfinal", torch.float64, (B, self.k_info))
+        self._n_iter_check(n_iter, B)
+        if self.early_stop:
+            self._require_early_stop()
+            self.handle.call("tdec_decode_planes_es_dev", B, _n.ptr(planes), _n.ptr(bits), _n.ptr(lfinal),
+                             _n.ptr(n_iter), self._stream(stream))
+            return bits
         self.handle.call("tdec_decode_planes_dev", B, _n.ptr(planes), _n.ptr(bits), _n.ptr(lfinal),
                          self._stream(stream))
         return bits

@@ -79,14 +79,19 @@ class DevicePipeline:
     3-4 % SLOWER on MI355X (294 vs 285 ms per 1 M codewords): a
     wave that demaps is not streaming, and at two waves per SIMD the decoder
     needs every wave streaming to keep HBM busy.  Buffers are sized once; run()
-    is stream-ordered and allocation free."""
+    is stream-ordered and allocation free.
+
+    A codec built with early_stop=True decodes through the early-stop frame
+    decoder (two launches, never fused); the iterations each codeword of the
+    last batch ran are in `n_iter` (int32 [B] on the device, first rows)."""
 
     def __init__(self, codec, mod, B, device, fused=False, overlap=False, gate=True):
         import torch
         self.codec, self.mod, self.B = codec, mod, B
         self.bps = D.MODULATIONS[mod]["bps"]
         self.cons = D.constellation(mod)
-        self.fused = bool(fused) and codec.fused_available(self.cons, self.bps)
+        self.early_stop = bool(getattr(codec, "early_stop", False))
+        self.fused = bool(fused) and not self.early_stop and codec.fused_available(self.cons, self.bps)
         self.overlap = bool(overlap) and not self.fused
         if self.fused:
             codec.reserve_fused(B)
@@ -95,6 +100,7 @@ class DevicePipeline:
             codec.reserve(B)
             self.planes = torch.empty(codec.planes_bytes(B) // 4, dtype=torch.float32, device=device)
         self.bits = torch.empty((B, codec.k_info), dtype=torch.int32, device=device)
+        self.n_iter = torch.empty(B, dtype=torch.int32, device=device) if self.early_stop else None
         if self.overlap:
             # Batch i+1's demap runs on its own handle (handles order only their own
             # buffers), its own low-priority stream and the other plane buffer, so
@@ -121,6 +127,7 @@ class DevicePipeline:
         everything queued on `stream`, i.e. no overlap."""
         _, div32, nve = D.demap_mode(np.complex64, self.cons.dtype, np.float64(noise_var))
         bits = self.bits[:syms.shape[0]]          # the first rows: a contiguous view
+        es = {"n_iter": self.n_iter[:syms.shape[0]]} if self.early_stop else {}
         if self.overlap:
             import torch
             stream = torch.cuda.current_stream() if stream is None else stream
@@ -141,7 +148,7 @@ class DevicePipeline:
             sk.wait_event(self.demap_done[b])
             if events is not None:
                 events[0].record(sk)
-            self.codec.decode_planes_device(self.planes_db[b], syms.shape[0], bits, stream=sk)
+            self.codec.decode_planes_device(self.planes_db[b], syms.shape[0], bits, stream=sk, **es)
             if events is not None:
                 events[1].record(sk)
             self.decode_done[b].record(sk)
@@ -157,7 +164,7 @@ class DevicePipeline:
                                            stream=stream)
             if events is not None:
                 events[0].record(stream)
-            self.codec.decode_planes_device(self.planes, syms.shape[0], bits, stream=stream)
+            self.codec.decode_planes_device(self.planes, syms.shape[0], bits, stream=stream, **es)
         if events is not None:
             events[1].record(stream)
         return bits

@@ -1,0 +1,150 @@
+#!/usr/bin/env python3
+"""Early-stop measurements, one JSON document on stdout.
+
+  python tools/es_measure.py latency    [--parent lib/libtdec_parent.so]
+  python tools/es_measure.py throughput [--batch 65536]
+
+latency: one host-pointer decode per call (what DVBRCS2_Turbo.decode() costs below
+its numpy conversions: the C call tdec_decode_batch / tdec_decode_batch_es with B = 1)
+at N = 48 / 212 / 752 r = 1/3, valid-perm, BPSK LLRs at 2 / 4 / 8 dB, 20 frames per
+point, the variants interleaved call by call in one process: this build's plain
+decode, this build's early-stop decode and, with --parent, the parent commit's plain
+decode from its own library (a second code object in the same process, as
+tools/ab.py loads it).  Median ms per call and the mean n_iter.
+
+throughput: the configs[2] shape (16QAM, N = 752 r = 1/3, valid-perm) at 2 and 6 dB,
+device-resident planes: the frame kernel with early stop (tdec_decode_planes_es_dev,
+every batch size) against the tile decoder at 8 fixed iterations
+(tdec_decode_planes_dev), HIP events, median of 5."""
+import argparse
+import ctypes as C
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+
+from modulations_amd import _native, tables as T  # noqa: E402
+from modulations_amd import dvb_rcs2_turbo as M  # noqa: E402
+
+
+def open_lib(path):
+    L = C.CDLL(os.path.abspath(path))
+    _native._declare(L)
+    return L
+
+
+def make_handle(L, codec, iters=8):
+    tabs = T.packed_tables(codec.next_state, codec.out_W, codec.out_Y, codec.prev_state, codec.prev_input)
+    pm = np.ascontiguousarray(T.puncture_matrix(codec.punct))
+    h = C.c_void_p()
+    rc = L.tdec_create(0, codec.N, codec.punct["period"], pm.ctypes.data, iters, codec.algo, codec.perm.ctypes.data,
+                       codec.inv_perm.ctypes.data, tabs.ctypes.data, C.byref(h))
+    assert rc == 0, L.tdec_last_error()
+    return h
+
+
+def latency(a):
+    import early_stop_ref as R
+    cur = _native.lib()
+    par = open_lib(a.parent) if a.parent else None
+    out = {"what": "host-pointer decode of one frame per call, median ms of the C call", "frames": 20, "reps": a.reps,
+           "points": []}
+    for n in (48, 212, 752):
+        codec = M.DVBRCS2_Turbo(n, "1/3", interleaver="valid-perm")
+        hc = make_handle(cur, codec)
+        hp = make_handle(par, codec) if par else None
+        for ebn0 in (2.0, 4.0, 8.0):
+            _, llr = R.bpsk_llrs(codec, np.random.default_rng(n), 20, ebn0)
+            bits = np.zeros(codec.k_info, np.int32)
+            nit = np.zeros(1, np.int32)
+            variants = {"plain": lambda f: cur.tdec_decode_batch(hc, 1, f.ctypes.data, f.size, bits.ctypes.data, None),
+                        "early_stop": lambda f: cur.tdec_decode_batch_es(hc, 1, f.ctypes.data, f.size, bits.ctypes.data,
+                                                                         None, nit.ctypes.data)}
+            if par:
+                variants["parent_plain"] = lambda f: par.tdec_decode_batch(hp, 1, f.ctypes.data, f.size,
+                                                                           bits.ctypes.data, None)
+            order = list(variants)[::-1] if a.reverse else list(variants)
+            ts = {k: [] for k in variants}
+            its = []
+            for rep in range(a.reps + 1):   # the first pass warms up
+                for f in llr:
+                    for k in order:
+                        t0 = time.perf_counter()
+                        rc = variants[k](f)
+                        dt = time.perf_counter() - t0
+                        assert rc == 0
+                        if rep:
+                            ts[k].append(dt)
+                            if k == "early_stop":
+                                its.append(int(nit[0]))
+            rec = {"N": n, "ebn0_db": ebn0, "order": order, "mean_n_iter": float(np.mean(its))}
+            rec.update({k + "_ms": round(float(np.median(v)) * 1e3, 4) for k, v in ts.items()})
+            ref = rec.get("parent_plain_ms", rec["plain_ms"])
+            rec["early_stop_over_" + ("parent" if par else "plain")] = round(rec["early_stop_ms"] / ref, 3)
+            if par:
+                rec["plain_over_parent"] = round(rec["plain_ms"] / rec["parent_plain_ms"], 3)
+            out["points"].append(rec)
+        cur.tdec_destroy(hc)
+        if par:
+            par.tdec_destroy(hp)
+    print(json.dumps(out, indent=1))
+
+
+def throughput(a):
+    import torch
+    from modulations_amd import demap as D
+    from modulations_amd.workload import make_symbols
+    dev = torch.device("cuda", 0)
+    B = a.batch
+    out = {"what": "decode of device-resident planes, HIP events, median ms of 5", "batch": B, "N": 752, "rate": "1/3",
+           "mod": "16QAM", "interleaver": "valid-perm", "points": []}
+    plain = M.DVBRCS2_Turbo(752, "1/3", interleaver="valid-perm")
+    es = M.DVBRCS2_Turbo(752, "1/3", interleaver="valid-perm", early_stop=True)
+    cons = D.constellation("16QAM")
+    planes = torch.empty(plain.planes_bytes(B) // 4, dtype=torch.float32, device=dev)
+    plain.reserve(B)
+    bits = [torch.empty((B, plain.k_info), dtype=torch.int32, device=dev) for _ in range(2)]
+    nit = torch.zeros(B, dtype=torch.int32, device=dev)
+    for ebn0 in (2.0, 6.0):
+        _, syms, n0 = make_symbols(plain, B, "16QAM", ebn0, 7, dev, want_info=False)
+        _, div32, nve = D.demap_mode(np.complex64, cons.dtype, np.float64(n0))
+        plain.demap_planes_device(syms, cons, 4, nve, planes, div_f32=div32)
+        ms = {"tile_8_iterations": [], "frame_early_stop": []}
+        for rep in range(6):
+            for k, fn in (("tile_8_iterations", lambda: plain.decode_planes_device(planes, B, bits[0])),
+                          ("frame_early_stop", lambda: es.decode_planes_device(planes, B, bits[1], n_iter=nit))):
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                fn()
+                e1.record()
+                torch.cuda.synchronize()
+                if rep:
+                    ms[k].append(e0.elapsed_time(e1))
+        rec = {"ebn0_db": ebn0, "mean_n_iter": float(nit.double().mean()),
+               "rows_where_bits_differ": int((bits[0] != bits[1]).any(1).sum())}
+        for k, v in ms.items():
+            rec[k + "_ms"] = round(float(np.median(v)), 3)
+            rec[k + "_cw_per_s"] = round(B / (float(np.median(v)) * 1e-3))
+        out["points"].append(rec)
+    print(json.dumps(out, indent=1))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("what", choices=["latency", "throughput"])
+    ap.add_argument("--parent", default=None, help="the parent commit's libtdec.so (latency)")
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--reverse", action="store_true", help="latency: time the variants in the opposite order")
+    ap.add_argument("--batch", type=int, default=65536)
+    a = ap.parse_args()
+    (latency if a.what == "latency" else throughput)(a)
+
+
+if __name__ == "__main__":
+    main()
