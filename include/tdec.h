@@ -155,6 +155,24 @@ int tdec_es_capacity(tdec_t *h);
  * this process (host only: no handle, no device call), else 0. */
 int tdec_early_stop_available(int n_couples);
 
+/* The same rule on the throughput tile decoder (64 codewords per wave, one per
+ * lane): a lane leaves the iterations on its own, the wave goes
+ * on to its next tile once its 64 codewords have ended.  Same outputs, bit for
+ * bit, as the calls above (max-log and log-MAP); d_lfinal / d_n_iter nullable.
+ * For batches: every block size of the tables (N > 805 included), independent
+ * of TDEC_FRAME.  Capacity as tdec_decode_planes_dev / tdec_decode_batch_dev:
+ * tdec_reserve(max_batch) first, a larger _dev call is TDEC_ECAPACITY and writes
+ * nothing; the host-pointer call reserves and chunks like tdec_decode_batch
+ * (TDEC_HOST_CHUNK).  With iterations = 1 this is the plain decode, n_iter = 1.
+ * TDEC_ES_TILE_WAVES in the environment (read per call) caps the persistent
+ * waves of a launch (diagnostics and tests). */
+int tdec_decode_batch_es_tile(tdec_t *h, int B, const float *llr, long llr_stride, int32_t *bits, double *lfinal,
+                              int32_t *n_iter);
+int tdec_decode_planes_es_tile_dev(tdec_t *h, int B, const float *d_planes, int32_t *d_bits, double *d_lfinal,
+                                   int32_t *d_n_iter, void *stream);
+int tdec_decode_batch_es_tile_dev(tdec_t *h, int B, const float *d_llr, long llr_stride, int32_t *d_bits,
+                                  double *d_lfinal, int32_t *d_n_iter, void *stream);
+
 /* Soft demapper: compute_llr (test_sdr_with_coding.py:200-225) over any
  * labelled constellation (label i = bits MSB first).  syms: n_sym complex
  * values (f32 pairs, or f64 pairs when sym_f64); cons: M points (host memory,

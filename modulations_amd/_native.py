@@ -33,6 +33,7 @@ EXPORTS = (
     "tdec_siso_staged", "tdec_siso_stats",
     "tdec_decode_batch_es", "tdec_decode_planes_es_dev", "tdec_decode_batch_es_dev", "tdec_es_capacity",
     "tdec_early_stop_available",
+    "tdec_decode_batch_es_tile", "tdec_decode_planes_es_tile_dev", "tdec_decode_batch_es_tile_dev",
 )
 
 _lib = None
@@ -78,6 +79,12 @@ def _declare(L):
         L.tdec_early_stop_available.argtypes = [C.c_int]
         for f in (L.tdec_decode_batch_es, L.tdec_decode_planes_es_dev, L.tdec_decode_batch_es_dev, L.tdec_es_capacity,
                   L.tdec_early_stop_available):
+            f.restype = C.c_int
+    if hasattr(L, "tdec_decode_batch_es_tile"):   # (A/B tools also load older builds without the tile early stop)
+        L.tdec_decode_batch_es_tile.argtypes = [_vp, C.c_int, _vp, C.c_long, _vp, _vp, _vp]
+        L.tdec_decode_planes_es_tile_dev.argtypes = [_vp, C.c_int, _vp, _vp, _vp, _vp, _vp]
+        L.tdec_decode_batch_es_tile_dev.argtypes = [_vp, C.c_int, _vp, C.c_long, _vp, _vp, _vp, _vp]
+        for f in (L.tdec_decode_batch_es_tile, L.tdec_decode_planes_es_tile_dev, L.tdec_decode_batch_es_tile_dev):
             f.restype = C.c_int
     if hasattr(L, "tdec_tail_gate"):   # (A/B tools also load older builds without it)
         L.tdec_tail_gate.argtypes = [_vp, _vp]

@@ -15,7 +15,7 @@ only those int64 counters are all-reduced.  Finished points are written to
 §5).  The file records the sweep's configuration and the generator version;
 a rerun into it with any other configuration (modulation, block size, rate,
 algorithm, iterations, interleaver, codewords per point, base seed, early
-stop) or generator is refused instead of mixing two data streams, and each point's
+stop and its decoder) or generator is refused instead of mixing two data streams, and each point's
 generator key is derived from its Eb/N0 value (not its index in --ebn0), so a
 resumed sweep over a different grid regenerates exactly the same data.
 """
@@ -49,6 +49,8 @@ def sweep_config(a, inv_perm=None):
            "seed": int(a.seed)}
     if getattr(a, "early_stop", False):   # (absent without the flag: files of earlier sweeps keep resuming)
         cfg["early_stop"] = True
+        if getattr(a, "es_decoder", "frame") != "frame":   # (absent at the default, for the same reason)
+            cfg["es_decoder"] = a.es_decoder
     if inv_perm is not None:
         cfg["inv_perm_digest"] = interleaver_digest(inv_perm)
     return cfg
@@ -116,13 +118,7 @@ def run_point(pipe, codec, mod, ebn0, start, count, batch, seed, device, times=N
     return cnt
 
 
-def main(argv=None):
-    import torch
-    import torch.distributed as dist
-    from . import dvb_rcs2_turbo as M
-    from . import sharding as S
-    from .workload import DevicePipeline
-
+def arg_parser():
     ap = argparse.ArgumentParser()
     ap.add_argument("--mod", default="256QAM")
     ap.add_argument("--n", "--couples", dest="n", type=int, default=752)
@@ -137,10 +133,23 @@ def main(argv=None):
     ap.add_argument("--early-stop", action="store_true",
                     help="stop each codeword once its hard decisions repeat (--iterations is the cap); "
                          "records mean_iters and iter_hist per point")
+    ap.add_argument("--es-decoder", choices=["frame", "tile"], default="frame",
+                    help="with --early-stop: the frame decoder (default) or the throughput tile decoder")
     ap.add_argument("--out", default=None)
     ap.add_argument("--dist-backend", default="nccl", help="nccl (= RCCL) on the node; gloo to rehearse")
     ap.add_argument("--all-on-device0", action="store_true", help="every rank on GPU 0 (rehearsal on a 1-GPU box)")
     ap.add_argument("--dist-timeout", type=float, default=300.0, help="torch.distributed timeout (s)")
+    return ap
+
+
+def main(argv=None):
+    import torch
+    import torch.distributed as dist
+    from . import dvb_rcs2_turbo as M
+    from . import sharding as S
+    from .workload import DevicePipeline
+
+    ap = arg_parser()
     a = ap.parse_args(argv)
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -151,7 +160,7 @@ def main(argv=None):
     # the codec touches no GPU until its first call: its inv_perm keys the sweep
     try:
         host_codec = M.DVBRCS2_Turbo(a.n, a.rate, a.iterations, algo=a.algo, interleaver=a.interleaver,
-                                     early_stop=a.early_stop)
+                                     early_stop=a.early_stop, es_decoder=a.es_decoder)
     except ValueError as e:
         ap.error(str(e))
     cfg = sweep_config(a, host_codec.inv_perm)
@@ -170,7 +179,7 @@ def main(argv=None):
             dist.init_process_group(a.dist_backend, timeout=to)
     device = torch.device("cuda", dev_idx)
     codec = M.DVBRCS2_Turbo(a.n, a.rate, a.iterations, algo=a.algo, interleaver=a.interleaver,
-                            device=device.index, early_stop=a.early_stop)
+                            device=device.index, early_stop=a.early_stop, es_decoder=a.es_decoder)
     if world > 1:   # every rank must decode with the same de-interleaver
         S.check_same_interleaver(codec.inv_perm, dist, device if a.dist_backend == "nccl" else "cpu")
     pipe = DevicePipeline(codec, a.mod, a.batch, device)
@@ -205,6 +214,8 @@ def main(argv=None):
         if a.early_stop:
             h = [int(x) for x in cnt[3:].tolist()]
             rec["early_stop"] = True
+            if a.es_decoder != "frame":
+                rec["es_decoder"] = a.es_decoder
             rec["iter_hist"] = h   # iter_hist[i]: codewords that ran i iterations
             rec["mean_iters"] = sum(i * c for i, c in enumerate(h)) / max(1, ncw)
         results.append(rec)

@@ -340,6 +340,14 @@ const void *decode_kernel(int algo, bool ragged) {
     return ragged ? (const void *)k_turbo_decode<true> : (const void *)k_turbo_decode<false>;
 }
 
+typedef void (*decode_es_fn)(DecodeArgs, const int *, const int *, const int *, EsArgs);
+
+const void *decode_es_kernel(int algo, bool ragged) {
+    if (algo)
+        return ragged ? (const void *)k_turbo_decode_logmap_es<true> : (const void *)k_turbo_decode_logmap_es<false>;
+    return ragged ? (const void *)k_turbo_decode_es<true> : (const void *)k_turbo_decode_es<false>;
+}
+
 }  // namespace
 
 constexpr size_t SIMD_PROG_BYTES = sizeof(int) * 8192 * 16;   // [XCC, SE, SH, CU, SIMD] key x 16 wave slots
@@ -371,6 +379,7 @@ struct tdec_ctx {
     unsigned tail_seq = 0;             // sequence number of its last whole-tile launch
     int *d_simd_prog = nullptr;        // max-log issue priority: per-SIMD progress slots (zeroed before each launch)
     float4 *ck_p = nullptr;            //   alpha checkpoints + beta1 ring (inside ws)
+    uint32_t *prev_p = nullptr;        //   the early-stop tile loop's previous decisions (inside ws, last)
     int ws_waves = 0;
     DevBuf planes_own;                 // planes for tdec_decode_batch(_dev)
     int cap_batch = 0;
@@ -789,6 +798,7 @@ static int n_tiles_of(int B) { return (B + WAVE - 1) / WAVE; }
 static long ws_stride_of(const tdec_t *h) { return 3L * rows_of(h->N) * WAVE; }
 static int ck_rows_of(const tdec_t *h) { return (h->N + ck_win_of(h->algo) - 1) / ck_win_of(h->algo); }
 static long ck_stride_of(const tdec_t *h) { return (long)(ck_rows_of(h) + RING) * 4 * WAVE; }
+static size_t es_prev_rows_of(const tdec_t *h) { return ((size_t)h->N + 15) / 16; }
 
 // The decoders' tile queue: the counter zeroed on the launch's stream, or null
 // (static striding) below 4 tiles per wave.  Measured (same bits): 1 M codewords
@@ -831,7 +841,10 @@ static int ensure_ws(tdec_t *h, int waves) {
     // aux: the all-zero a-priori row of the first iteration (64 lanes, zeroed
     // below) and one sink row per wave for the stores the decoder discards
     const size_t aux_off = ck_off + row * (ck_stride_of(h) / WAVE) * sizeof(float4);
-    const size_t total = aux_off + ((size_t)WAVE + row) * sizeof(double2);
+    // the early-stop tile loop's previous hard decisions: ceil(N / 16) rows of uint32,
+    // appended, so the regions above stay where they were
+    const size_t prev_off = aux_off + ((size_t)WAVE + row) * sizeof(double2);
+    const size_t total = prev_off + row * es_prev_rows_of(h) * sizeof(uint32_t);
     bool placed = false;
     if (total >= (1ul << 30)) {
         h->ws.release();
@@ -848,6 +861,7 @@ static int ensure_ws(tdec_t *h, int waves) {
     h->le_p = (double2 *)h->ws.p;
     h->ck_p = (float4 *)((char *)h->ws.p + ck_off);
     h->aux_p = (double2 *)((char *)h->ws.p + aux_off);
+    h->prev_p = (uint32_t *)((char *)h->ws.p + prev_off);
     HIPCHK(hipMemsetAsync(h->aux_p, 0, WAVE * sizeof(double2), h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
     h->ws_waves = waves;
@@ -1181,6 +1195,105 @@ int tdec_decode_batch_es_dev(tdec_t *h, int B, const float *d_llr, long llr_stri
                                            d_n_iter ? d_n_iter + r0 : nullptr, stream);
         if (rc) return rc;
     }
+    return 0;
+}
+
+// ---- early stop on the throughput tile decoder ---------------------------
+// k_turbo_decode_es / k_turbo_decode_logmap_es: the persistent tile loop with per-lane
+// termination.  Every batch size and every N of the tables runs on it (no frame kernel:
+// TDEC_FRAME does not matter).  Capacity as tdec_decode_planes_dev: tdec_reserve sizes
+// the workspace and a larger call is TDEC_ECAPACITY; a batch that tdec_reserve covered
+// with the small-batch decoders' workspace only gets the tile workspace on first use.
+// Tiles take different times here, so the launch draws tiles from the queue whenever a
+// wave serves more than one (tile_queue()'s 4 x waves threshold is a measurement of the
+// fixed-iteration kernel).  TDEC_ES_TILE_WAVES (read per call) caps the persistent waves
+// of the launch: tests make one or two waves serve several tiles with it.
+int tdec_decode_planes_es_tile_dev(tdec_t *h, int B, const float *d_planes, int32_t *d_bits, double *d_lfinal,
+                                   int32_t *d_n_iter, void *stream) {
+    if (!h || B < 0) return fail(TDEC_EINVAL, "bad decode arguments");
+    if (B == 0) return 0;
+    if (!d_planes || !d_bits) return fail(TDEC_EINVAL, "bad decode arguments");
+    Guard g(h->device);
+    hipStream_t st = (hipStream_t)stream;
+    const int tiles = n_tiles_of(B);
+    const int full = std::min(tiles, h->max_waves);
+    if (full > h->ws_waves) {
+        if (B > h->cap_batch) return fail(TDEC_ECAPACITY, "workspace too small: call tdec_reserve first");
+        quiesce(h);   // regrowth frees
+        if (int rc = ensure_ws(h, full)) return rc;
+    }
+    int waves = full;
+    if (const char *pc = getenv("TDEC_ES_TILE_WAVES")) waves = std::max(1, std::min(waves, atoi(pc)));
+    if (int rc = order_on(h, st)) return rc;
+    int *queue = nullptr;
+    if (tiles > waves) {
+        HIPCHK(hipMemsetAsync(h->d_tile_ctr, 0, sizeof(int), st));
+        queue = h->d_tile_ctr;
+    }
+    DecodeArgs a{B, h->N, h->iters, tiles, waves, d_planes, h->le_p, h->ck_p, d_bits, d_lfinal, h->d_used,
+                 waves * WAVE, h->aux_p, queue, ck_rows_of(h)};
+    if (h->d_simd_prog && hipMemsetAsync(h->d_simd_prog, 0, SIMD_PROG_BYTES, st) == hipSuccess) a.simd_prog = h->d_simd_prog;
+    const EsArgs e{d_n_iter, h->prev_p};
+    const int *pm = h->d_perm, *iv = h->d_inv;
+    const dim3 grid((waves + DEC_WAVES - 1) / DEC_WAVES);
+    hipLaunchKernelGGL((decode_es_fn)decode_es_kernel(h->algo, h->N % win_of(h->algo) != 0), grid, dim3(DEC_BLOCK), 0,
+                       st, a, pm, iv, (const int *)h->d_used, e);
+    HIPCHK(hipGetLastError());
+    return mark_used(h, st);
+}
+
+int tdec_decode_batch_es_tile_dev(tdec_t *h, int B, const float *d_llr, long llr_stride, int32_t *d_bits,
+                                  double *d_lfinal, int32_t *d_n_iter, void *stream) {
+    if (!h || B < 0) return fail(TDEC_EINVAL, "bad decode arguments");
+    if (B == 0) return 0;
+    if (!d_llr || !d_bits) return fail(TDEC_EINVAL, "bad decode arguments");
+    if (B > h->cap_batch) return fail(TDEC_ECAPACITY, "batch larger than tdec_reserve()");
+    if (int rc = order_on(h, (hipStream_t)stream)) return rc;   // planes_own may still be read elsewhere
+    int rc = tdec_depuncture_dev(h, B, d_llr, llr_stride, (float *)h->planes_own.p, stream);
+    if (!rc)
+        rc = tdec_decode_planes_es_tile_dev(h, B, (const float *)h->planes_own.p, d_bits, d_lfinal, d_n_iter, stream);
+    return rc;
+}
+
+// The host-pointer call: chunks of tdec_decode_batch's size (TDEC_HOST_CHUNK overrides
+// it), one after the other on the handle's stream.
+int tdec_decode_batch_es_tile(tdec_t *h, int B, const float *llr, long llr_stride, int32_t *bits, double *lfinal,
+                              int32_t *n_iter) {
+    if (!h || B < 0) return fail(TDEC_EINVAL, "bad decode arguments");
+    if (llr_stride < h->llr_len) return fail(TDEC_ESHORT, "llr rows shorter than the de-puncture walk");
+    if (B == 0) return 0;
+    if (!llr || !bits) return fail(TDEC_EINVAL, "bad decode arguments");
+    Guard g(h->device);
+    quiesce(h);
+    long chunk = std::max(1L, (long)h->max_waves / 2) * WAVE;
+    if (const char *pc = getenv("TDEC_HOST_CHUNK")) chunk = std::max(1L, atol(pc));
+    const int C = (int)std::min<long>(B, chunk);
+    const size_t row_b = (size_t)2 * h->N;
+    int rc = tdec_reserve(h, C);
+    if (!rc) rc = h->h_llr.ensure((size_t)C * llr_stride * sizeof(float));
+    if (!rc) rc = h->h_bits.ensure(C * row_b * sizeof(int32_t));
+    if (!rc && lfinal) rc = h->h_lf.ensure(C * row_b * sizeof(double));
+    if (!rc && n_iter) rc = h->h_nit.ensure((size_t)C * sizeof(int32_t));
+    if (rc) return rc;
+    DrainOnExit drain{h->stream, nullptr};
+    for (long r0 = 0; r0 < B; r0 += C) {
+        const size_t n = (size_t)std::min<long>(C, B - r0);
+        HIPCHK(hipMemcpyAsync(h->h_llr.p, llr + r0 * llr_stride, n * llr_stride * sizeof(float), hipMemcpyHostToDevice,
+                              h->stream));
+        if ((rc = tdec_decode_batch_es_tile_dev(h, (int)n, (const float *)h->h_llr.p, llr_stride, (int32_t *)h->h_bits.p,
+                                                lfinal ? (double *)h->h_lf.p : nullptr,
+                                                n_iter ? (int32_t *)h->h_nit.p : nullptr, h->stream)))
+            return rc;
+        HIPCHK(hipMemcpyAsync(bits + r0 * row_b, h->h_bits.p, n * row_b * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+        if (lfinal)
+            HIPCHK(hipMemcpyAsync(lfinal + r0 * row_b, h->h_lf.p, n * row_b * sizeof(double), hipMemcpyDeviceToHost,
+                                  h->stream));
+        if (n_iter)
+            HIPCHK(hipMemcpyAsync(n_iter + r0, h->h_nit.p, n * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+    }
+    HIPCHK(hipStreamSynchronize(h->stream));
+    drain.disarm();
+    mark_idle(h);
     return 0;
 }
 

@@ -313,9 +313,20 @@ template <int E> __device__ __forceinline__ f2 pk_add_bcast(f2 t, f2 y) {
     return r;
 }
 
-template <int ALGO>
+// The extrinsic scaling factor (:496): one value for the wave (double), or, in
+// the early-stop tile loop, 1.0 for the lanes whose current iteration is their
+// final one and 0.7 for the others.  The lanes are a 64-bit mask in an SGPR pair
+// and the factor is two v_cndmask on it where the tail applies it: no VGPR is
+// held for it across the trellis loops.
+struct LaneSf {
+    unsigned long long fin;
+};
+__device__ __forceinline__ double sf_of(double sf) { return sf; }
+__device__ __forceinline__ double sf_of(const LaneSf &s) { return __builtin_amdgcn_inverse_ballot_w64(s.fin) ? 1.0 : 0.7; }
+
+template <int ALGO, class SF>
 __device__ __forceinline__ void extrinsic(const float (&a)[NS], const float (&g)[8], const float (&b1)[NS], double inA,
-                                          double inB, double sf, double &leA, double &leB) {
+                                          double inB, SF sf, double &leA, double &leB) {
     float LpA, LpB;
     if constexpr (ALGO == 0) {
         float app[4];
@@ -381,8 +392,8 @@ __device__ __forceinline__ void extrinsic(const float (&a)[NS], const float (&g)
         LpB = jac(app[0], app[2]) - jac(app[1], app[3]);
     }
     // bits -> nats (log-MAP), then the reference's f64 tail (:262-281)
-    double x = ((ALGO ? (double)LpA * LM_LN2 : (double)LpA) - inA) * sf;
-    double y = ((ALGO ? (double)LpB * LM_LN2 : (double)LpB) - inB) * sf;
+    double x = ((ALGO ? (double)LpA * LM_LN2 : (double)LpA) - inA) * sf_of(sf);
+    double y = ((ALGO ? (double)LpB * LM_LN2 : (double)LpB) - inB) * sf_of(sf);
     x = x > 300.0 ? 300.0 : x;
     x = x < -300.0 ? -300.0 : x;
     y = y > 300.0 ? 300.0 : y;
@@ -710,10 +721,10 @@ __device__ __forceinline__ void store_vec(float4 *c, unsigned cs, unsigned base,
 // unconditional (the last window re-loads its own rows), so the number of
 // memory operations issued after them is the same on every path and the
 // compiler's wait counts stay exact.
-template <int ALGO, int W, bool RAG, class In, class Out>
+template <int ALGO, int W, bool RAG, class In, class Out, class SF>
 __device__ __forceinline__ void back_window(const In &in, const Out &out, int k0, int len, Raw (&raw)[W],
                                             float (&an)[NS], float (&b)[NS], const float4 *ck, unsigned cs, int lane,
-                                            int N, double sf) {
+                                            int N, SF sf) {
     // len = steps in this window (W except for a ragged top window when W does not divide N)
     float gw[W][8], lcA[W], lcB[W];
     double iAw[W], iBw[W];
@@ -901,9 +912,9 @@ __device__ __forceinline__ void phase_prio(bool forward, const Prio &pr) {
 // The SISO with checkpoints every W steps (the row SISO, the fused demap-decode
 // kernel and the log-MAP throughput decoder; max-log's throughput decoder runs
 // siso8 below).
-template <int ALGO, int W, bool RAG, class In, class Out>
+template <int ALGO, int W, bool RAG, class In, class Out, class SF>
 __device__ void siso(const In &in, const Out &out, int N, float4 *ck, float4 *ring, unsigned cs, int lane,
-                     double sf) {
+                     SF sf) {
     const int top = RAG ? ((N - 1) / W) * W : N - W;   // start of the (possibly short) top window
     constexpr int RSTEP = rstep_of(W);
     Raw raw[W];
@@ -993,10 +1004,10 @@ __device__ void siso(const In &in, const Out &out, int N, float4 *ck, float4 *ri
 
 // Positions kb+3 .. kb of a half window (kb+len-1 .. kb if ragged), alpha[kb]
 // given, midpoint recompute as back_window.
-template <int ALGO, bool RAG, class Out>
+template <int ALGO, bool RAG, class Out, class SF>
 __device__ __forceinline__ void window_half(const Out &out, int kb, int len, const float (&a0)[NS],
                                             const float (&gw)[4][8], const double (&iAw)[4], const double (&iBw)[4],
-                                            const float (&lcA)[4], const float (&lcB)[4], float (&b)[NS], double sf) {
+                                            const float (&lcA)[4], const float (&lcB)[4], float (&b)[NS], SF sf) {
     constexpr int H = 2;
     float am[NS];
 #pragma unroll
@@ -1053,11 +1064,11 @@ __device__ __forceinline__ void ck_read(const lds_f4 *slot, int lane, float (&x)
         x[vec_elem<true>(q, 3)] = v.w;
     }
 }
-template <int ALGO, bool RAG, class In, class Out>
+template <int ALGO, bool RAG, class In, class Out, class SF>
 __device__ __forceinline__ void back_window8(const In &in, const Out &out, int k0, int len, Raw (&rt)[4],
                                              const LdsStage &st, const LdsStage &sn,
                                              float (&b)[NS], const float4 *ck, unsigned cs, int lane, int N,
-                                             double sf) {
+                                             SF sf) {
     const int lenT = RAG ? (len > 4 ? len - 4 : 0) : 4;
     const int lenB = RAG ? (len < 4 ? len : 4) : 4;
     const int kn = k0 >= 8 ? k0 - 8 : 0;   // the next window
@@ -1149,8 +1160,8 @@ __device__ __forceinline__ void pass_mark(unsigned long long &, int) {}
 __device__ __forceinline__ void merge_mark(int, int, int) {}
 #endif
 
-template <int ALGO, bool RAG, class In, class Out>
-__device__ void siso8(const In &in, const Out &out, int N, float4 *ck, float4 *ring, unsigned cs, int lane, double sf,
+template <int ALGO, bool RAG, class In, class Out, class SF>
+__device__ void siso8(const In &in, const Out &out, int N, float4 *ck, float4 *ring, unsigned cs, int lane, SF sf,
                       const LdsStage &lb, const LdsStage &lb1, const Prio &pr = Prio{}) {
     unsigned long long tpass = TDEC_PASS_TIMING ? __builtin_amdgcn_s_memtime() : 0;
     phase_prio(true, pr);
@@ -1295,9 +1306,9 @@ __host__ __device__ constexpr int win_unstaged(int algo) { return algo ? WIN_LM 
 // (win_of) and the fused demap-decode kernel (win_unstaged).
 __host__ __device__ constexpr int cmin(int a, int b) { return a < b ? a : b; }
 __host__ __device__ constexpr int ck_win_of(int algo) { return cmin(WIN, cmin(win_of(algo), win_unstaged(algo))); }
-template <int ALGO, bool RAG, bool STAGED, class In, class Out>
+template <int ALGO, bool RAG, bool STAGED, class In, class Out, class SF>
 __device__ __forceinline__ void run_siso(const In &in, const Out &out, int N, float4 *ck, float4 *ring, unsigned cs,
-                                         int lane, double sf, float4 *lv, double2 *ll, const Prio &pr = Prio{}) {
+                                         int lane, SF sf, float4 *lv, double2 *ll, const Prio &pr = Prio{}) {
     if constexpr (ALGO == 0 && STAGED) {
         const int w = threadIdx.x >> 6;
         lds_f4 *v = (lds_f4 *)lv;
@@ -1344,6 +1355,14 @@ struct DecodeArgs {
     unsigned tail_seq = 0;
 };
 
+// What the early-stop tile loop (turbo_decode_tiles<..., ES = true>) takes beyond DecodeArgs.
+struct EsArgs {
+    int32_t *n_iter = nullptr;   // [B]: iterations run per codeword, or null
+    // [ceil(N / 16)][n_waves][64]: a lane's hard decisions of the previous iteration, 2 bits
+    // per couple, rows interleaving the waves like the other workspace rows
+    uint32_t *prev = nullptr;
+};
+
 // DVBRCS2_Turbo.decode (:464-537) for 64 codewords per wave, persistent over tiles.
 // Where a tile's planes come from.  PlanesIn: the caller's plane buffer
 // (tdec_decode_planes_dev); fill / publish are no-ops.  The fused demap
@@ -1380,11 +1399,23 @@ __device__ unsigned g_wave_hw[WT_MAX][2];   // HW_ID (wave, SIMD, CU, SH, SE fie
 // measured slower at configs[1]: 10.74 vs 9.65 ms per 102 400 codewords, the clock
 // 1.68 vs 1.83 GHz: the extra waves' instruction streams cost more power than the
 // balance saved, profiles/r06a/, DESIGN.md appendix.)
-template <int ALGO, bool RAG, bool STAGED = false, class Pro = PlanesIn>
+//
+// ES (early stop): every lane leaves the iterations on its own.
+// Two wave-uniform lane masks carry the state: `fin` (the lane's current iteration
+// is its final one: it runs at sf = 1.0 beside neighbours at 0.7) and `done` (the
+// lane's outputs are written; it keeps executing and its values are discarded).
+// After SISO 2 of every iteration the decision loop of the epilogue runs: a lane
+// in `fin` writes its bits / L_final / n_iter and moves to `done`; any other
+// compares its 2N decisions with the previous iteration's (D_0: the signs of the
+// systematic LLRs) and, when all agree, enters `fin` for the next trip.  The tile
+// is retired when `done` covers the wave.  Le1 is stored densely on every
+// iteration (the check reads it), as in the frame kernel's ES variant.
+template <int ALGO, bool RAG, bool STAGED = false, class Pro = PlanesIn, bool ES = false>
 __device__ __forceinline__ void turbo_decode_tiles(const DecodeArgs &p, const int *__restrict__ perm,
                                                    const int *__restrict__ inv, const int *__restrict__ used,
                                                    float4 *lv, double2 *ll,
-                                                   uint32_t *epi, const Pro &pro = Pro{}, int epi_stride = 2 * WAVE) {
+                                                   uint32_t *epi, const Pro &pro = Pro{}, int epi_stride = 2 * WAVE,
+                                                   const EsArgs &es = EsArgs{}) {
     const int lane = threadIdx.x & (WAVE - 1);
     const int wave = __builtin_amdgcn_readfirstlane(blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6));
     if (wave >= p.n_waves) return;
@@ -1423,6 +1454,7 @@ __device__ __forceinline__ void turbo_decode_tiles(const DecodeArgs &p, const in
     // (the kernel's instruction footprint is shared by the CU's waves).
     int tile = wave, it = 0, nxt = 0;
     bool has_next = false;
+    [[maybe_unused]] unsigned long long fin = 0, done = 0;   // ES: lane masks (SGPR pairs)
     for (;;) {
         if (tile >= p.n_tiles) break;
         if (it == 0) {
@@ -1435,11 +1467,24 @@ __device__ __forceinline__ void turbo_decode_tiles(const DecodeArgs &p, const in
             has_next = nxt < p.n_tiles;
             if (p.tail_flag && lane == 0 && (p.tile_ctr ? !has_next : tile == p.n_tiles - 1))
                 atomicMax(p.tail_flag, p.tail_seq);
+            if constexpr (ES) {   // a new tile: the padding lanes of a partial last tile never emit
+                done = ~__builtin_amdgcn_ballot_w64((long)tile * WAVE + lane < p.B);
+                fin = 0;
+            }
         }
         const float *base = pro.tile_planes(tile, wave, N, buf);
         const float4 *X = reinterpret_cast<const float4 *>(base);
         const float2 *Z = reinterpret_cast<const float2 *>(base + NW * 4);
-        {
+        if constexpr (ES) {
+            if (it >= p.iters - 1) fin = ~done;   // the cap: every lane still decoding ends here
+            const LaneSf sf{fin};
+            run_siso<ALGO, RAG, STAGED>(TileIn{X, it ? Le2 : p.aux, inv, lane, it ? rs : 0u},
+                                        TileOutPre{P1, Le1, lane, rs, used, sink}, N, ck, ring, rs, lane, sf, lv, ll, pr);
+            pr.prog += PRIO_UNITS;
+            run_siso<ALGO, RAG, STAGED>(TileInPre{Z, P1, perm, lane, rs}, TileOut{Le2, lane, rs}, N, ck, ring, rs, lane,
+                                        sf, lv, ll, pr);
+            pr.prog += PRIO_UNITS;
+        } else {
             const double sf = it < p.iters - 1 ? 0.7 : 1.0;     // :496
             const bool last = it == p.iters - 1;
             run_siso<ALGO, RAG, STAGED>(TileIn{X, it ? Le2 : p.aux, inv, lane, it ? rs : 0u},
@@ -1451,6 +1496,100 @@ __device__ __forceinline__ void turbo_decode_tiles(const DecodeArgs &p, const in
                                         sf, lv, ll, pr);
             pr.prog += PRIO_UNITS;
             if (has_next) pro.fill(nxt, wave, N, buf ^ 1, 2 * it + 1, 2 * p.iters);
+        }
+        if constexpr (ES) {
+            // The epilogue's decision loop (below: the same loads, the same expression),
+            // after every iteration.
+            const long cw = (long)tile * WAVE + lane;
+            const unsigned long long emit = fin & ~done;   // lanes whose final iteration this was
+            const bool lane_emit = __builtin_amdgcn_inverse_ballot_w64(emit);
+            const bool lane_live = !__builtin_amdgcn_inverse_ballot_w64(done);
+            uint32_t *hb = epi + (threadIdx.x >> 6) * epi_stride;
+            uint32_t *pv = es.prev + (long)wave * WAVE + lane;
+            const long nb = 2L * N;
+            bool same = true;
+            for (int kc = 0; kc < N; kc += 32) {
+                uint32_t w0 = 0, w1 = 0;   // this iteration's decisions,
+                uint32_t q0 = 0, q1 = 0;   // the previous one's
+                double *lo = (p.lfinal && lane_emit) ? p.lfinal + cw * nb : nullptr;
+                const int kn = min(32, N - kc);
+                const unsigned r0 = (unsigned)(kc >> 4) * rs, r1 = r0 + rs;   // rows of w0 / w1 (w1: kn > 16 only)
+                if (it) {
+                    q0 = at(pv, r0);
+                    if (kn > 16) q1 = at(pv, r1);
+                }
+                for (int kg = 0; kg < kn; kg += 8) {
+                    float2 xa[8];
+                    double2 la[8], le[8];
+#pragma unroll
+                    for (int u = 0; u < 8; ++u) {
+                        const int k = min(kc + kg + u, N - 1);   // past the chunk: a valid row, unused
+                        const float4 x = at(X, k * WAVE + lane);
+                        xa[u] = make_float2(x.x, x.y);
+                        la[u] = at(Le2, wsrow(inv[k], rs) + lane);
+                        le[u] = at(Le1, wsrow(k, rs) + lane);
+                    }
+#pragma unroll
+                    for (int u = 0; u < 8; ++u) {
+                        const int kk = kg + u, k = kc + kk;
+                        if (kk >= kn) break;   // wave-uniform
+                        const double fa = ((double)xa[u].x + la[u].x) + le[u].x;
+                        const double fb = ((double)xa[u].y + la[u].y) + le[u].y;
+                        const uint32_t two = (fa < 0.0 ? 1u : 0u) | (fb < 0.0 ? 2u : 0u);
+                        if (kk < 16) w0 |= two << (2 * kk);
+                        else w1 |= two << (2 * (kk - 16));
+                        if (it == 0) {   // D_0: the signs of the systematic channel LLRs
+                            const uint32_t d0 = (xa[u].x < 0.0f ? 1u : 0u) | (xa[u].y < 0.0f ? 2u : 0u);
+                            if (kk < 16) q0 |= d0 << (2 * kk);
+                            else q1 |= d0 << (2 * (kk - 16));
+                        }
+                        if (lo) *reinterpret_cast<double2 *>(lo + 2 * k) = make_double2(fa, fb);
+                    }
+                }
+                same = same && w0 == q0 && w1 == q1;
+                if (lane_live) {   // a done lane stores nothing
+                    at(pv, r0) = w0;
+                    if (kn > 16) at(pv, r1) = w1;
+                }
+                if (emit == 0) continue;   // wave-uniform: no lane ends on this iteration
+                hb[lane] = w0;
+                hb[WAVE + lane] = w1;
+                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+                __builtin_amdgcn_wave_barrier();
+                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+                // the epilogue's 1 KiB-run writer, for the rows that end here only
+                const int per = (2 * kn + 3) / 4;
+                for (int t = lane; t < WAVE * per; t += WAVE) {
+                    const int l = t / per, pc = t - l * per;
+                    if (!((emit >> l) & 1)) continue;   // (rows past B are never in emit)
+                    const long row = (long)tile * WAVE + l;
+                    const uint32_t w = hb[(pc >> 3) * WAVE + l] >> (4 * (pc & 7));
+                    const int j = 4 * pc;
+                    int32_t *dst = p.bits + row * nb + 2L * kc + j;
+                    if (j + 4 <= 2 * kn && (nb & 3) == 0)
+                        *reinterpret_cast<int4 *>(dst) = make_int4(w & 1, (w >> 1) & 1, (w >> 2) & 1, (w >> 3) & 1);
+                    else
+                        for (int e = 0; e < 4 && j + e < 2 * kn; ++e) dst[e] = (w >> e) & 1;
+                }
+                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+                __builtin_amdgcn_wave_barrier();
+                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            }
+            if (lane_emit && es.n_iter) es.n_iter[cw] = it + 1;
+            done |= emit;
+            fin = __builtin_amdgcn_ballot_w64(same) & ~done;   // agreed: the next iteration is the final one
+            if (done != ~0ull) {
+                ++it;
+                continue;
+            }
+            if (has_next) pro.publish();
+            buf ^= 1;
+            tile = nxt;
+            it = 0;
+#if TDEC_WAVE_TIMING
+            ++wtiles;
+#endif
+            continue;
         }
         if (it < p.iters - 1) {
             ++it;
@@ -1561,6 +1700,22 @@ __global__ __launch_bounds__(DEC_BLOCK) __attribute__((amdgpu_waves_per_eu(DEC_W
     DecodeArgs p, const int *__restrict__ perm, const int *__restrict__ inv, const int *__restrict__ used) {
     __shared__ uint32_t epi[DEC_WAVES * 2 * WAVE];
     turbo_decode_tiles<1, RAG>(p, perm, inv, used, nullptr, nullptr, epi, PlanesIn{p.planes});
+}
+// The same two with per-codeword early stop (tdec_decode_*_es_tile*): the caller's planes only.
+template <bool RAG>
+__global__ __launch_bounds__(DEC_BLOCK) __attribute__((amdgpu_waves_per_eu(DEC_WPE))) void k_turbo_decode_es(
+    DecodeArgs p, const int *__restrict__ perm, const int *__restrict__ inv, const int *__restrict__ used, EsArgs es) {
+    __shared__ float4 lv[LDS_LV];
+    __shared__ double2 ll[LDS_STAGE];
+    turbo_decode_tiles<0, RAG, true, PlanesIn, true>(p, perm, inv, used, lv, ll, reinterpret_cast<uint32_t *>(lv),
+                                                     PlanesIn{p.planes}, EPI_STRIDE_ML, es);
+}
+template <bool RAG>
+__global__ __launch_bounds__(DEC_BLOCK) __attribute__((amdgpu_waves_per_eu(DEC_WPE))) void k_turbo_decode_logmap_es(
+    DecodeArgs p, const int *__restrict__ perm, const int *__restrict__ inv, const int *__restrict__ used, EsArgs es) {
+    __shared__ uint32_t epi[DEC_WAVES * 2 * WAVE];
+    turbo_decode_tiles<1, RAG, false, PlanesIn, true>(p, perm, inv, used, nullptr, nullptr, epi, PlanesIn{p.planes},
+                                                      2 * WAVE, es);
 }
 
 // One SISO over B codewords given as [B][N] rows (the bcjr_max_log_map boundary).

@@ -138,12 +138,20 @@ class DVBRCS2_Turbo:
                  repeat (tdec_decode_*_es).  `iterations` is then the
                  cap; each row's result is exactly that of a fixed decode with
                  iterations = its count (decode_batch(return_iters=True),
-                 decode_device(n_iter=)).  Runs on the frame decoder: ValueError
-                 where that is unavailable (TDEC_FRAME=0).
+                 decode_device(n_iter=)).
+      es_decoder which decoder early_stop=True runs on (ignored without it; the
+                 outputs are the same bit for bit):
+                 'frame' (default)  one codeword per workgroup: the lowest latency
+                          per call; ValueError where the frame decoder is
+                          unavailable (TDEC_FRAME=0, N > 805).
+                 'tile'   the throughput decoder (64 codewords per wave), which
+                          retires a tile once all its codewords have stopped
+                          (tdec_decode_*_es_tile*): for batches,
+                          every block size, independent of TDEC_FRAME.
     """
 
     def __init__(self, N_couples, code_rate, iterations=8, *, algo="max-log", inv_perm="numpy",
-                 interleaver="reference", device=None, early_stop=False):
+                 interleaver="reference", device=None, early_stop=False, es_decoder="frame"):
         self.N = N_couples
         self.k_info = N_couples * 2
         self.iterations = iterations
@@ -168,6 +176,9 @@ class DVBRCS2_Turbo:
         self.n_coded = _t.coded_size(self.N, self.punct)
         self.device = _default_device() if device is None else device
         self.early_stop = bool(early_stop)
+        if es_decoder not in ("frame", "tile"):
+            raise ValueError(f"unknown es_decoder {es_decoder!r} ('frame' or 'tile')")
+        self.es_decoder = es_decoder
         if self.early_stop:
             self._require_early_stop()
         self._h = None
@@ -175,7 +186,10 @@ class DVBRCS2_Turbo:
 
     def _require_early_stop(self):
         """ValueError where the early-stop entry points cannot serve this codec (a
-        host-side question: asked before any device work)."""
+        host-side question: asked before any device work).  The tile decoder serves
+        every codec."""
+        if self.es_decoder == "tile":
+            return
         if not _n.lib().tdec_early_stop_available(int(self.N)):
             raise ValueError(f"early_stop=True needs the frame decoder, which is unavailable for N = {self.N} "
                              "in this process (TDEC_FRAME=0, or the block does not fit its LDS plan)")
@@ -251,7 +265,8 @@ class DVBRCS2_Turbo:
         iters = np.full(B, self.iterations, np.int32) if return_iters else None
         if B and self.early_stop:
             self._require_early_stop()
-            h.call("tdec_decode_batch_es", B, _n.ptr(llr), llr.shape[1], _n.ptr(bits), _n.ptr(lf), _n.ptr(iters))
+            h.call("tdec_decode_batch_es_tile" if self.es_decoder == "tile" else "tdec_decode_batch_es", B,
+                   _n.ptr(llr), llr.shape[1], _n.ptr(bits), _n.ptr(lf), _n.ptr(iters))
         elif B:
             h.call("tdec_decode_batch", B, _n.ptr(llr), llr.shape[1], _n.ptr(bits), _n.ptr(lf))
         res = (bits,) + ((lf,) if return_lfinal else ()) + ((iters,) if return_iters else ())
@@ -320,8 +335,8 @@ class DVBRCS2_Turbo:
         if B and llr.shape[1] < self.handle.llr_len:
             raise IndexError(f"index {llr.shape[1]} is out of bounds for axis 0 with size {llr.shape[1]}")
         self._n_iter_check(n_iter, B)
-        if self.early_stop:
-            self._require_early_stop()   # (the early-stop calls size their own workspace)
+        if self.early_stop and self.es_decoder == "frame":
+            self._require_early_stop()   # (the frame early-stop calls size their own workspace)
         else:
             self.reserve(B)
         if bits is None:
@@ -330,7 +345,8 @@ class DVBRCS2_Turbo:
         if lfinal is not None:
             self._dev_check(lfinal, "lfinal", torch.float64, (B, self.k_info))
         if self.early_stop:
-            self.handle.call("tdec_decode_batch_es_dev", B, _n.ptr(llr), llr.stride(0) if B > 1 else llr.shape[1],
+            self.handle.call("tdec_decode_batch_es_tile_dev" if self.es_decoder == "tile"
+                             else "tdec_decode_batch_es_dev", B, _n.ptr(llr), llr.stride(0) if B > 1 else llr.shape[1],
                              _n.ptr(bits), _n.ptr(lfinal), _n.ptr(n_iter), self._stream(stream))
             return bits
         self.handle.call("tdec_decode_batch_dev", B, _n.ptr(llr), llr.stride(0) if B > 1 else llr.shape[1],
@@ -348,7 +364,8 @@ class DVBRCS2_Turbo:
         self._n_iter_check(n_iter, B)
         if self.early_stop:
             self._require_early_stop()
-            self.handle.call("tdec_decode_planes_es_dev", B, _n.ptr(planes), _n.ptr(bits), _n.ptr(lfinal),
+            self.handle.call("tdec_decode_planes_es_tile_dev" if self.es_decoder == "tile"
+                             else "tdec_decode_planes_es_dev", B, _n.ptr(planes), _n.ptr(bits), _n.ptr(lfinal),
                              _n.ptr(n_iter), self._stream(stream))
             return bits
         self.handle.call("tdec_decode_planes_dev", B, _n.ptr(planes), _n.ptr(bits), _n.ptr(lfinal),

@@ -2,7 +2,7 @@
 """Early-stop measurements, one JSON document on stdout.
 
   python tools/es_measure.py latency    [--parent lib/libtdec_parent.so]
-  python tools/es_measure.py throughput [--batch 65536]
+  python tools/es_measure.py throughput [--batch 65536] [--parent lib/libtdec_parent.so] [--reverse]
 
 latency: one host-pointer decode per call (what DVBRCS2_Turbo.decode() costs below
 its numpy conversions: the C call tdec_decode_batch / tdec_decode_batch_es with B = 1)
@@ -12,10 +12,13 @@ decode, this build's early-stop decode and, with --parent, the parent commit's p
 decode from its own library (a second code object in the same process, as
 tools/ab.py loads it).  Median ms per call and the mean n_iter.
 
-throughput: the configs[2] shape (16QAM, N = 752 r = 1/3, valid-perm) at 2 and 6 dB,
-device-resident planes: the frame kernel with early stop (tdec_decode_planes_es_dev,
-every batch size) against the tile decoder at 8 fixed iterations
-(tdec_decode_planes_dev), HIP events, median of 5."""
+throughput: the configs[2] shape (16QAM, N = 752 r = 1/3, valid-perm) at 2, 4 and 6 dB,
+device-resident planes: the tile decoder at 8 fixed iterations (tdec_decode_planes_dev;
+with --parent also the parent commit's, from its own library), the frame kernel with
+early stop (tdec_decode_planes_es_dev) and the tile decoder with early stop
+(tdec_decode_planes_es_tile_dev), interleaved round by round, HIP events:
+median, min and max ms of --reps rounds, the mean n_iter and the mean over tiles of the
+tile's largest n_iter (the iterations the tile decoder runs)."""
 import argparse
 import ctypes as C
 import json
@@ -102,45 +105,79 @@ def throughput(a):
     from modulations_amd.workload import make_symbols
     dev = torch.device("cuda", 0)
     B = a.batch
-    out = {"what": "decode of device-resident planes, HIP events, median ms of 5", "batch": B, "N": 752, "rate": "1/3",
-           "mod": "16QAM", "interleaver": "valid-perm", "points": []}
+    assert B % 64 == 0
+    par = open_lib(a.parent) if a.parent else None
+    out = {"what": "decode of device-resident planes, HIP events, ms over %d timed rounds, the variants "
+                   "interleaved round by round in one process" % a.reps,
+           "batch": B, "N": 752, "rate": "1/3", "mod": "16QAM", "interleaver": "valid-perm", "points": []}
     plain = M.DVBRCS2_Turbo(752, "1/3", interleaver="valid-perm")
-    es = M.DVBRCS2_Turbo(752, "1/3", interleaver="valid-perm", early_stop=True)
+    frame = M.DVBRCS2_Turbo(752, "1/3", interleaver="valid-perm", early_stop=True)
+    tile = M.DVBRCS2_Turbo(752, "1/3", interleaver="valid-perm", early_stop=True, es_decoder="tile")
     cons = D.constellation("16QAM")
     planes = torch.empty(plain.planes_bytes(B) // 4, dtype=torch.float32, device=dev)
     plain.reserve(B)
-    bits = [torch.empty((B, plain.k_info), dtype=torch.int32, device=dev) for _ in range(2)]
-    nit = torch.zeros(B, dtype=torch.int32, device=dev)
-    for ebn0 in (2.0, 6.0):
+    tile.reserve(B)
+    names = ["tile_8_iterations", "frame_early_stop", "tile_early_stop"]
+    bits = {k: torch.empty((B, plain.k_info), dtype=torch.int32, device=dev) for k in names}
+    nit = {k: torch.zeros(B, dtype=torch.int32, device=dev) for k in names[1:]}
+    st = torch.cuda.current_stream()
+    fns = {"tile_8_iterations": lambda: plain.decode_planes_device(planes, B, bits["tile_8_iterations"]),
+           "frame_early_stop": lambda: frame.decode_planes_device(planes, B, bits["frame_early_stop"],
+                                                                  n_iter=nit["frame_early_stop"]),
+           "tile_early_stop": lambda: tile.decode_planes_device(planes, B, bits["tile_early_stop"],
+                                                                n_iter=nit["tile_early_stop"])}
+    if par:   # the parent commit's fixed tile decoder, from its own library
+        hp = make_handle(par, plain)
+        assert par.tdec_reserve(hp, B) == 0, par.tdec_last_error()
+        bits["parent_tile_8_iterations"] = torch.empty_like(bits["tile_8_iterations"])
+        pb = bits["parent_tile_8_iterations"]
+        fns["parent_tile_8_iterations"] = lambda: par.tdec_decode_planes_dev(hp, B, planes.data_ptr(), pb.data_ptr(),
+                                                                             None, st.cuda_stream)
+        names = ["parent_tile_8_iterations"] + names
+    if a.skip_frame:
+        names.remove("frame_early_stop")
+    order = names[::-1] if a.reverse else names
+    out["order"] = order
+    for ebn0 in (2.0, 4.0, 6.0):
         _, syms, n0 = make_symbols(plain, B, "16QAM", ebn0, 7, dev, want_info=False)
         _, div32, nve = D.demap_mode(np.complex64, cons.dtype, np.float64(n0))
         plain.demap_planes_device(syms, cons, 4, nve, planes, div_f32=div32)
-        ms = {"tile_8_iterations": [], "frame_early_stop": []}
-        for rep in range(6):
-            for k, fn in (("tile_8_iterations", lambda: plain.decode_planes_device(planes, B, bits[0])),
-                          ("frame_early_stop", lambda: es.decode_planes_device(planes, B, bits[1], n_iter=nit))):
+        ms = {k: [] for k in order}
+        for rep in range(a.reps + 1):   # the first round warms up
+            for k in order:
                 e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
                 e0.record()
-                fn()
+                fns[k]()
                 e1.record()
                 torch.cuda.synchronize()
                 if rep:
                     ms[k].append(e0.elapsed_time(e1))
-        rec = {"ebn0_db": ebn0, "mean_n_iter": float(nit.double().mean()),
-               "rows_where_bits_differ": int((bits[0] != bits[1]).any(1).sum())}
+        nt = nit["tile_early_stop"]
+        rec = {"ebn0_db": ebn0, "mean_n_iter": float(nt.double().mean()),
+               # the iterations a tile runs: the work the tile decoder actually does
+               "mean_tile_max_n_iter": float(nt.view(-1, 64).max(1).values.double().mean()),
+               "rows_where_bits_differ_from_fixed": int((bits["tile_8_iterations"]
+                                                         != bits["tile_early_stop"]).any(1).sum())}
+        if not a.skip_frame:
+            rec["tile_vs_frame_rows_differing"] = int(((bits["frame_early_stop"] != bits["tile_early_stop"]).any(1)
+                                                      | (nit["frame_early_stop"] != nt)).sum())
         for k, v in ms.items():
             rec[k + "_ms"] = round(float(np.median(v)), 3)
+            rec[k + "_ms_min_max"] = [round(float(np.min(v)), 3), round(float(np.max(v)), 3)]
             rec[k + "_cw_per_s"] = round(B / (float(np.median(v)) * 1e-3))
         out["points"].append(rec)
+    if par:
+        par.tdec_destroy(hp)
     print(json.dumps(out, indent=1))
 
 
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("what", choices=["latency", "throughput"])
-    ap.add_argument("--parent", default=None, help="the parent commit's libtdec.so (latency)")
+    ap.add_argument("--parent", default=None, help="the parent commit's libtdec.so, timed beside this build's")
     ap.add_argument("--reps", type=int, default=5)
-    ap.add_argument("--reverse", action="store_true", help="latency: time the variants in the opposite order")
+    ap.add_argument("--reverse", action="store_true", help="time the variants in the opposite order")
+    ap.add_argument("--skip-frame", action="store_true", help="throughput: leave the frame kernel out")
     ap.add_argument("--batch", type=int, default=65536)
     a = ap.parse_args()
     (latency if a.what == "latency" else throughput)(a)
