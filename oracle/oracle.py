@@ -44,6 +44,14 @@ def lib():
         L.orc_decode_batch.argtypes = [C.c_int, C.c_int, C.c_int, _u8p, C.c_int, C.c_int, _i32p, _i32p,
                                        _i32p, _f32p, C.c_long, C.c_long, _i32p, C.c_void_p, C.c_int]
         L.orc_decode_batch.restype = C.c_int
+        L.orc_siso_depths.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, _f64p, _f64p,
+                                      _i32p, C.c_double, C.c_int, _i32p]
+        L.orc_siso_depths.restype = C.c_int
+        L.orc_decode_depths.argtypes = [C.c_int, C.c_int, _u8p, C.c_int, C.c_int, _i32p, _i32p, _i32p,
+                                        _f32p, C.c_long, _i32p]
+        L.orc_decode_depths.restype = C.c_int
+        L.orc_depuncture.argtypes = [C.c_int, C.c_int, _u8p, _f32p, C.c_long, _f32p]
+        L.orc_depuncture.restype = C.c_int
         L.orc_encode.argtypes = [C.c_int, C.c_int, _u8p, _i32p, _i32p, _i32p, _i32p, _i32p]
         L.orc_encode.restype = C.c_long
         L.orc_demap_c64.argtypes = [_f32p, C.c_long, _f32p, C.c_int, C.c_int, C.c_double, C.c_int, _f64p]
@@ -109,6 +117,47 @@ def siso(LcA, LcB, LcW, LcY, LaA, LaB, tables, sf, algo=0):
         lib().orc_siso64(n, *(c(x, np.float64) for x in lc), c(LaA, np.float64), c(LaB, np.float64),
                          c(tables, np.int32), float(sf), algo, LeA, LeB)
     return LeA, LeB
+
+
+def siso_depths(LcA, LcB, LcW, LcY, LaA, LaB, tables, sf, algo=0):
+    """Where the reference's second passes meet its first, for the inputs of siso()
+    (algo 0 or 1, the same dtype rule): (f2, b2).  f2 is the smallest k in 0..N with
+    alpha2[k] == alpha1[k] on all 16 states, b2 the smallest d in 0..N with
+    beta2[N-d] == beta1[N-d]; -1: no such step.  C ==, so a NaN never merges."""
+    n = len(LcA)
+    lc = [np.asarray(x) for x in (LcA, LcB, LcW, LcY)]
+    f64 = not all(x.dtype == np.float32 for x in lc)
+    lc = [np.ascontiguousarray(x, np.float64 if f64 else np.float32) for x in lc]
+    d = np.zeros(2, np.int32)
+    rc = lib().orc_siso_depths(n, int(f64), *(x.ctypes.data for x in lc), np.ascontiguousarray(LaA, np.float64),
+                               np.ascontiguousarray(LaB, np.float64), np.ascontiguousarray(tables, np.int32),
+                               float(sf), algo, d)
+    if rc:
+        raise ValueError(f"oracle error {rc}")
+    return int(d[0]), int(d[1])
+
+
+def decode_depths(llr, n, period, punct, iterations, perm, inv, tables, algo=0):
+    """siso_depths of every SISO call of decode(): int32 [iterations][2][2], indexed
+    by SISO 1 / SISO 2 and F2 / B2."""
+    llr = np.ascontiguousarray(llr, np.float32)
+    d = np.zeros((iterations, 2, 2), np.int32)
+    rc = lib().orc_decode_depths(n, period, np.ascontiguousarray(punct, np.uint8), iterations, algo,
+                                 np.ascontiguousarray(perm, np.int32), np.ascontiguousarray(inv, np.int32),
+                                 np.ascontiguousarray(tables, np.int32), llr, llr.size, d)
+    if rc:
+        raise IndexError("llr too short") if rc == -1 else ValueError(f"oracle error {rc}")
+    return d
+
+
+def depuncture(llr, n, period, punct):
+    """The de-puncture walk of decode() (:476-487): float32 [6][n] planes
+    A, B, W1, Y1, W2, Y2, punctured entries zero."""
+    llr = np.ascontiguousarray(llr, np.float32)
+    out = np.zeros((6, n), np.float32)
+    if lib().orc_depuncture(n, period, np.ascontiguousarray(punct, np.uint8), llr, llr.size, out):
+        raise IndexError("llr too short")
+    return out
 
 
 def decode(llr, n, period, punct, iterations, perm, inv, tables, algo=0, want_lfinal=False):

@@ -22,6 +22,12 @@ int orc_decode(int N, int period, const uint8_t *punct, int iterations, int algo
 int orc_decode_batch(int B, int N, int period, const uint8_t *punct, int iterations, int algo,
                      const int32_t *perm, const int32_t *inv_perm, const int32_t *tables, const float *llr,
                      long llr_stride, long n_llr, int32_t *bits, double *lfinal, int nthreads);
+int orc_siso_depths(int N, int f64, const void *LcA, const void *LcB, const void *LcW, const void *LcY,
+                     const double *LaA, const double *LaB, const int32_t *tables, double sf, int algo,
+                     int32_t *depths);
+int orc_decode_depths(int N, int period, const uint8_t *punct, int iterations, int algo, const int32_t *perm,
+                      const int32_t *inv_perm, const int32_t *tables, const float *llr, long n_llr,
+                      int32_t *depths);
 long orc_encode(int N, int period, const uint8_t *punct, const int32_t *perm, const int32_t *tables,
                 const int32_t *G, const int32_t *bits, int32_t *coded);
 void orc_demap_c64(const float *syms, long n_sym, const float *cons, int M, int bps, double noise_var,
@@ -87,6 +93,11 @@ int main(void)
                 CHECK(orc_decode(N, period, punct, 1, algo, perm, inv, tables, tail, n_need - 1, bits, NULL) == -1);
                 CHECK(orc_decode(N, period, punct, 0, algo, perm, inv, tables, llr, n_llr, bits, NULL) == -2);
                 free(tail);
+                /* merge depths of the same decode: [iterations][2][2], each in -1 .. N */
+                int32_t dep[2 * 4];
+                CHECK(orc_decode_depths(N, period, punct, 2, algo, perm, inv, tables, llr + n_llr, n_llr, dep) == 0);
+                for (int i = 0; i < 8; ++i) CHECK(dep[i] >= -1 && dep[i] <= N);
+                CHECK(orc_decode_depths(N, period, punct, 0, algo, perm, inv, tables, llr, n_llr, dep) == -2);
                 /* one SISO with extreme a-priori values */
                 float *lc = malloc(sizeof(float) * 4 * N);
                 double *la = malloc(sizeof(double) * 4 * N);
@@ -94,6 +105,12 @@ int main(void)
                 la[0] = 1e300;
                 orc_siso(N, lc, lc + N, lc + 2 * N, lc + 3 * N, la, la + N, tables, 0.7, algo, la + 2 * N,
                          la + 3 * N);
+                int32_t sd[2];
+                CHECK(orc_siso_depths(N, 0, lc, lc + N, lc + 2 * N, lc + 3 * N, la, la + N, tables, 0.7, algo, sd) == 0);
+                CHECK(sd[0] >= -1 && sd[0] <= N && sd[1] >= -1 && sd[1] <= N);
+                /* the exact f64 reference (algo 2) reports no depths */
+                CHECK(orc_siso_depths(N, 0, lc, lc + N, lc + 2 * N, lc + 3 * N, la, la + N, tables, 0.7, 2, sd) == -3);
+                CHECK(orc_decode_depths(N, period, punct, 1, 2, perm, inv, tables, llr, n_llr, dep) == -3);
                 /* encoder */
                 int32_t *info = malloc(sizeof(int32_t) * 2 * N), *coded = malloc(sizeof(int32_t) * (6 * N + 8));
                 for (int i = 0; i < 2 * N; ++i) info[i] = urand() < 0.5;

@@ -211,7 +211,7 @@ static inline double LC(const lc_in *c, int i, int k)
 static void siso_exact(int N, const lc_in *lc, const double *LaA, const double *LaB, const int32_t *tables,
                        double sf, double *LeA, double *LeB);
 static void siso_core(int N, const lc_in *lc, const double *LaA, const double *LaB, const int32_t *tables,
-                      double sf, int algo, double *LeA, double *LeB);
+                      double sf, int algo, double *LeA, double *LeB, int32_t *depths);
 
 /* bcjr_max_log_map, dvb_rcs2_turbo.py:116-281 (algo 0); algo 1 = the build's
  * log-MAP (above): same passes, metrics in bits, max -> max*; algo 2 = exact
@@ -222,7 +222,7 @@ void orc_siso(int N, const float *LcA, const float *LcB, const float *LcW, const
 {
     const lc_in lc = {{LcA, LcB, LcW, LcY}, 0};
     if (algo == 2) siso_exact(N, &lc, LaA, LaB, tables, sf, LeA, LeB);
-    else siso_core(N, &lc, LaA, LaB, tables, sf, algo, LeA, LeB);
+    else siso_core(N, &lc, LaA, LaB, tables, sf, algo, LeA, LeB, NULL);
 }
 
 /* The same with float64 channel LLRs (numba's float64 specialisation). */
@@ -232,11 +232,44 @@ void orc_siso64(int N, const double *LcA, const double *LcB, const double *LcW, 
 {
     const lc_in lc = {{LcA, LcB, LcW, LcY}, 1};
     if (algo == 2) siso_exact(N, &lc, LaA, LaB, tables, sf, LeA, LeB);
-    else siso_core(N, &lc, LaA, LaB, tables, sf, algo, LeA, LeB);
+    else siso_core(N, &lc, LaA, LaB, tables, sf, algo, LeA, LeB, NULL);
 }
 
+/* The merge depths of one SISO call (algo 0 or 1; f64 != 0: the channel LLRs
+ * are float64 arrays): depths[0] forward, depths[1] backward (merge_depth).
+ * Returns 0, or -3 for algo 2 (the f64 accuracy reference keeps no pass-1 copy). */
+int orc_siso_depths(int N, int f64, const void *LcA, const void *LcB, const void *LcW, const void *LcY,
+                     const double *LaA, const double *LaB, const int32_t *tables, double sf, int algo,
+                     int32_t *depths)
+{
+    if (algo == 2) return -3;
+    const lc_in lc = {{LcA, LcB, LcW, LcY}, f64 != 0};
+    double *le = (double *)malloc(sizeof(double) * 2 * (size_t)(N > 0 ? N : 1));
+    siso_core(N, &lc, LaA, LaB, tables, sf, algo, le, le + N, depths);
+    free(le);
+    return 0;
+}
+
+/* Where the second pass of a recursion meets the first (the merge argument of
+ * DESIGN.md §3): v1 / v2 hold the (N + 1) x 16 vectors of pass 1 / pass 2.  Forward:
+ * the smallest k in 0..N with v2[k] == v1[k] on all 16 states; backward: the
+ * smallest d in 0..N with v2[N - d] == v1[N - d]; -1 when no step qualifies.
+ * C ==: a NaN never equals anything, -0.0 equals 0.0. */
+static int32_t merge_depth(int N, const float *v1, const float *v2, int backward)
+{
+    for (int d = 0; d <= N; ++d) {
+        const size_t k = (size_t)(backward ? N - d : d) * NS;
+        int eq = 1;
+        for (int s = 0; s < NS; ++s) eq &= v2[k + s] == v1[k + s];
+        if (eq) return d;
+    }
+    return -1;
+}
+
+/* depths: NULL, or int32 [2] that receives the merge depths of the forward and
+ * the backward second pass (merge_depth); nothing else changes. */
 static void siso_core(int N, const lc_in *lc, const double *LaA, const double *LaB, const int32_t *tables,
-                      double sf, int algo, double *LeA, double *LeB)
+                      double sf, int algo, double *LeA, double *LeB, int32_t *depths)
 {
     const int32_t *nx = tables, *ow = tables + 64, *oy = tables + 128, *ps = tables + 192, *pi = tables + 256;
     float *gamma = (float *)calloc((size_t)N * NS * 4, sizeof(float));
@@ -244,6 +277,9 @@ static void siso_core(int N, const lc_in *lc, const double *LaA, const double *L
     float *beta = (float *)calloc((size_t)(N + 1) * NS, sizeof(float));
     float *UV = (float *)calloc((size_t)N * 4, sizeof(float));   /* log-MAP: U0, U1, V0, V1 per k */
     const double hw = algo ? LM_K : 0.5;   /* branch-metric half weight: nats (reference) or bits */
+    /* pass 2 overwrites pass 1 in place: its copy, kept only when depths are asked for */
+    const size_t vec_bytes = (size_t)(N + 1) * NS * sizeof(float);
+    float *pass1 = depths ? (float *)malloc(vec_bytes) : NULL;
 
     /* 1. gamma (:127-160): f64 sum in fixed order, stored as f32 */
     for (int k = 0; k < N; ++k) {
@@ -280,8 +316,10 @@ static void siso_core(int N, const lc_in *lc, const double *LaA, const double *L
 
     /* 2. forward, double pass (:162-197) */
     for (int pass = 0; pass < 2; ++pass) {
-        if (pass == 1)
+        if (pass == 1) {
+            if (depths) memcpy(pass1, alpha, vec_bytes);
             for (int s = 0; s < NS; ++s) ALP(0, s) = ALP(N, s);
+        }
         for (int k = 0; k < N; ++k) {
             for (int n = 0; n < NS; ++n) {
                 float mv;
@@ -309,10 +347,14 @@ static void siso_core(int N, const lc_in *lc, const double *LaA, const double *L
         }
     }
 
+    if (depths) depths[0] = merge_depth(N, pass1, alpha, 0);
+
     /* 3. backward, double pass (:199-230) */
     for (int pass = 0; pass < 2; ++pass) {
-        if (pass == 1)
+        if (pass == 1) {
+            if (depths) memcpy(pass1, beta, vec_bytes);
             for (int s = 0; s < NS; ++s) BET(N, s) = BET(0, s);
+        }
         for (int k = N - 1; k >= 0; --k) {
             for (int s = 0; s < NS; ++s) {
                 float mv;
@@ -333,6 +375,8 @@ static void siso_core(int N, const lc_in *lc, const double *LaA, const double *L
             for (int s = 0; s < NS; ++s) BET(k, s) -= norm;
         }
     }
+
+    if (depths) { depths[1] = merge_depth(N, pass1, beta, 1); free(pass1); }
 
     /* 4. extrinsic (:232-281) */
     for (int k = 0; k < N; ++k) {
@@ -497,9 +541,9 @@ int orc_depuncture(int N, int period, const uint8_t *punct, const float *llr, lo
 /* DVBRCS2_Turbo.decode, dvb_rcs2_turbo.py:464-537.  Returns 0, or -1 when the
  * LLR vector is too short (the reference raises IndexError), -2 when
  * iterations < 1 (the reference raises UnboundLocalError). */
-int orc_decode(int N, int period, const uint8_t *punct, int iterations, int algo,
-               const int32_t *perm, const int32_t *inv_perm, const int32_t *tables,
-               const float *llr, long n_llr, int32_t *bits, double *lfinal)
+static int decode_impl(int N, int period, const uint8_t *punct, int iterations, int algo,
+                       const int32_t *perm, const int32_t *inv_perm, const int32_t *tables,
+                       const float *llr, long n_llr, int32_t *bits, double *lfinal, int32_t *depths)
 {
     if (iterations < 1) return -2;
     size_t n = (size_t)N;
@@ -512,12 +556,16 @@ int orc_decode(int N, int period, const uint8_t *punct, int iterations, int algo
     double *La2A = buf + 4 * n, *La2B = buf + 5 * n, *Le2A = buf + 6 * n, *Le2B = buf + 7 * n;
     for (int it = 0; it < iterations; ++it) {
         double sf = it < iterations - 1 ? 0.7 : 1.0;
-        orc_siso(N, LcA, LcB, W1, Y1, LaA, LaB, tables, sf, algo, Le1A, Le1B);
+        const lc_in lc1 = {{LcA, LcB, W1, Y1}, 0}, lc2 = {{LcAi, LcBi, W2, Y2}, 0};
+        /* algo 2 is the exact f64 reference, as in orc_siso (decode_depths refuses it) */
+        if (algo == 2) siso_exact(N, &lc1, LaA, LaB, tables, sf, Le1A, Le1B);
+        else siso_core(N, &lc1, LaA, LaB, tables, sf, algo, Le1A, Le1B, depths ? depths + 4 * it : NULL);
         for (size_t k = 0; k < n; ++k) {
             La2A[k] = Le1A[perm[k]]; La2B[k] = Le1B[perm[k]];
             LcAi[k] = LcA[perm[k]]; LcBi[k] = LcB[perm[k]];
         }
-        orc_siso(N, LcAi, LcBi, W2, Y2, La2A, La2B, tables, sf, algo, Le2A, Le2B);
+        if (algo == 2) siso_exact(N, &lc2, La2A, La2B, tables, sf, Le2A, Le2B);
+        else siso_core(N, &lc2, La2A, La2B, tables, sf, algo, Le2A, Le2B, depths ? depths + 4 * it + 2 : NULL);
         for (size_t k = 0; k < n; ++k) { LaA[k] = Le2A[inv_perm[k]]; LaB[k] = Le2B[inv_perm[k]]; }
     }
     for (size_t k = 0; k < n; ++k) {
@@ -529,6 +577,28 @@ int orc_decode(int N, int period, const uint8_t *punct, int iterations, int algo
     }
     free(Lc); free(LcAi); free(buf);
     return 0;
+}
+
+int orc_decode(int N, int period, const uint8_t *punct, int iterations, int algo,
+               const int32_t *perm, const int32_t *inv_perm, const int32_t *tables,
+               const float *llr, long n_llr, int32_t *bits, double *lfinal)
+{
+    return decode_impl(N, period, punct, iterations, algo, perm, inv_perm, tables, llr, n_llr, bits, lfinal, NULL);
+}
+
+/* The merge depths of every SISO call of orc_decode (max-log or the build's
+ * log-MAP): depths int32 [iterations][2][2], indexed by SISO 1 / SISO 2 and
+ * forward / backward (merge_depth).  Same return codes as orc_decode. */
+int orc_decode_depths(int N, int period, const uint8_t *punct, int iterations, int algo,
+                      const int32_t *perm, const int32_t *inv_perm, const int32_t *tables,
+                      const float *llr, long n_llr, int32_t *depths)
+{
+    if (algo == 2) return -3;   /* the f64 accuracy reference keeps no pass-1 copy */
+    int32_t *bits = (int32_t *)malloc(sizeof(int32_t) * 2 * (size_t)(N > 0 ? N : 1));
+    const int rc = decode_impl(N, period, punct, iterations, algo, perm, inv_perm, tables, llr, n_llr, bits, NULL,
+                               depths);
+    free(bits);
+    return rc;
 }
 
 /* Batched decode over B codewords (row stride llr_stride floats), OpenMP over

@@ -1,0 +1,242 @@
+"""Finite inputs whose second recursion passes merge late, or never.
+
+TEST INFRASTRUCTURE (a plain module, like early_stop_ref.py).  Every decoder here
+skips the rest of a second pass once its state vector equals the first pass's at
+the same step.  Noisy rows merge within a few dozen to ~200 steps,
+so they never reach the deep ends of those shortcuts; these builders make rows
+that do, out of finite numbers only.
+
+The construction: a *stretch* of positions with |L_A| = |L_B| = STRETCH (random
+signs), W = Y = 0 and zero a-priori.  There every trellis state has exactly one
+predecessor (successor) whose branch beats the others by STRETCH or more, which
+is more than the spread of the state metrics, so a recursion step only permutes
+the state vector and subtracts one entry: whatever difference the second pass
+brings in from the first pass's end vector is carried through unchanged.
+Everything outside the stretch is *noise*: independent integers in
+[-NOISE, NOISE] on all six inputs.  All values are small integers, so every f32
+and f64 operation of the max-log SISO is exact and the merge depths
+(oracle.siso_depths) are the same on every host.
+
+Families (the `family` argument):
+  "f_late(D)"  stretch over [0, D): delays the forward merge by D
+  "b_late(D)"  stretch over [n - D, n): delays the backward merge by D
+  "never"      stretch everywhere but a noise island of 8..16 positions
+  "plain"      noise only
+The functions are seeded and pure.  Which seed puts a family's depth into the
+class a test needs was found by a CPU search over oracle.siso_depths /
+oracle.decode_depths (search_seed below); the seeds found are the tables SISO_SEEDS
+and DECODE_SEEDS, and tests/test_merge_depth_host.py asserts every one still lands
+in its class.
+"""
+import re
+
+import numpy as np
+
+from oracle import oracle as O
+
+STRETCH = 64.0   # |L_A| = |L_B| on the stretch
+NOISE = 3        # noise values are integers in [-NOISE, NOISE]
+
+
+def parse_family(family):
+    """('f_late' | 'b_late', D) or ('never' | 'plain', 0)."""
+    m = re.fullmatch(r"(f_late|b_late)\((\d+)\)", family)
+    if m:
+        return m.group(1), int(m.group(2))
+    if family in ("never", "plain"):
+        return family, 0
+    raise ValueError(f"unknown family {family!r}")
+
+
+def _planes(n, family, seed, n_par):
+    """(stretch mask [n], A, B [n], parities [n_par][n], a-priori [2][n]) as float64 integers."""
+    kind, D = parse_family(family)
+    if D > n:
+        raise ValueError(f"{family}: the stretch is longer than the block ({n})")
+    rng = np.random.default_rng([int(seed), n])
+    noise = rng.integers(-NOISE, NOISE + 1, (4 + n_par, n)).astype(np.float64)
+    sign = rng.choice([-1.0, 1.0], (2, n))
+    isl_len = int(rng.integers(8, 17))
+    isl_at = int(rng.integers(0, n - isl_len + 1)) if n > isl_len else 0
+    m = np.zeros(n, bool)
+    if kind == "f_late":
+        m[:D] = True
+    elif kind == "b_late":
+        m[n - D:] = True
+    elif kind == "never":
+        m[:] = True
+        m[isl_at:isl_at + isl_len] = False
+    A = np.where(m, STRETCH * sign[0], noise[0])
+    B = np.where(m, STRETCH * sign[1], noise[1])
+    par = np.where(m, 0.0, noise[2:2 + n_par])
+    la = np.where(m, 0.0, noise[2 + n_par:])
+    return m, A, B, par, la
+
+
+def siso_rows(n, family, seed):
+    """One SISO row of `family`: (LcA, LcB, LcW, LcY float32 [n], LaA, LaB float64 [n])."""
+    _, A, B, par, la = _planes(n, family, seed, 2)
+    f = lambda x: np.ascontiguousarray(x, np.float32)   # noqa: E731
+    return f(A), f(B), f(par[0]), f(par[1]), la[0].copy(), la[1].copy()
+
+
+def llr_positions(n, punct):
+    """Index into the received LLR vector of every de-punctured plane entry:
+    int [6][n] (A, B, W1, Y1, W2, Y2), -1 where the entry is punctured -- read off
+    the oracle's own de-puncture walk (orc_depuncture) on the vector 1, 2, 3, ..."""
+    from modulations_amd import tables as T
+    n_coded = T.coded_size(n, punct)
+    pos = O.depuncture(np.arange(1, n_coded + 1, dtype=np.float32), n, punct["period"], T.puncture_matrix(punct))
+    return pos.astype(np.int64) - 1
+
+
+def decode_llr(codec, family, seed, stretch=STRETCH):
+    """One received-LLR vector (float32 [codec.n_coded]) of `family`: the stretch
+    applies to the systematic LLRs A / B in natural order; W1, Y1, W2 and Y2 are
+    zero outside the noise positions (decoder 2 reads W2 / Y2 in interleaved order,
+    so its parities are noisy where its index, not its systematic pair, is outside
+    the stretch).  Values go to the positions the codec's de-puncture walk reads."""
+    n = codec.N
+    _, A, B, par, _ = _planes(n, family, seed, 4)
+    planes = np.stack([A, B, *par])
+    if stretch != STRETCH:
+        big = np.abs(planes[:2]) == STRETCH
+        planes[:2] = np.where(big, np.sign(planes[:2]) * stretch, planes[:2])
+    pos = llr_positions(n, codec.punct)
+    llr = np.zeros(codec.n_coded, np.float32)
+    keep = pos >= 0
+    llr[pos[keep]] = planes[keep]
+    return llr
+
+
+# ---- the shortcuts' constants, restated, and the depth classes they define -------------
+RING = 16        # modulations_amd/csrc/tdec_kernels.hip:873  beta1 kept at RING window starts
+
+
+def rstep_of(w):  # tdec_kernels.hip:874  siso<0, W>: every rstep-th window start is kept
+    return 1 if w >= 16 else 16 // w
+
+
+CK8 = 8          # tdec_kernels.hip:1168  siso8's window step / checkpoint interval (WS, CK)
+RSTEP8 = 2       # tdec_kernels.hip:1133  siso8 keeps every 2nd window start
+WIN = 4          # tdec_kernels.hip:1281  the row SISO runs siso<0, 4>; tdec_spl.hip:17 SPL_W = 4, :173 rw % 4
+FR_LMIN = 32     # modulations_amd/csrc/tdec_frame.hip:66
+
+
+def fr_seg_len(n, p):   # tdec_frame.hip:67-71
+    k = min(max(n // FR_LMIN, 1), p)
+    return (n + 4 * k - 1) // (4 * k) * 4
+
+
+def b2_checks(n, w, rstep):
+    """The depths d (steps from the top) at which a backward second pass with
+    w-step windows compares beta2 with the kept beta1 (tdec_kernels.hip:977-987,
+    :1244-1257, tdec_spl.hip:171-177): the entry of window r = 0, rstep, 2 rstep, ...
+    below RING * rstep; the top window may be short."""
+    top = (n - 1) // w * w
+    n_win = top // w + 1
+    return [0 if r == 0 else (n - top) + w * (r - 1) for r in range(0, min(n_win, RING * rstep), rstep)]
+
+
+def ring_reach(n):
+    """(lo, hi): the last depth at which siso8 and siso<0, 4> / the state-per-lane
+    prototype can still see a backward merge, smaller and larger of the two."""
+    last = [b2_checks(n, CK8, RSTEP8)[-1], b2_checks(n, WIN, rstep_of(WIN))[-1]]
+    return min(last), max(last)
+
+
+FAR = 700        # class (c): the issue's "at least 700 at N = 752"; blocks shorter than that have no class (c)
+
+
+def depth_class(n, depth):
+    """The class of a merge depth (forward or backward, the same bounds):
+      'a'  inside the ring's reach and off every grid: 128 < depth < lo, not a
+           multiple of 4 (the checkpoints of every kernel and the frame decoder's
+           4- and 8-step blocks start at multiples of 4 from a segment start, itself
+           a multiple of 4) and none of the ring's own compare depths;
+      'b'  just past the ring: hi < depth <= hi + 64;
+      'c'  far past: depth >= FAR;
+      'd'  never (-1);
+    None otherwise."""
+    lo, hi = ring_reach(n)
+    if depth < 0:
+        return "d"
+    if depth >= FAR:
+        return "c"
+    if hi < depth <= hi + 64:
+        return "b"
+    grid = set(b2_checks(n, CK8, RSTEP8)) | set(b2_checks(n, WIN, rstep_of(WIN)))
+    if 128 < depth < lo and depth % 4 and depth not in grid:
+        return "a"
+    return None
+
+
+def search_seed(build, accept, seeds=range(1000)):
+    """The first seed whose build(seed) satisfies accept(...): how the seed tables
+    below were found (CPU only)."""
+    for s in seeds:
+        if accept(build(s)):
+            return s
+    raise LookupError("no seed in range")
+
+
+# ---- the fixtures the GPU tests use (seeds found with search_seed, then pinned) -----------
+# SISO level, per block size: (family, seed, direction whose class the row is there for,
+# class).  Every block holds each class for F2 and for B2 plus plain rows; N = 212 is
+# shorter than FAR, so it has no class (c), and its class (b) is a merge in the last
+# few steps, past the ring's last compare (212 < RING * 16).
+SISO_SEEDS = {
+    212: [("f_late(139)", 1, "f2", "a"), ("b_late(139)", 0, "b2", "a"), ("f_late(195)", 187, "f2", "b"),
+          ("b_late(193)", 131, "b2", "b"), ("never", 0, "both", "d"), ("plain", 0, None, None),
+          ("plain", 1, None, None)],
+    752: [("f_late(203)", 0, "f2", "a"), ("b_late(203)", 0, "b2", "a"), ("f_late(259)", 2, "f2", "b"),
+          ("b_late(259)", 1, "b2", "b"), ("f_late(700)", 1, "f2", "c"), ("b_late(700)", 1, "b2", "c"),
+          ("never", 0, "both", "d"), ("plain", 0, None, None)],
+    790: [("f_late(203)", 0, "f2", "a"), ("b_late(203)", 4, "b2", "a"), ("f_late(259)", 1, "f2", "b"),
+          ("b_late(259)", 0, "b2", "b"), ("f_late(700)", 0, "f2", "c"), ("b_late(700)", 0, "b2", "c"),
+          ("never", 0, "both", "d"), ("plain", 0, None, None)],
+    848: [("f_late(203)", 0, "f2", "a"), ("b_late(203)", 1, "b2", "a"), ("f_late(259)", 0, "f2", "b"),
+          ("b_late(259)", 0, "b2", "b"), ("f_late(700)", 0, "f2", "c"), ("b_late(700)", 0, "b2", "c"),
+          ("never", 0, "both", "d"), ("plain", 0, None, None)],
+}
+
+# Decode level, per (N, rate): seeds of "never" vectors whose every SISO call of all 8
+# iterations, both decoders, both directions, is in class (c) or (d), and one vector
+# whose decoder-1 B2 is in class (b) in iteration 1 and again in a later iteration.
+DECODE_SEEDS = {
+    (752, "1/3"): {"never": [0, 2, 3, 6], "b": ("b_late(259)", 0)},
+    (220, "1/2"): {"never": [1, 2, 3, 4], "b": ("b_late(203)", 88)},
+    (848, "1/3"): {"never": [0, 1, 2, 3], "b": ("b_late(259)", 0)},
+}
+
+
+def siso_batch(n, f64=False):
+    """The SISO batch of block size n: ([LcA, LcB, LcW, LcY] [B, n] float32 (float64
+    with f64), [LaA, LaB] [B, n] float64, SISO_SEEDS[n])."""
+    rows = [siso_rows(n, fam, seed) for fam, seed, _, _ in SISO_SEEDS[n]]
+    Lc = [np.stack([r[i] for r in rows]).astype(np.float64 if f64 else np.float32) for i in range(4)]
+    La = [np.stack([r[4 + i] for r in rows]) for i in range(2)]
+    return Lc, La, SISO_SEEDS[n]
+
+
+def decode_batch3(codec):
+    """Three codewords for the one-codeword-per-workgroup decoders: never, class (b), plain."""
+    s = DECODE_SEEDS[(codec.N, codec.rate)]
+    return np.stack([decode_llr(codec, "never", s["never"][0]), decode_llr(codec, *s["b"]),
+                     decode_llr(codec, "plain", 0)])
+
+
+TILE_LATE_LANES = (0, 31, 63, 64 + 2)   # class (c) / (d) rows: first tile's ends and middle, the partial tile
+TILE_B_LANE = 1                         # the class (b) row
+
+
+def decode_batch69(codec):
+    """64 + 5 codewords for the tile decoders: never-merging rows in lanes 0, 31 and 63
+    of the first tile and lane 2 of the partial one, a class (b) row in lane 1,
+    everything else plain -- masked and unmasked lanes share both waves."""
+    s = DECODE_SEEDS[(codec.N, codec.rate)]
+    rows = [decode_llr(codec, "plain", i) for i in range(69)]
+    for lane, seed in zip(TILE_LATE_LANES, s["never"]):
+        rows[lane] = decode_llr(codec, "never", seed)
+    rows[TILE_B_LANE] = decode_llr(codec, *s["b"])
+    return np.stack(rows)

@@ -9,9 +9,12 @@ by IEEE == (NaN == NaN where the reference produces NaN).
 The segment machinery is exact only if the merge test and the re-run rounds
 are right, so the inputs below also include the cases that defeat early
 merging: NaN / inf LLRs (a NaN vector never equals the stored one: every
-segment runs to its end and hands its vector on), tiny LLRs (long mixing),
-lengths that leave empty or short segments (N = 1 .. 17) and lengths that are
-not multiples of 4."""
+segment runs to its end and hands its vector on), tiny LLRs (denormal and
+near-tie arithmetic; max-log is scale invariant, so they merge no later than
+the same rows unscaled: oracle.siso_depths gives 59 .. 168 steps for the "tiny"
+rows below against 67 .. 163 unscaled), lengths that leave empty or short
+segments (N = 1 .. 17) and lengths that are not multiples of 4.  Finite rows
+that merge hundreds of steps late, or never, are in tests/test_gpu_merge_depth.py."""
 import numpy as np
 import pytest
 
@@ -62,8 +65,9 @@ def test_frame_siso_every_length_to_160(wpd, monkeypatch):
     """Every N from 1 to 160 (segments per direction N / 32, split evenly in whole
     4-step blocks, ragged last blocks, 8-step fast blocks and their per-step tail)
     on both recursion layouts (TDEC_FR_SISO_WPD1_MAX: one wave per direction, or
-    two), at a low a-priori scale so merges come late and rounds hand end vectors
-    down the chain."""
+    two), at a low a-priori scale: by oracle.siso_depths about half of these rows
+    below N = 100 never merge within their block (a merge takes 25 .. 150 steps at
+    this scale), so rounds hand end vectors down the chain."""
     if wpd == "two":
         monkeypatch.setenv("TDEC_FR_SISO_WPD1_MAX", "0")
     rng = np.random.default_rng(160)
