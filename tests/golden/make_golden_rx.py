@@ -100,24 +100,25 @@ def run_recorded(SM, m, cap, mod, n_bits):
     return bits, stats, rec.calls
 
 
-def first_run(flags, pre):
-    """First i < n - pre with flags[i : i + pre // 2] all set, else -1 (a sliding count)."""
-    half = pre // 2
-    c = np.concatenate([[0], np.cumsum(flags.astype(np.int64))])
-    ok = (c[half:] - c[:len(c) - half]) == half          # ok[i]: flags[i:i+half] all set
-    idx = np.nonzero(ok[:max(len(flags) - pre, 0)])[0]
-    return int(idx[0]) if len(idx) else -1
+sys.path.insert(0, os.path.dirname(OUT))
+from rx_patterns import first_run  # noqa: E402  (tests/rx_patterns.py: the search as a sliding count)
+
+QAM_AXIS = {"16QAM": (4, 10), "64QAM": (8, 42), "256QAM": (16, 170)}   # levels per axis, 1 / scale ** 2
 
 
 def boundary_margin(syms, mod):
     """Smallest distance of a symbol from a decision boundary of the hard demodulator."""
+    if mod == "BPSK":
+        return np.min(np.abs(syms.real))
     if mod == "QPSK":
         return min(np.min(np.abs(syms.real)), np.min(np.abs(syms.imag)))
     if mod == "8PSK":
         q = np.angle(syms) / (np.pi / 4)
         return np.min(np.abs((q - np.floor(q)) - 0.5) * (np.pi / 4) * np.abs(syms))
-    x = np.concatenate([syms.real, syms.imag]) * np.sqrt(10)
-    return np.min(np.abs(x[:, None] - np.array([-2.0, 0.0, 2.0])[None, :])) / np.sqrt(10)
+    levels, s = QAM_AXIS[mod]
+    x = np.concatenate([syms.real, syms.imag]) * np.sqrt(s)
+    edges = np.arange(-(levels - 2), levels - 1, 2.0)      # 16QAM: -2, 0, 2; 64QAM: -6 .. 6
+    return np.min(np.abs(x[:, None] - edges[None, :])) / np.sqrt(s)
 
 
 def halfway_symbol():
