@@ -333,19 +333,26 @@ int check_demap_args(int M, int bps) {
     return 0;
 }
 
-typedef void (*decode_fn)(DecodeArgs, const int *, const int *, const int *);
-
 const void *decode_kernel(int algo, bool ragged) {
     if (algo) return ragged ? (const void *)k_turbo_decode_logmap<true> : (const void *)k_turbo_decode_logmap<false>;
     return ragged ? (const void *)k_turbo_decode<true> : (const void *)k_turbo_decode<false>;
 }
 
-typedef void (*decode_es_fn)(DecodeArgs, const int *, const int *, const int *, EsArgs);
-
 const void *decode_es_kernel(int algo, bool ragged) {
     if (algo)
         return ragged ? (const void *)k_turbo_decode_logmap_es<true> : (const void *)k_turbo_decode_logmap_es<false>;
     return ragged ? (const void *)k_turbo_decode_es<true> : (const void *)k_turbo_decode_es<false>;
+}
+
+// Every page-locked staging layout puts its arrays at 256-byte boundaries (the zero-copy
+// kernels store int2 / double2 there whatever the row stride).
+constexpr size_t up256(size_t x) { return (x + 255) / 256 * 256; }
+
+// Rows per chunk of the chunked host-pointer paths: TDEC_HOST_CHUNK (read per call; tests
+// use a small value to exercise the chunk loops) or the caller's default.
+long host_chunk(long dflt) {
+    const char *pc = getenv("TDEC_HOST_CHUNK");
+    return pc ? std::max(1L, atol(pc)) : dflt;
 }
 
 }  // namespace
@@ -435,12 +442,12 @@ int mark_used(tdec_ctx *h, hipStream_t s) {
 // handle's streams read / write the caller's host buffers, so they must have
 // finished before the caller gets control back (errors included).
 struct DrainOnExit {
-    hipStream_t a, b;
+    hipStream_t a, b = nullptr, c = nullptr;
     ~DrainOnExit() {
-        if (a) hipStreamSynchronize(a);
-        if (b && b != a) hipStreamSynchronize(b);
+        for (hipStream_t s : {a, b, c})
+            if (s) hipStreamSynchronize(s);
     }
-    void disarm() { a = b = nullptr; }   // the call synchronised its streams itself
+    void disarm() { a = b = c = nullptr; }   // the call synchronised its streams itself
 };
 // A host-pointer call that synchronised its stream leaves nothing queued on the
 // handle's buffers: no event to record (mark_used) and none to wait on later.
@@ -1036,73 +1043,68 @@ int tdec_depuncture_dev(tdec_t *h, int B, const float *d_llr, long llr_stride, f
     return 0;
 }
 
-int tdec_decode_planes_dev(tdec_t *h, int B, const float *d_planes, int32_t *d_bits, double *d_lfinal,
-                           void *stream) {
+}  // extern "C"
+
+// ---- host code the decode entry points share ---------------------------------------------
+// The argument checks, in the order a caller can observe: an empty batch is a no-op before the pointers
+// are looked at, but the host-pointer forms (host_stride) check their stride before that (an empty batch of
+// short rows is TDEC_ESHORT).  A TDEC_E* code, ARGS_EMPTY (CHECK_ARGS: the entry point returns 0) or 0 to go on.
+enum { ARGS_EMPTY = 1 };
+#define CHECK_ARGS(...) if (const int a_ = decode_args(__VA_ARGS__)) return a_ == ARGS_EMPTY ? 0 : a_
+static int decode_args(const tdec_t *h, int B, const void *in, const void *bits, const long *host_stride = nullptr) {
     if (!h || B < 0) return fail(TDEC_EINVAL, "bad decode arguments");
-    if (B == 0) return 0;
-    if (!d_planes || !d_bits) return fail(TDEC_EINVAL, "bad decode arguments");
-    Guard g(h->device);
-    hipStream_t st = (hipStream_t)stream;
-    if (use_lowlat(h, B)) {
-        if (int rc = order_on(h, st)) return rc;
-        if (use_frame_decoder(h)) {
-            if (int rc = frame_lds_attr(h->device)) return rc;
-            const bool lg = frame_le2_global(h->N);
-            FrArgs a{B, h->N, h->iters, d_planes, (double2 *)h->ll_ws.p, d_bits, d_lfinal, h->n_used,
-                     lg ? (double2 *)h->ll_ws.p + (size_t)B * h->N : nullptr};
-            const bool w1 = fr_wpd(h->N, false) == 1;
-            const auto kern = h->algo ? (lg ? (w1 ? k_turbo_decode_frame<true, 1, 1> : k_turbo_decode_frame<true, 1, 2>)
-                                            : (w1 ? k_turbo_decode_frame<false, 1, 1> : k_turbo_decode_frame<false, 1, 2>))
-                                      : (lg ? (w1 ? k_turbo_decode_frame<true, 0, 1> : k_turbo_decode_frame<true, 0, 2>)
-                                            : (w1 ? k_turbo_decode_frame<false, 0, 1> : k_turbo_decode_frame<false, 0, 2>));
-            hipLaunchKernelGGL(kern, dim3((unsigned)B), dim3(FR_BLOCK), fr_lds(h->N, true, lg).total, st, a,
-                               (const int *)h->d_perm, (const int *)h->d_inv, (const int *)h->d_ford);
-            HIPCHK(hipGetLastError());
-            return mark_used(h, st);
-        }
-        LLArgs a{B, h->N, h->iters, d_planes, (double2 *)h->ll_ws.p, (float *)h->ll_st.p, d_bits, d_lfinal,
-                 (const int *)h->d_ulist, h->n_used};
-        hipLaunchKernelGGL(k_turbo_decode_lowlat, dim3((unsigned)B), dim3(WAVE), ll_lds_bytes(h->N), st, a,
-                           (const int *)h->d_perm, (const int *)h->d_inv);
-        HIPCHK(hipGetLastError());
-        return mark_used(h, st);
-    }
-    const int tiles = n_tiles_of(B);
-    const int waves = std::min(tiles, h->max_waves);
-    if (waves > h->ws_waves) return fail(TDEC_ECAPACITY, "workspace too small: call tdec_reserve first");
-    if (int rc = order_on(h, st)) return rc;
-    DecodeArgs a{B, h->N, h->iters, tiles, waves, d_planes, h->le_p, h->ck_p, d_bits, d_lfinal, h->d_used,
-                 waves * WAVE, h->aux_p, tile_queue(h, tiles, waves, st), ck_rows_of(h)};
-    if (h->d_simd_prog && hipMemsetAsync(h->d_simd_prog, 0, SIMD_PROG_BYTES, st) == hipSuccess) a.simd_prog = h->d_simd_prog;
-    a.tail_flag = h->d_tail;
-    a.tail_seq = ++h->tail_seq;
-    const int *pm = h->d_perm, *iv = h->d_inv;
-    const dim3 grid((waves + DEC_WAVES - 1) / DEC_WAVES);
-    hipLaunchKernelGGL((decode_fn)decode_kernel(h->algo, h->N % win_of(h->algo) != 0), grid, dim3(DEC_BLOCK), 0, st,
-                       a, pm, iv, (const int *)h->d_used);
-    HIPCHK(hipGetLastError());
-    return mark_used(h, st);
+    if (host_stride && *host_stride < h->llr_len) return fail(TDEC_ESHORT, "llr rows shorter than the de-puncture walk");
+    if (B == 0) return ARGS_EMPTY;
+    if (!in || !bits) return fail(TDEC_EINVAL, "bad decode arguments");
+    return 0;
 }
 
-int tdec_tail_gate(tdec_t *h, void *stream) {
-    if (!h) return fail(TDEC_EINVAL, "bad tail gate arguments");
-    if (!h->tail_seq) return 0;   // no throughput launch yet: nothing to wait for
-    Guard g(h->device);
-    hipLaunchKernelGGL(k_tail_gate, dim3(1), dim3(WAVE), 0, (hipStream_t)stream, (const unsigned *)h->d_tail,
-                       h->tail_seq);
+// k_turbo_decode_frame<LG, ALGO, WPD> and, with early stop, k_turbo_decode_frame_es<LG, ALGO, WPD>
+// by [early stop][ALGO][LG: Le2 in global scratch][WPD - 1] (the kernels frame_lds_attr prepares)
+typedef void (*frame_fn)(FrArgs, const int *, const int *, const int *);
+typedef void (*frame_es_fn)(FrArgs, const int *, const int *, const int *, int32_t *);
+#define FRAME_KERNELS_OF(K)                                                                                         \
+    {{{(const void *)K<false, 0, 1>, (const void *)K<false, 0, 2>}, {(const void *)K<true, 0, 1>, (const void *)K<true, 0, 2>}}, \
+     {{(const void *)K<false, 1, 1>, (const void *)K<false, 1, 2>}, {(const void *)K<true, 1, 1>, (const void *)K<true, 1, 2>}}}
+static const void *const FRAME_KERNELS[2][2][2][2] = {FRAME_KERNELS_OF(k_turbo_decode_frame), FRAME_KERNELS_OF(k_turbo_decode_frame_es)};
+#undef FRAME_KERNELS_OF
+// One launch of the frame decoder (es: the early-stop kernel, n_iter nullable) over n rows of a plane
+// buffer.  The caller has set the LDS attribute (frame_lds_attr) and ordered the stream (order_on).
+static int launch_frame_decode(tdec_t *h, bool es, int n, const float *planes, int32_t *bits, double *lfinal,
+                               int32_t *n_iter, hipStream_t st) {
+    const int N = h->N;
+    const bool lg = frame_le2_global(N);
+    const FrArgs a{n, N, h->iters, planes, (double2 *)h->ll_ws.p, bits, lfinal, h->n_used,
+                   lg ? (double2 *)h->ll_ws.p + (size_t)n * N : nullptr};
+    const void *k = FRAME_KERNELS[es][h->algo != 0][lg][fr_wpd(N, false) - 1];
+    const dim3 grid((unsigned)n), block(FR_BLOCK);
+    const size_t lds = fr_lds(N, true, lg).total;
+    const int *pm = h->d_perm, *iv = h->d_inv, *ord = h->d_ford;
+    if (es) hipLaunchKernelGGL((frame_es_fn)k, grid, block, lds, st, a, pm, iv, ord, n_iter);
+    else hipLaunchKernelGGL((frame_fn)k, grid, block, lds, st, a, pm, iv, ord);
     HIPCHK(hipGetLastError());
     return 0;
 }
 
-int tdec_decode_batch_dev(tdec_t *h, int B, const float *d_llr, long llr_stride, int32_t *d_bits, double *d_lfinal,
-                          void *stream) {
-    if (!h || B < 0) return fail(TDEC_EINVAL, "bad decode arguments");
-    if (B == 0) return 0;
-    if (B > h->cap_batch) return fail(TDEC_ECAPACITY, "batch larger than tdec_reserve()");
-    if (int rc = order_on(h, (hipStream_t)stream)) return rc;   // planes_own may still be read elsewhere
-    int rc = tdec_depuncture_dev(h, B, d_llr, llr_stride, (float *)h->planes_own.p, stream);
-    if (!rc) rc = tdec_decode_planes_dev(h, B, (const float *)h->planes_own.p, d_bits, d_lfinal, stream);
-    return rc;
+// One launch of a persistent tile loop (k_turbo_decode*, *_es, k_turbo_decode_syms): `waves` waves in
+// workgroups of block_waves over the batch's tiles.  queue: the zeroed tile counter, or null for static striding
+// (the caller's policy).  extra: what the kernel takes after DecodeArgs and the tables (EsArgs, FusedDemapArgs).
+enum { TL_ISSUE_PRIO = 1,   // zero and pass the max-log issue-priority slots (simd_prog)
+       TL_TAIL = 2 };       // raise the handle's tail flag to a new sequence number (tdec_tail_gate)
+template <typename... Extra>
+static int launch_tiles(tdec_t *h, const void *kern, int block_waves, int B, int waves, const float *planes,
+                        int32_t *bits, double *lfinal, int *queue, int flags, hipStream_t st, Extra... extra) {
+    DecodeArgs a{B, h->N, h->iters, n_tiles_of(B), waves, planes, h->le_p, h->ck_p, bits, lfinal, h->d_used,
+                 waves * WAVE, h->aux_p, queue, ck_rows_of(h)};
+    if ((flags & TL_ISSUE_PRIO) && h->d_simd_prog && hipMemsetAsync(h->d_simd_prog, 0, SIMD_PROG_BYTES, st) == hipSuccess)
+        a.simd_prog = h->d_simd_prog;
+    if (flags & TL_TAIL) a.tail_flag = h->d_tail, a.tail_seq = ++h->tail_seq;
+    typedef void (*kernel_fn)(DecodeArgs, const int *, const int *, const int *, Extra...);
+    const dim3 grid((waves + block_waves - 1) / block_waves);
+    hipLaunchKernelGGL((kernel_fn)kern, grid, dim3(block_waves * WAVE), 0, st, a, (const int *)h->d_perm,
+                       (const int *)h->d_inv, (const int *)h->d_used, extra...);
+    HIPCHK(hipGetLastError());
+    return mark_used(h, st);
 }
 
 // ---- early stop: the frame decoder with per-codeword termination --------------
@@ -1129,171 +1131,35 @@ static int ensure_es(tdec_t *h, int B) {
     return h->ll_ws.ensure(rows * (frame_le2_global(h->N) ? 2 : 1) * h->N * sizeof(double2));
 }
 
-int tdec_es_capacity(tdec_t *h) {
-    if (!h) return fail(TDEC_EINVAL, "null handle");
-    if (int rc = es_available(h)) return rc;
-    return es_rows(h);
-}
-
-int tdec_early_stop_available(int n_couples) {
-    const char *e = getenv("TDEC_FRAME");
-    return !(e && e[0] == '0') && n_couples > 0 && frame_fits(n_couples, true);
-}
-
-int tdec_decode_planes_es_dev(tdec_t *h, int B, const float *d_planes, int32_t *d_bits, double *d_lfinal,
-                              int32_t *d_n_iter, void *stream) {
-    if (!h || B < 0) return fail(TDEC_EINVAL, "bad decode arguments");
-    if (B == 0) return 0;
-    if (!d_planes || !d_bits) return fail(TDEC_EINVAL, "bad decode arguments");
-    if (int rc = es_available(h)) return rc;
-    Guard g(h->device);
-    hipStream_t st = (hipStream_t)stream;
-    if (int rc = ensure_es(h, B)) return rc;
-    if (int rc = frame_lds_attr(h->device)) return rc;
-    if (int rc = order_on(h, st)) return rc;
-    const int C = es_rows(h), N = h->N;
-    const bool lg = frame_le2_global(N), w1 = fr_wpd(N, false) == 1;
-    const auto kern = h->algo ? (lg ? (w1 ? k_turbo_decode_frame_es<true, 1, 1> : k_turbo_decode_frame_es<true, 1, 2>)
-                                    : (w1 ? k_turbo_decode_frame_es<false, 1, 1> : k_turbo_decode_frame_es<false, 1, 2>))
-                              : (lg ? (w1 ? k_turbo_decode_frame_es<true, 0, 1> : k_turbo_decode_frame_es<true, 0, 2>)
-                                    : (w1 ? k_turbo_decode_frame_es<false, 0, 1> : k_turbo_decode_frame_es<false, 0, 2>));
-    // chunks of C rows (whole tiles) reuse the workspace one after the other on the stream
+// The body of the three tdec_decode_batch*_dev: de-puncture into the handle's own planes, then the mode's
+// tdec_decode_planes*_dev.  The tile modes take the batch whole and refuse one above tdec_reserve(); the early-stop
+// frame mode walks it in chunks of es_rows() and sizes the planes for one chunk on first use, like its workspace.
+enum DecodeMode { DEC_PLAIN, DEC_ES_FRAME, DEC_ES_TILE };
+static int decode_batch_dev(tdec_t *h, DecodeMode mode, int B, const float *d_llr, long llr_stride, int32_t *d_bits,
+                            double *d_lfinal, int32_t *d_n_iter, void *stream) {
+    if (mode != DEC_ES_FRAME && B > h->cap_batch) return fail(TDEC_ECAPACITY, "batch larger than tdec_reserve()");
+    int C = B;
+    if (mode == DEC_ES_FRAME) {
+        Guard g(h->device);   // for the allocations; the calls below select the device themselves
+        if (int rc = ensure_es(h, B)) return rc;
+        C = std::min(B, es_rows(h));
+        if (tdec_planes_bytes(h, C) > h->planes_own.cap) {
+            quiesce(h);
+            if (int rc = h->planes_own.ensure(tdec_planes_bytes(h, C))) return rc;
+        }
+    }
+    if (int rc = order_on(h, (hipStream_t)stream)) return rc;   // planes_own may still be read elsewhere
+    float *planes = (float *)h->planes_own.p;
     for (long r0 = 0; r0 < B; r0 += C) {
         const int n = (int)std::min<long>(C, B - r0);
-        FrArgs a{n, N, h->iters, d_planes + (r0 / WAVE) * tile_floats(N), (double2 *)h->ll_ws.p, d_bits + r0 * 2 * N,
-                 d_lfinal ? d_lfinal + r0 * 2 * N : nullptr, h->n_used, lg ? (double2 *)h->ll_ws.p + (size_t)n * N : nullptr};
-        hipLaunchKernelGGL(kern, dim3((unsigned)n), dim3(FR_BLOCK), fr_lds(N, true, lg).total, st, a,
-                           (const int *)h->d_perm, (const int *)h->d_inv, (const int *)h->d_ford,
-                           d_n_iter ? d_n_iter + r0 : nullptr);
-        HIPCHK(hipGetLastError());
-    }
-    return mark_used(h, st);
-}
-
-int tdec_decode_batch_es_dev(tdec_t *h, int B, const float *d_llr, long llr_stride, int32_t *d_bits, double *d_lfinal,
-                             int32_t *d_n_iter, void *stream) {
-    if (!h || B < 0) return fail(TDEC_EINVAL, "bad decode arguments");
-    if (B == 0) return 0;
-    if (!d_llr || !d_bits) return fail(TDEC_EINVAL, "bad decode arguments");
-    if (llr_stride < h->llr_len) return fail(TDEC_ESHORT, "llr rows shorter than the de-puncture walk");
-    if (int rc = es_available(h)) return rc;
-    Guard g(h->device);
-    if (int rc = ensure_es(h, B)) return rc;
-    // the handle's own planes hold one chunk (sized on first use, like the workspace)
-    const int C = std::min(B, es_rows(h));
-    if (tdec_planes_bytes(h, C) > h->planes_own.cap) {
-        quiesce(h);
-        if (int rc = h->planes_own.ensure(tdec_planes_bytes(h, C))) return rc;
-    }
-    if (int rc = order_on(h, (hipStream_t)stream)) return rc;
-    for (long r0 = 0; r0 < B; r0 += C) {
-        const int n = (int)std::min<long>(C, B - r0);
-        int rc = tdec_depuncture_dev(h, n, d_llr + r0 * llr_stride, llr_stride, (float *)h->planes_own.p, stream);
-        if (!rc)
-            rc = tdec_decode_planes_es_dev(h, n, (const float *)h->planes_own.p, d_bits + r0 * 2 * h->N,
-                                           d_lfinal ? d_lfinal + r0 * 2 * h->N : nullptr,
-                                           d_n_iter ? d_n_iter + r0 : nullptr, stream);
+        int32_t *bits = d_bits + r0 * 2 * h->N, *n_iter = d_n_iter ? d_n_iter + r0 : nullptr;
+        double *lfinal = d_lfinal ? d_lfinal + r0 * 2 * h->N : nullptr;
+        int rc = tdec_depuncture_dev(h, n, d_llr + r0 * llr_stride, llr_stride, planes, stream);
+        if (!rc && mode == DEC_PLAIN) rc = tdec_decode_planes_dev(h, n, planes, bits, lfinal, stream);
+        if (!rc && mode == DEC_ES_FRAME) rc = tdec_decode_planes_es_dev(h, n, planes, bits, lfinal, n_iter, stream);
+        if (!rc && mode == DEC_ES_TILE) rc = tdec_decode_planes_es_tile_dev(h, n, planes, bits, lfinal, n_iter, stream);
         if (rc) return rc;
     }
-    return 0;
-}
-
-// ---- early stop on the throughput tile decoder (DESIGN §8.1) ---------------------------
-// k_turbo_decode_es / k_turbo_decode_logmap_es: the persistent tile loop with per-lane
-// termination.  Every batch size and every N of the tables runs on it (no frame kernel:
-// TDEC_FRAME does not matter).  Capacity as tdec_decode_planes_dev: tdec_reserve sizes
-// the workspace and a larger call is TDEC_ECAPACITY; a batch that tdec_reserve covered
-// with the small-batch decoders' workspace only gets the tile workspace on first use.
-// Tiles take different times here, so the launch draws tiles from the queue whenever a
-// wave serves more than one (tile_queue()'s 4 x waves threshold is a measurement of the
-// fixed-iteration kernel).  TDEC_ES_TILE_WAVES (read per call) caps the persistent waves
-// of the launch: tests make one or two waves serve several tiles with it.
-int tdec_decode_planes_es_tile_dev(tdec_t *h, int B, const float *d_planes, int32_t *d_bits, double *d_lfinal,
-                                   int32_t *d_n_iter, void *stream) {
-    if (!h || B < 0) return fail(TDEC_EINVAL, "bad decode arguments");
-    if (B == 0) return 0;
-    if (!d_planes || !d_bits) return fail(TDEC_EINVAL, "bad decode arguments");
-    Guard g(h->device);
-    hipStream_t st = (hipStream_t)stream;
-    const int tiles = n_tiles_of(B);
-    const int full = std::min(tiles, h->max_waves);
-    if (full > h->ws_waves) {
-        if (B > h->cap_batch) return fail(TDEC_ECAPACITY, "workspace too small: call tdec_reserve first");
-        quiesce(h);   // regrowth frees
-        if (int rc = ensure_ws(h, full)) return rc;
-    }
-    int waves = full;
-    if (const char *pc = getenv("TDEC_ES_TILE_WAVES")) waves = std::max(1, std::min(waves, atoi(pc)));
-    if (int rc = order_on(h, st)) return rc;
-    int *queue = nullptr;
-    if (tiles > waves) {
-        HIPCHK(hipMemsetAsync(h->d_tile_ctr, 0, sizeof(int), st));
-        queue = h->d_tile_ctr;
-    }
-    DecodeArgs a{B, h->N, h->iters, tiles, waves, d_planes, h->le_p, h->ck_p, d_bits, d_lfinal, h->d_used,
-                 waves * WAVE, h->aux_p, queue, ck_rows_of(h)};
-    if (h->d_simd_prog && hipMemsetAsync(h->d_simd_prog, 0, SIMD_PROG_BYTES, st) == hipSuccess) a.simd_prog = h->d_simd_prog;
-    const EsArgs e{d_n_iter, h->prev_p};
-    const int *pm = h->d_perm, *iv = h->d_inv;
-    const dim3 grid((waves + DEC_WAVES - 1) / DEC_WAVES);
-    hipLaunchKernelGGL((decode_es_fn)decode_es_kernel(h->algo, h->N % win_of(h->algo) != 0), grid, dim3(DEC_BLOCK), 0,
-                       st, a, pm, iv, (const int *)h->d_used, e);
-    HIPCHK(hipGetLastError());
-    return mark_used(h, st);
-}
-
-int tdec_decode_batch_es_tile_dev(tdec_t *h, int B, const float *d_llr, long llr_stride, int32_t *d_bits,
-                                  double *d_lfinal, int32_t *d_n_iter, void *stream) {
-    if (!h || B < 0) return fail(TDEC_EINVAL, "bad decode arguments");
-    if (B == 0) return 0;
-    if (!d_llr || !d_bits) return fail(TDEC_EINVAL, "bad decode arguments");
-    if (B > h->cap_batch) return fail(TDEC_ECAPACITY, "batch larger than tdec_reserve()");
-    if (int rc = order_on(h, (hipStream_t)stream)) return rc;   // planes_own may still be read elsewhere
-    int rc = tdec_depuncture_dev(h, B, d_llr, llr_stride, (float *)h->planes_own.p, stream);
-    if (!rc)
-        rc = tdec_decode_planes_es_tile_dev(h, B, (const float *)h->planes_own.p, d_bits, d_lfinal, d_n_iter, stream);
-    return rc;
-}
-
-// The host-pointer call: chunks of tdec_decode_batch's size (TDEC_HOST_CHUNK overrides
-// it), one after the other on the handle's stream.
-int tdec_decode_batch_es_tile(tdec_t *h, int B, const float *llr, long llr_stride, int32_t *bits, double *lfinal,
-                              int32_t *n_iter) {
-    if (!h || B < 0) return fail(TDEC_EINVAL, "bad decode arguments");
-    if (llr_stride < h->llr_len) return fail(TDEC_ESHORT, "llr rows shorter than the de-puncture walk");
-    if (B == 0) return 0;
-    if (!llr || !bits) return fail(TDEC_EINVAL, "bad decode arguments");
-    Guard g(h->device);
-    quiesce(h);
-    long chunk = std::max(1L, (long)h->max_waves / 2) * WAVE;
-    if (const char *pc = getenv("TDEC_HOST_CHUNK")) chunk = std::max(1L, atol(pc));
-    const int C = (int)std::min<long>(B, chunk);
-    const size_t row_b = (size_t)2 * h->N;
-    int rc = tdec_reserve(h, C);
-    if (!rc) rc = h->h_llr.ensure((size_t)C * llr_stride * sizeof(float));
-    if (!rc) rc = h->h_bits.ensure(C * row_b * sizeof(int32_t));
-    if (!rc && lfinal) rc = h->h_lf.ensure(C * row_b * sizeof(double));
-    if (!rc && n_iter) rc = h->h_nit.ensure((size_t)C * sizeof(int32_t));
-    if (rc) return rc;
-    DrainOnExit drain{h->stream, nullptr};
-    for (long r0 = 0; r0 < B; r0 += C) {
-        const size_t n = (size_t)std::min<long>(C, B - r0);
-        HIPCHK(hipMemcpyAsync(h->h_llr.p, llr + r0 * llr_stride, n * llr_stride * sizeof(float), hipMemcpyHostToDevice,
-                              h->stream));
-        if ((rc = tdec_decode_batch_es_tile_dev(h, (int)n, (const float *)h->h_llr.p, llr_stride, (int32_t *)h->h_bits.p,
-                                                lfinal ? (double *)h->h_lf.p : nullptr,
-                                                n_iter ? (int32_t *)h->h_nit.p : nullptr, h->stream)))
-            return rc;
-        HIPCHK(hipMemcpyAsync(bits + r0 * row_b, h->h_bits.p, n * row_b * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
-        if (lfinal)
-            HIPCHK(hipMemcpyAsync(lfinal + r0 * row_b, h->h_lf.p, n * row_b * sizeof(double), hipMemcpyDeviceToHost,
-                                  h->stream));
-        if (n_iter)
-            HIPCHK(hipMemcpyAsync(n_iter + r0, h->h_nit.p, n * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
-    }
-    HIPCHK(hipStreamSynchronize(h->stream));
-    drain.disarm();
-    mark_idle(h);
     return 0;
 }
 
@@ -1305,17 +1171,63 @@ int tdec_decode_batch_es_tile(tdec_t *h, int B, const float *llr, long llr_strid
 constexpr int ZC_MAX_ROWS = 64;
 static bool zero_copy(int B) { return B <= ZC_MAX_ROWS; }
 
+// The page-locked staging of a small host-pointer decode: LLR rows, bits, L_final and (early stop) n_iter.
+struct Staging {
+    size_t in_b, bits_b, lf_b, ni_b, o_bits, o_lf, o_ni, pin_b;
+    Staging(const tdec_t *h, int B, long llr_stride, bool lfinal, bool n_iter)
+        : in_b((size_t)B * llr_stride * sizeof(float)), bits_b((size_t)B * 2 * h->N * sizeof(int32_t)),
+          lf_b(lfinal ? (size_t)B * 2 * h->N * sizeof(double) : 0), ni_b(n_iter ? (size_t)B * sizeof(int32_t) : 0),
+          o_bits(up256(in_b)), o_lf(up256(o_bits + bits_b)), o_ni(n_iter ? up256(o_lf + lf_b) : o_lf + lf_b),
+          pin_b(o_ni + ni_b) {}
+    void copy_in(char *pin, const float *llr) const { std::memcpy(pin, llr, in_b); }
+    void copy_out(const char *pin, int32_t *bits, double *lfinal, int32_t *n_iter) const {
+        std::memcpy(bits, pin + o_bits, bits_b);
+        if (lfinal) std::memcpy(lfinal, pin + o_lf, lf_b);
+        if (n_iter) std::memcpy(n_iter, pin + o_ni, ni_b);
+    }
+};
 
-// Host-pointer decode in chunks, so device memory stays bounded for any B:
-// by default half the resident-wave capacity (65 536 codewords on MI355X);
-// TDEC_HOST_CHUNK overrides it (tests use a small value to exercise the chunk
-// loop).  Three streams and two alternating device buffers per direction:
-// uploads (h->cstream), decodes (h->stream) and downloads (h->dstream), so the
-// upload of chunk i+1, the decode of chunk i and the download of chunk i-1 run
-// at once (the two PCIe directions and the GPU).  With pageable host memory HIP
-// stages every copy through its own pinned buffer on the CPU, which caps the
-// path at the host's staging rate; host buffers from tdec_host_alloc (or
-// registered by the caller) go straight to the DMA engines.
+// The end of a host-pointer call on the handle's stream: once that is waited for, the exit drain has nothing left
+// to do and nothing is queued on the handle's buffers; a small call's outputs (s) then go to the caller.
+static int settle(tdec_t *h, DrainOnExit &drain, const Staging *s = nullptr, int32_t *bits = nullptr,
+                  double *lfinal = nullptr, int32_t *n_iter = nullptr) {
+    HIPCHK(hipStreamSynchronize(h->stream));
+    drain.disarm();
+    mark_idle(h);
+    if (s) s->copy_out((const char *)h->pin.p, bits, lfinal, n_iter);
+    return 0;
+}
+// The chunk of tdec_decode_batch and tdec_decode_batch_es_tile: half the resident-wave capacity by default.
+static long tile_host_chunk(const tdec_t *h) { return host_chunk(std::max(1L, (long)h->max_waves / 2) * WAVE); }
+
+// The serial chunk loop of the early-stop host-pointer calls: C rows at a time through the device staging, one
+// chunk after the other on the handle's stream -- upload, decode(n, d_llr, d_bits, d_lfinal), download of
+// bits / L_final / n_iter (from h_nit, which the caller has sized) -- and one wait at the end.
+template <typename Decode>
+static int host_chunks(tdec_t *h, int B, int C, const float *llr, long llr_stride, int32_t *bits, double *lfinal,
+                       int32_t *n_iter, Decode decode) {
+    const size_t row_b = (size_t)2 * h->N;
+    int rc = h->h_llr.ensure((size_t)C * llr_stride * sizeof(float));
+    if (!rc) rc = h->h_bits.ensure(C * row_b * sizeof(int32_t));
+    if (!rc && lfinal) rc = h->h_lf.ensure(C * row_b * sizeof(double));
+    if (rc) return rc;
+    DrainOnExit drain{h->stream, nullptr};
+    for (long r0 = 0; r0 < B; r0 += C) {
+        const size_t n = (size_t)std::min<long>(C, B - r0);
+        HIPCHK(hipMemcpyAsync(h->h_llr.p, llr + r0 * llr_stride, n * llr_stride * sizeof(float), hipMemcpyHostToDevice,
+                              h->stream));
+        if ((rc = decode((int)n, (const float *)h->h_llr.p, (int32_t *)h->h_bits.p, lfinal ? (double *)h->h_lf.p : nullptr)))
+            return rc;
+        HIPCHK(hipMemcpyAsync(bits + r0 * row_b, h->h_bits.p, n * row_b * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+        if (lfinal)
+            HIPCHK(hipMemcpyAsync(lfinal + r0 * row_b, h->h_lf.p, n * row_b * sizeof(double), hipMemcpyDeviceToHost,
+                                  h->stream));
+        if (n_iter)
+            HIPCHK(hipMemcpyAsync(n_iter + r0, h->h_nit.p, n * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+    }
+    return settle(h, drain);
+}
+
 constexpr size_t SMALL_CALL_BYTES = 16u << 20;
 struct EventPair {
     hipEvent_t e[2] = {nullptr, nullptr};
@@ -1330,63 +1242,193 @@ struct EventPair {
     }
 };
 
-int tdec_decode_batch(tdec_t *h, int B, const float *llr, long llr_stride, int32_t *bits, double *lfinal) {
+extern "C" {
+
+int tdec_decode_planes_dev(tdec_t *h, int B, const float *d_planes, int32_t *d_bits, double *d_lfinal,
+                           void *stream) {
+    CHECK_ARGS(h, B, d_planes, d_bits);
+    Guard g(h->device);
+    hipStream_t st = (hipStream_t)stream;
+    if (use_lowlat(h, B)) {
+        if (int rc = order_on(h, st)) return rc;
+        if (use_frame_decoder(h)) {
+            if (int rc = frame_lds_attr(h->device)) return rc;
+            if (int rc = launch_frame_decode(h, false, B, d_planes, d_bits, d_lfinal, nullptr, st)) return rc;
+            return mark_used(h, st);
+        }
+        LLArgs a{B, h->N, h->iters, d_planes, (double2 *)h->ll_ws.p, (float *)h->ll_st.p, d_bits, d_lfinal,
+                 (const int *)h->d_ulist, h->n_used};
+        hipLaunchKernelGGL(k_turbo_decode_lowlat, dim3((unsigned)B), dim3(WAVE), ll_lds_bytes(h->N), st, a,
+                           (const int *)h->d_perm, (const int *)h->d_inv);
+        HIPCHK(hipGetLastError());
+        return mark_used(h, st);
+    }
+    const int tiles = n_tiles_of(B), waves = std::min(tiles, h->max_waves);
+    if (waves > h->ws_waves) return fail(TDEC_ECAPACITY, "workspace too small: call tdec_reserve first");
+    if (int rc = order_on(h, st)) return rc;
+    // the tile queue from 4 tiles per wave (tile_queue()); the one launch that raises the tail flag
+    return launch_tiles(h, decode_kernel(h->algo, h->N % win_of(h->algo) != 0), DEC_WAVES, B, waves, d_planes, d_bits,
+                        d_lfinal, tile_queue(h, tiles, waves, st), TL_ISSUE_PRIO | TL_TAIL, st);
+}
+
+int tdec_tail_gate(tdec_t *h, void *stream) {
+    if (!h) return fail(TDEC_EINVAL, "bad tail gate arguments");
+    if (!h->tail_seq) return 0;   // no throughput launch yet: nothing to wait for
+    Guard g(h->device);
+    hipLaunchKernelGGL(k_tail_gate, dim3(1), dim3(WAVE), 0, (hipStream_t)stream, (const unsigned *)h->d_tail,
+                       h->tail_seq);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+int tdec_decode_batch_dev(tdec_t *h, int B, const float *d_llr, long llr_stride, int32_t *d_bits, double *d_lfinal,
+                          void *stream) {
+    // not CHECK_ARGS: this form reports TDEC_ECAPACITY before any look at its pointers, which
+    // tdec_depuncture_dev (d_llr, the stride) and tdec_decode_planes_dev (d_bits) then check
     if (!h || B < 0) return fail(TDEC_EINVAL, "bad decode arguments");
-    if (llr_stride < h->llr_len) return fail(TDEC_ESHORT, "llr rows shorter than the de-puncture walk");
     if (B == 0) return 0;
-    if (!llr || !bits) return fail(TDEC_EINVAL, "bad decode arguments");
+    return decode_batch_dev(h, DEC_PLAIN, B, d_llr, llr_stride, d_bits, d_lfinal, nullptr, stream);
+}
+
+int tdec_es_capacity(tdec_t *h) {
+    if (!h) return fail(TDEC_EINVAL, "null handle");
+    if (int rc = es_available(h)) return rc;
+    return es_rows(h);
+}
+
+int tdec_early_stop_available(int n_couples) {
+    const char *e = getenv("TDEC_FRAME");
+    return !(e && e[0] == '0') && n_couples > 0 && frame_fits(n_couples, true);
+}
+
+int tdec_decode_planes_es_dev(tdec_t *h, int B, const float *d_planes, int32_t *d_bits, double *d_lfinal,
+                              int32_t *d_n_iter, void *stream) {
+    CHECK_ARGS(h, B, d_planes, d_bits);
+    if (int rc = es_available(h)) return rc;
+    Guard g(h->device);
+    hipStream_t st = (hipStream_t)stream;
+    if (int rc = ensure_es(h, B)) return rc;
+    if (int rc = frame_lds_attr(h->device)) return rc;
+    if (int rc = order_on(h, st)) return rc;
+    const int C = es_rows(h), N = h->N;
+    // chunks of C rows (whole tiles) reuse the workspace one after the other on the stream
+    for (long r0 = 0; r0 < B; r0 += C) {
+        const int n = (int)std::min<long>(C, B - r0);
+        if (int rc = launch_frame_decode(h, true, n, d_planes + (r0 / WAVE) * tile_floats(N), d_bits + r0 * 2 * N,
+                                         d_lfinal ? d_lfinal + r0 * 2 * N : nullptr, d_n_iter ? d_n_iter + r0 : nullptr, st))
+            return rc;
+    }
+    return mark_used(h, st);
+}
+
+int tdec_decode_batch_es_dev(tdec_t *h, int B, const float *d_llr, long llr_stride, int32_t *d_bits, double *d_lfinal,
+                             int32_t *d_n_iter, void *stream) {
+    CHECK_ARGS(h, B, d_llr, d_bits);
+    if (llr_stride < h->llr_len) return fail(TDEC_ESHORT, "llr rows shorter than the de-puncture walk");
+    if (int rc = es_available(h)) return rc;
+    return decode_batch_dev(h, DEC_ES_FRAME, B, d_llr, llr_stride, d_bits, d_lfinal, d_n_iter, stream);
+}
+
+// ---- early stop on the throughput tile decoder (DESIGN §8.1) ---------------------------
+// k_turbo_decode_es / k_turbo_decode_logmap_es: the persistent tile loop with per-lane
+// termination.  Every batch size and every N of the tables runs on it (no frame kernel:
+// TDEC_FRAME does not matter).  Capacity as tdec_decode_planes_dev: tdec_reserve sizes
+// the workspace and a larger call is TDEC_ECAPACITY; a batch that tdec_reserve covered
+// with the small-batch decoders' workspace only gets the tile workspace on first use.
+// Tiles take different times here, so the launch draws tiles from the queue whenever a
+// wave serves more than one (tile_queue()'s 4 x waves threshold is a measurement of the
+// fixed-iteration kernel).  TDEC_ES_TILE_WAVES (read per call) caps the persistent waves
+// of the launch: tests make one or two waves serve several tiles with it.
+int tdec_decode_planes_es_tile_dev(tdec_t *h, int B, const float *d_planes, int32_t *d_bits, double *d_lfinal,
+                                   int32_t *d_n_iter, void *stream) {
+    CHECK_ARGS(h, B, d_planes, d_bits);
+    Guard g(h->device);
+    hipStream_t st = (hipStream_t)stream;
+    const int tiles = n_tiles_of(B), full = std::min(tiles, h->max_waves);
+    if (full > h->ws_waves) {
+        if (B > h->cap_batch) return fail(TDEC_ECAPACITY, "workspace too small: call tdec_reserve first");
+        quiesce(h);   // regrowth frees
+        if (int rc = ensure_ws(h, full)) return rc;
+    }
+    int waves = full;
+    if (const char *pc = getenv("TDEC_ES_TILE_WAVES")) waves = std::max(1, std::min(waves, atoi(pc)));
+    if (int rc = order_on(h, st)) return rc;
+    int *queue = tiles > waves ? h->d_tile_ctr : nullptr;   // not tile_queue()'s threshold (above)
+    if (queue) HIPCHK(hipMemsetAsync(queue, 0, sizeof(int), st));
+    return launch_tiles(h, decode_es_kernel(h->algo, h->N % win_of(h->algo) != 0), DEC_WAVES, B, waves, d_planes, d_bits,
+                        d_lfinal, queue, TL_ISSUE_PRIO, st, EsArgs{d_n_iter, h->prev_p});
+}
+
+int tdec_decode_batch_es_tile_dev(tdec_t *h, int B, const float *d_llr, long llr_stride, int32_t *d_bits,
+                                  double *d_lfinal, int32_t *d_n_iter, void *stream) {
+    CHECK_ARGS(h, B, d_llr, d_bits);   // the pointers first here, then TDEC_ECAPACITY
+    return decode_batch_dev(h, DEC_ES_TILE, B, d_llr, llr_stride, d_bits, d_lfinal, d_n_iter, stream);
+}
+
+// The host-pointer call: chunks of tdec_decode_batch's size (TDEC_HOST_CHUNK overrides
+// it), one after the other on the handle's stream.
+int tdec_decode_batch_es_tile(tdec_t *h, int B, const float *llr, long llr_stride, int32_t *bits, double *lfinal,
+                              int32_t *n_iter) {
+    CHECK_ARGS(h, B, llr, bits, &llr_stride);
+    Guard g(h->device);
+    quiesce(h);
+    const int C = (int)std::min<long>(B, tile_host_chunk(h));
+    if (int rc = tdec_reserve(h, C)) return rc;
+    if (int rc = n_iter ? h->h_nit.ensure((size_t)C * sizeof(int32_t)) : 0) return rc;
+    int32_t *d_nit = n_iter ? (int32_t *)h->h_nit.p : nullptr;
+    return host_chunks(h, B, C, llr, llr_stride, bits, lfinal, n_iter,
+                       [&](int n, const float *d_llr, int32_t *d_bits, double *d_lf) {
+                           return tdec_decode_batch_es_tile_dev(h, n, d_llr, llr_stride, d_bits, d_lf, d_nit, h->stream);
+                       });
+}
+
+// Host-pointer decode in chunks, so device memory stays bounded for any B:
+// by default half the resident-wave capacity (65 536 codewords on MI355X);
+// TDEC_HOST_CHUNK overrides it (tests use a small value to exercise the chunk
+// loop).  Three streams and two alternating device buffers per direction:
+// uploads (h->cstream), decodes (h->stream) and downloads (h->dstream), so the
+// upload of chunk i+1, the decode of chunk i and the download of chunk i-1 run
+// at once (the two PCIe directions and the GPU).  With pageable host memory HIP
+// stages every copy through its own pinned buffer on the CPU, which caps the
+// path at the host's staging rate; host buffers from tdec_host_alloc (or
+// registered by the caller) go straight to the DMA engines.
+int tdec_decode_batch(tdec_t *h, int B, const float *llr, long llr_stride, int32_t *bits, double *lfinal) {
+    CHECK_ARGS(h, B, llr, bits, &llr_stride);
     Guard g(h->device);
     quiesce(h);   // earlier _dev work on other streams may still use the buffers staged below
-    long chunk = std::max(1L, (long)h->max_waves / 2) * WAVE;
-    if (const char *pc = getenv("TDEC_HOST_CHUNK")) chunk = std::max(1L, atol(pc));
-    const int C = (int)std::min<long>(B, chunk);
+    const int C = (int)std::min<long>(B, tile_host_chunk(h));
     const long n_chunks = (B + C - 1) / C;
     // Small calls (one chunk, <= SMALL_CALL_BYTES of traffic; decode() per frame is
     // 12 KB in and 6 KB out): one page-locked staging buffer, one DMA each way on
     // the handle's stream, no events -- the pageable copies' runtime staging and
     // the pipeline's event setup were most of a per-frame call.
-    const size_t in_b = (size_t)B * llr_stride * sizeof(float), bits_b = (size_t)B * 2 * h->N * sizeof(int32_t),
-                 lf_b = lfinal ? (size_t)B * 2 * h->N * sizeof(double) : 0;
-    // page-locked layout: LLR rows, bits, L_final, each at a 256-B boundary (the
-    // zero-copy kernels store int2 / double2 there whatever the row stride)
-    auto up256 = [](size_t x) { return (x + 255) / 256 * 256; };
-    const size_t o_bits = up256(in_b), o_lf = up256(o_bits + bits_b), pin_b = o_lf + lf_b;
-    if (n_chunks == 1 && pin_b <= SMALL_CALL_BYTES) {
+    const Staging s(h, B, llr_stride, lfinal != nullptr, false);
+    if (n_chunks == 1 && s.pin_b <= SMALL_CALL_BYTES) {
         int rc = tdec_reserve(h, B);
-        if (!rc) rc = h->h_llr.ensure(in_b);
-        if (!rc) rc = h->h_bits.ensure(bits_b);
-        if (!rc && lfinal) rc = h->h_lf.ensure(lf_b);
-        if (!rc) rc = h->pin.ensure(pin_b);
+        if (!rc) rc = h->h_llr.ensure(s.in_b);
+        if (!rc) rc = h->h_bits.ensure(s.bits_b);
+        if (!rc && lfinal) rc = h->h_lf.ensure(s.lf_b);
+        if (!rc) rc = h->pin.ensure(s.pin_b);
         if (rc) return rc;
         DrainOnExit drain{h->stream, nullptr};
         char *pin = (char *)h->pin.p;
-        std::memcpy(pin, llr, in_b);
+        s.copy_in(pin, llr);
         if (zero_copy(B) && use_lowlat(h, B) && use_frame_decoder(h) && h->pin.dev) {
             // zero copy: the de-puncture kernel reads the LLR rows from the page-locked
             // buffer and the frame decoder writes bits / L_final into it
             char *dp = (char *)h->pin.dev;
-            if ((rc = tdec_decode_batch_dev(h, B, (const float *)dp, llr_stride, (int32_t *)(dp + o_bits),
-                                            lfinal ? (double *)(dp + o_lf) : nullptr, h->stream)))
+            rc = tdec_decode_batch_dev(h, B, (const float *)dp, llr_stride, (int32_t *)(dp + s.o_bits),
+                                       lfinal ? (double *)(dp + s.o_lf) : nullptr, h->stream);
+        } else {
+            HIPCHK(hipMemcpyAsync(h->h_llr.p, pin, s.in_b, hipMemcpyHostToDevice, h->stream));
+            if ((rc = tdec_decode_batch_dev(h, B, (const float *)h->h_llr.p, llr_stride, (int32_t *)h->h_bits.p,
+                                            lfinal ? (double *)h->h_lf.p : nullptr, h->stream)))
                 return rc;
-            HIPCHK(hipStreamSynchronize(h->stream));
-            drain.disarm();
-            mark_idle(h);
-            std::memcpy(bits, pin + o_bits, bits_b);
-            if (lfinal) std::memcpy(lfinal, pin + o_lf, lf_b);
-            return 0;
+            HIPCHK(hipMemcpyAsync(pin + s.o_bits, h->h_bits.p, s.bits_b, hipMemcpyDeviceToHost, h->stream));
+            if (lfinal) HIPCHK(hipMemcpyAsync(pin + s.o_lf, h->h_lf.p, s.lf_b, hipMemcpyDeviceToHost, h->stream));
         }
-        HIPCHK(hipMemcpyAsync(h->h_llr.p, pin, in_b, hipMemcpyHostToDevice, h->stream));
-        if ((rc = tdec_decode_batch_dev(h, B, (const float *)h->h_llr.p, llr_stride, (int32_t *)h->h_bits.p,
-                                        lfinal ? (double *)h->h_lf.p : nullptr, h->stream)))
-            return rc;
-        HIPCHK(hipMemcpyAsync(pin + o_bits, h->h_bits.p, bits_b, hipMemcpyDeviceToHost, h->stream));
-        if (lfinal) HIPCHK(hipMemcpyAsync(pin + o_lf, h->h_lf.p, lf_b, hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(hipStreamSynchronize(h->stream));
-        drain.disarm();
-        mark_idle(h);
-        std::memcpy(bits, pin + o_bits, bits_b);
-        if (lfinal) std::memcpy(lfinal, pin + o_lf, lf_b);
-        return 0;
+        if (rc) return rc;
+        return settle(h, drain, &s, bits, lfinal);
     }
     const int nbuf = n_chunks > 1 ? 2 : 1;
     int rc = tdec_reserve(h, C);
@@ -1400,13 +1442,7 @@ int tdec_decode_batch(tdec_t *h, int B, const float *llr, long llr_stride, int32
     hipStream_t us = nbuf == 2 ? h->cstream : h->stream, ds = nbuf == 2 ? h->dstream : h->stream;
     EventPair up, dec, down;
     // declared after the events, so it is destroyed (drains the streams) before they are
-    struct Drain3 {
-        hipStream_t a, b, c;
-        ~Drain3() {
-            for (hipStream_t s : {a, b, c})
-                if (s) hipStreamSynchronize(s);
-        }
-    } drain{h->stream, us != h->stream ? us : nullptr, ds != h->stream ? ds : nullptr};
+    DrainOnExit drain{h->stream, us != h->stream ? us : nullptr, ds != h->stream ? ds : nullptr};
     if ((rc = up.create()) || (rc = dec.create()) || (rc = down.create())) return rc;
     float *dl = (float *)h->h_llr.p;
     int32_t *db = (int32_t *)h->h_bits.p;
@@ -1456,62 +1492,29 @@ int tdec_decode_batch(tdec_t *h, int B, const float *llr, long llr_stride, int32
 // on the handle's stream.
 int tdec_decode_batch_es(tdec_t *h, int B, const float *llr, long llr_stride, int32_t *bits, double *lfinal,
                          int32_t *n_iter) {
-    if (!h || B < 0) return fail(TDEC_EINVAL, "bad decode arguments");
-    if (llr_stride < h->llr_len) return fail(TDEC_ESHORT, "llr rows shorter than the de-puncture walk");
-    if (B == 0) return 0;
-    if (!llr || !bits) return fail(TDEC_EINVAL, "bad decode arguments");
+    CHECK_ARGS(h, B, llr, bits, &llr_stride);
     if (int rc = es_available(h)) return rc;
     Guard g(h->device);
     quiesce(h);
-    const size_t row_b = (size_t)2 * h->N;
-    DrainOnExit drain{h->stream, nullptr};
     if (zero_copy(B)) {
-        const size_t in_b = (size_t)B * llr_stride * sizeof(float), bits_b = B * row_b * sizeof(int32_t),
-                     lf_b = lfinal ? B * row_b * sizeof(double) : 0, ni_b = (size_t)B * sizeof(int32_t);
-        auto up256 = [](size_t x) { return (x + 255) / 256 * 256; };
-        const size_t o_bits = up256(in_b), o_lf = up256(o_bits + bits_b), o_ni = up256(o_lf + lf_b), pin_b = o_ni + ni_b;
-        if (int rc = h->pin.ensure(pin_b)) return rc;
+        const Staging s(h, B, llr_stride, lfinal != nullptr, true);
+        DrainOnExit drain{h->stream, nullptr};
+        if (int rc = h->pin.ensure(s.pin_b)) return rc;
         if (h->pin.dev) {
-            char *pin = (char *)h->pin.p, *dp = (char *)h->pin.dev;
-            std::memcpy(pin, llr, in_b);
-            if (int rc = tdec_decode_batch_es_dev(h, B, (const float *)dp, llr_stride, (int32_t *)(dp + o_bits),
-                                                  lfinal ? (double *)(dp + o_lf) : nullptr, (int32_t *)(dp + o_ni), h->stream))
+            char *dp = (char *)h->pin.dev;
+            s.copy_in((char *)h->pin.p, llr);
+            if (int rc = tdec_decode_batch_es_dev(h, B, (const float *)dp, llr_stride, (int32_t *)(dp + s.o_bits),
+                                                  lfinal ? (double *)(dp + s.o_lf) : nullptr, (int32_t *)(dp + s.o_ni), h->stream))
                 return rc;
-            HIPCHK(hipStreamSynchronize(h->stream));
-            drain.disarm();
-            mark_idle(h);
-            std::memcpy(bits, pin + o_bits, bits_b);
-            if (lfinal) std::memcpy(lfinal, pin + o_lf, lf_b);
-            if (n_iter) std::memcpy(n_iter, pin + o_ni, ni_b);
-            return 0;
+            return settle(h, drain, &s, bits, lfinal, n_iter);
         }
     }
-    long chunk = ES_ROWS_DEFAULT;
-    if (const char *pc = getenv("TDEC_HOST_CHUNK")) chunk = std::max(1L, atol(pc));
-    const int C = (int)std::min<long>(B, chunk);
-    int rc = h->h_llr.ensure((size_t)C * llr_stride * sizeof(float));
-    if (!rc) rc = h->h_bits.ensure(C * row_b * sizeof(int32_t));
-    if (!rc && lfinal) rc = h->h_lf.ensure(C * row_b * sizeof(double));
-    if (!rc) rc = h->h_nit.ensure((size_t)C * sizeof(int32_t));
-    if (rc) return rc;
-    for (long r0 = 0; r0 < B; r0 += C) {
-        const size_t n = (size_t)std::min<long>(C, B - r0);
-        HIPCHK(hipMemcpyAsync(h->h_llr.p, llr + r0 * llr_stride, n * llr_stride * sizeof(float), hipMemcpyHostToDevice,
-                              h->stream));
-        if ((rc = tdec_decode_batch_es_dev(h, (int)n, (const float *)h->h_llr.p, llr_stride, (int32_t *)h->h_bits.p,
-                                           lfinal ? (double *)h->h_lf.p : nullptr, (int32_t *)h->h_nit.p, h->stream)))
-            return rc;
-        HIPCHK(hipMemcpyAsync(bits + r0 * row_b, h->h_bits.p, n * row_b * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
-        if (lfinal)
-            HIPCHK(hipMemcpyAsync(lfinal + r0 * row_b, h->h_lf.p, n * row_b * sizeof(double), hipMemcpyDeviceToHost,
-                                  h->stream));
-        if (n_iter)
-            HIPCHK(hipMemcpyAsync(n_iter + r0, h->h_nit.p, n * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
-    }
-    HIPCHK(hipStreamSynchronize(h->stream));
-    drain.disarm();
-    mark_idle(h);
-    return 0;
+    const int C = (int)std::min<long>(B, host_chunk(ES_ROWS_DEFAULT));
+    if (int rc = h->h_nit.ensure((size_t)C * sizeof(int32_t))) return rc;   // the kernel counts whether asked or not
+    return host_chunks(h, B, C, llr, llr_stride, bits, lfinal, n_iter,
+                       [&](int n, const float *d_llr, int32_t *d_bits, double *d_lf) {
+                           return tdec_decode_batch_es_dev(h, n, d_llr, llr_stride, d_bits, d_lf, (int32_t *)h->h_nit.p, h->stream);
+                       });
 }
 
 // Pinned host memory for the host-pointer entry points (the DMA engines read and
@@ -1621,9 +1624,7 @@ static int siso_batch_impl(tdec_t *h, int B, const T *LcA, const T *LcB, const T
     quiesce(h);
     DrainOnExit drain{h->stream, nullptr};
     // rows in chunks, like tdec_decode_batch: device memory stays bounded for any B
-    long chunk = 4L * h->max_waves * WAVE;
-    if (const char *pc = getenv("TDEC_HOST_CHUNK")) chunk = std::max(1L, atol(pc));
-    const int C = (int)std::min<long>(B, chunk), waves = n_tiles_of(C);
+    const int C = (int)std::min<long>(B, host_chunk(4L * h->max_waves * WAVE)), waves = n_tiles_of(C);
     const size_t N = h->N, cf = (size_t)C * N * sizeof(T), cd = (size_t)C * N * sizeof(double);
     bool fr, spl;
     siso_route(h, F64, B, fr, spl);
@@ -1698,7 +1699,7 @@ static int siso_batch_impl(tdec_t *h, int B, const T *LcA, const T *LcB, const T
 // The caller-filled staging of small SISO calls: 8 slots [rows][N] of 8-byte
 // elements (LcA, LcB, LcW, LcY, LaA, LaB, LeA, LeB), each at a 256-B boundary; a
 // float32 channel-LLR row uses the first half of its slot.
-static size_t siso_slot(const tdec_t *h, int rows) { return ((size_t)rows * h->N * 8 + 255) / 256 * 256; }
+static size_t siso_slot(const tdec_t *h, int rows) { return up256((size_t)rows * h->N * 8); }
 
 // A zero-copy staged call waits for the frame SISO's per-row completion flags
 // (coherent, mapped host memory) instead of the stream: the rows' outputs are in
@@ -1778,7 +1779,7 @@ int tdec_siso_staging(tdec_t *h, int rows, void **buf, size_t *slot_bytes) {
         h->siso_rows = 0;
         if (int rc = h->pin_siso.ensure(8 * siso_slot(h, rows))) return rc;
         // the per-row completion flags (coherent: polled while the kernel runs)
-        if (int rc = h->pin_flags.ensure(((size_t)rows * 4 + 255) / 256 * 256, hipHostMallocCoherent | hipHostMallocMapped))
+        if (int rc = h->pin_flags.ensure(up256((size_t)rows * 4), hipHostMallocCoherent | hipHostMallocMapped))
             return rc;
         h->siso_rows = rows;
         std::memset(h->pin_flags.p, 0, (size_t)rows * 4);
@@ -2058,7 +2059,6 @@ int tdec_count_errors_dev(tdec_t *h, int B, int64_t cw0, uint64_t seed, const in
 }
 
 // ---- fused demap + decode (k_turbo_decode_syms) ---------------------------------------
-typedef void (*fused_fn)(DecodeArgs, const int *, const int *, const int *, FusedDemapArgs);
 
 // The instantiated (algorithm, symbol dtype, bits per symbol) combinations: the
 // BASELINE configurations (QPSK / 16QAM / 256QAM max-log, 8PSK log-MAP); anything
@@ -2105,16 +2105,13 @@ int tdec_demap_decode_dev(tdec_t *h, int B, const float *d_syms, int S, const vo
     hipStream_t st = (hipStream_t)stream;
     if (int rc = order_on(h, st)) return rc;
     if (int rc = h->cons.upload(cons, cons_f64, M, bps, cons_f64 != 0, st)) return rc;
-    DecodeArgs a{B, h->N, h->iters, tiles, waves, nullptr, h->le_p, h->ck_p, d_bits, d_lfinal, h->d_used,
-                 waves * WAVE, h->aux_p, tile_queue(h, tiles, waves, st), ck_rows_of(h)};
-    FusedDemapArgs fa{d_syms, S, std::min<long>((long)S * bps, h->llr_len), (const int *)h->d_src,
-                      (const int *)h->d_off, (float *)h->planes_w.p,
-                      demap_cfg(M, div_f32, -1, noise_var, h->cons.sep), h->cons.buf.p};
-    const dim3 grid((waves + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK);
-    hipLaunchKernelGGL((fused_fn)k, grid, dim3(BLOCK), 0, st, a, (const int *)h->d_perm, (const int *)h->d_inv,
-                       (const int *)h->d_used, fa);
-    HIPCHK(hipGetLastError());
-    return mark_used(h, st);
+    const FusedDemapArgs fa{d_syms, S, std::min<long>((long)S * bps, h->llr_len), (const int *)h->d_src,
+                            (const int *)h->d_off, (float *)h->planes_w.p,
+                            demap_cfg(M, div_f32, -1, noise_var, h->cons.sep), h->cons.buf.p};
+    // no caller's planes (each wave demaps into its own), workgroups of WAVES_PER_BLOCK waves;
+    // this launch neither arms the issue-priority slots nor raises the tail flag
+    return launch_tiles(h, k, WAVES_PER_BLOCK, B, waves, nullptr, d_bits, d_lfinal, tile_queue(h, tiles, waves, st), 0, st,
+                        fa);
 }
 
 int tdec_encode_dev(tdec_t *h, int B, const uint8_t *d_bits, uint8_t *d_coded, void *stream) {

@@ -188,6 +188,28 @@ def test_logmap_rows_equal_the_fixed_decode_with_their_count(n, rate, B, ebn0):
     np.testing.assert_array_equal(nit, frame.decode_batch(llr, return_iters=True)[1])
 
 
+def test_host_pointer_chunks(mixed48, monkeypatch):
+    """B = 130 through tdec_decode_batch_es_tile in chunks of 33 rows (three whole chunks
+    and one of 31): bits, L_final and n_iter equal those of the same call in one chunk,
+    the numpy rule's, and per count the fixed decode's with iterations = n_iter[row]."""
+    c, llr, ref = mixed48
+    rows = np.arange(130) % 64
+    big = np.ascontiguousarray(llr[rows])
+    monkeypatch.delenv("TDEC_HOST_CHUNK", raising=False)
+    whole = c.decode_batch(big, return_lfinal=True, return_iters=True)
+    monkeypatch.setenv("TDEC_HOST_CHUNK", "33")
+    bits, lf, nit = c.decode_batch(big, return_lfinal=True, return_iters=True)
+    monkeypatch.delenv("TDEC_HOST_CHUNK")
+    _equal((bits, lf, nit), whole)
+    _equal((bits, lf, nit), tuple(x[rows] for x in ref))
+    assert len(set(nit.tolist())) >= 3
+    for k in sorted(set(nit.tolist())):
+        at = np.flatnonzero(nit == k)
+        fb, fl = M.DVBRCS2_Turbo(48, "1/3", k, interleaver="valid-perm").decode_batch(big[at], return_lfinal=True)
+        assert np.array_equal(bits[at], fb), k
+        np.testing.assert_array_equal(lf[at], fl)
+
+
 def test_runs_without_the_frame_decoder(mixed48, monkeypatch):
     _, llr, ref = mixed48
     monkeypatch.setenv("TDEC_FRAME", "0")

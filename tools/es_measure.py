@@ -9,8 +9,9 @@ its numpy conversions: the C call tdec_decode_batch / tdec_decode_batch_es with 
 at N = 48 / 212 / 752 r = 1/3, valid-perm, BPSK LLRs at 2 / 4 / 8 dB, 20 frames per
 point, the variants interleaved call by call in one process: this build's plain
 decode, this build's early-stop decode and, with --parent, the parent commit's plain
-decode from its own library (a second code object in the same process, as
-tools/ab.py loads it).  Median ms per call and the mean n_iter.
+decode (and its early-stop decode, where it has one) from its own library (a second
+code object in the same process, as tools/ab.py loads it).  Median ms per call and
+the mean n_iter.
 
 throughput: the configs[2] shape (16QAM, N = 752 r = 1/3, valid-perm) at 2, 4 and 6 dB,
 device-resident planes: the tile decoder at 8 fixed iterations (tdec_decode_planes_dev;
@@ -72,6 +73,10 @@ def latency(a):
             if par:
                 variants["parent_plain"] = lambda f: par.tdec_decode_batch(hp, 1, f.ctypes.data, f.size,
                                                                            bits.ctypes.data, None)
+                if hasattr(par, "tdec_decode_batch_es"):
+                    variants["parent_early_stop"] = lambda f: par.tdec_decode_batch_es(hp, 1, f.ctypes.data, f.size,
+                                                                                       bits.ctypes.data, None,
+                                                                                       nit.ctypes.data)
             order = list(variants)[::-1] if a.reverse else list(variants)
             ts = {k: [] for k in variants}
             its = []
@@ -92,6 +97,8 @@ def latency(a):
             rec["early_stop_over_" + ("parent" if par else "plain")] = round(rec["early_stop_ms"] / ref, 3)
             if par:
                 rec["plain_over_parent"] = round(rec["plain_ms"] / rec["parent_plain_ms"], 3)
+            if "parent_early_stop_ms" in rec:
+                rec["early_stop_over_parent_early_stop"] = round(rec["early_stop_ms"] / rec["parent_early_stop_ms"], 3)
             out["points"].append(rec)
         cur.tdec_destroy(hc)
         if par:
