@@ -173,6 +173,38 @@ int tdec_decode_planes_es_tile_dev(tdec_t *h, int B, const float *d_planes, int3
 int tdec_decode_batch_es_tile_dev(tdec_t *h, int B, const float *d_llr, long llr_stride, int32_t *d_bits,
                                   double *d_lfinal, int32_t *d_n_iter, void *stream);
 
+/* The same rule on the throughput decoder with finished lanes refilled (DESIGN.md
+ * §8.3): a lane whose codeword has ended takes the next undecoded codeword of the
+ * batch, so a wave's trips (one iteration of its 64 lanes each) follow the sum of
+ * the iteration counts, not the per-tile maximum.  Same outputs, bit for bit, as
+ * the calls above (max-log and log-MAP); d_lfinal / d_n_iter nullable; every block
+ * size of the tables, independent of TDEC_FRAME; B = 0 is a no-op; with
+ * iterations = 1 this is the plain decode, n_iter = 1.
+ * Each persistent wave decodes from a plane buffer of its own (one 64-codeword
+ * tile: tdec_planes_bytes(h, 64) per wave), which only tdec_reserve_es_refill
+ * allocates, beside everything tdec_reserve(max_batch) sizes.  The _dev calls never
+ * allocate or synchronise: one beyond what tdec_reserve_es_refill covered is
+ * TDEC_ECAPACITY and writes nothing.  The host-pointer call reserves for itself
+ * and chunks like tdec_decode_batch (TDEC_HOST_CHUNK).  TDEC_ES_TILE_WAVES (read
+ * per call) caps the persistent waves of these launches too.
+ * Refill order: at the top of every trip the wave claims as many consecutive
+ * row indices from the launch's queue as it has free lanes (lanes whose codeword
+ * has ended, or that never had one), and the free lanes take them in ascending
+ * lane order; indices >= B leave a lane idle for the rest of the launch.  With
+ * one wave that order makes `trips` a function of the rows' iteration counts alone.
+ * tdec_es_refill_stats (a diagnostic, like tdec_siso_stats) waits for the device
+ * and returns, summed over the waves of the handle's most recent refill launch,
+ * the trips run and the codewords handed to lanes (= that launch's B); zeros
+ * before the first such launch. */
+int tdec_reserve_es_refill(tdec_t *h, int max_batch);
+int tdec_decode_batch_es_refill(tdec_t *h, int B, const float *llr, long llr_stride, int32_t *bits, double *lfinal,
+                                int32_t *n_iter);
+int tdec_decode_planes_es_refill_dev(tdec_t *h, int B, const float *d_planes, int32_t *d_bits, double *d_lfinal,
+                                     int32_t *d_n_iter, void *stream);
+int tdec_decode_batch_es_refill_dev(tdec_t *h, int B, const float *d_llr, long llr_stride, int32_t *d_bits,
+                                    double *d_lfinal, int32_t *d_n_iter, void *stream);
+int tdec_es_refill_stats(const tdec_t *h, long *trips, long *refills);
+
 /* Soft demapper: compute_llr (test_sdr_with_coding.py:200-225) over any
  * labelled constellation (label i = bits MSB first).  syms: n_sym complex
  * values (f32 pairs, or f64 pairs when sym_f64); cons: M points (host memory,

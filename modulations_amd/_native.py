@@ -34,6 +34,8 @@ EXPORTS = (
     "tdec_decode_batch_es", "tdec_decode_planes_es_dev", "tdec_decode_batch_es_dev", "tdec_es_capacity",
     "tdec_early_stop_available",
     "tdec_decode_batch_es_tile", "tdec_decode_planes_es_tile_dev", "tdec_decode_batch_es_tile_dev",
+    "tdec_reserve_es_refill", "tdec_decode_batch_es_refill", "tdec_decode_planes_es_refill_dev",
+    "tdec_decode_batch_es_refill_dev", "tdec_es_refill_stats",
 )
 
 _lib = None
@@ -85,6 +87,15 @@ def _declare(L):
         L.tdec_decode_planes_es_tile_dev.argtypes = [_vp, C.c_int, _vp, _vp, _vp, _vp, _vp]
         L.tdec_decode_batch_es_tile_dev.argtypes = [_vp, C.c_int, _vp, C.c_long, _vp, _vp, _vp, _vp]
         for f in (L.tdec_decode_batch_es_tile, L.tdec_decode_planes_es_tile_dev, L.tdec_decode_batch_es_tile_dev):
+            f.restype = C.c_int
+    if hasattr(L, "tdec_decode_batch_es_refill"):   # (A/B tools also load older builds without the refill early stop)
+        L.tdec_reserve_es_refill.argtypes = [_vp, C.c_int]
+        L.tdec_decode_batch_es_refill.argtypes = [_vp, C.c_int, _vp, C.c_long, _vp, _vp, _vp]
+        L.tdec_decode_planes_es_refill_dev.argtypes = [_vp, C.c_int, _vp, _vp, _vp, _vp, _vp]
+        L.tdec_decode_batch_es_refill_dev.argtypes = [_vp, C.c_int, _vp, C.c_long, _vp, _vp, _vp, _vp]
+        L.tdec_es_refill_stats.argtypes = [_vp, C.POINTER(C.c_long), C.POINTER(C.c_long)]
+        for f in (L.tdec_reserve_es_refill, L.tdec_decode_batch_es_refill, L.tdec_decode_planes_es_refill_dev,
+                  L.tdec_decode_batch_es_refill_dev, L.tdec_es_refill_stats):
             f.restype = C.c_int
     if hasattr(L, "tdec_tail_gate"):   # (A/B tools also load older builds without it)
         L.tdec_tail_gate.argtypes = [_vp, _vp]

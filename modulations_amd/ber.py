@@ -133,8 +133,9 @@ def arg_parser():
     ap.add_argument("--early-stop", action="store_true",
                     help="stop each codeword once its hard decisions repeat (--iterations is the cap); "
                          "records mean_iters and iter_hist per point")
-    ap.add_argument("--es-decoder", choices=["frame", "tile"], default="frame",
-                    help="with --early-stop: the frame decoder (default) or the throughput tile decoder")
+    ap.add_argument("--es-decoder", choices=["frame", "tile", "refill"], default="frame",
+                    help="with --early-stop: the frame decoder (default), the throughput tile decoder, or "
+                         "the tile decoder that refills finished lanes")
     ap.add_argument("--out", default=None)
     ap.add_argument("--dist-backend", default="nccl", help="nccl (= RCCL) on the node; gloo to rehearse")
     ap.add_argument("--all-on-device0", action="store_true", help="every rank on GPU 0 (rehearsal on a 1-GPU box)")

@@ -344,6 +344,11 @@ const void *decode_es_kernel(int algo, bool ragged) {
     return ragged ? (const void *)k_turbo_decode_es<true> : (const void *)k_turbo_decode_es<false>;
 }
 
+// The refill kernels (§8.3).  Defined at the end of this file: kernel templates are emitted in the order
+// this file first names them, and naming these last puts them behind every other kernel in the code
+// object, whose code (pc-relative distances included) then stays what it was without them.
+const void *decode_refill_kernel(int algo, bool ragged);
+
 // Every page-locked staging layout puts its arrays at 256-byte boundaries (the zero-copy
 // kernels store int2 / double2 there whatever the row stride).
 constexpr size_t up256(size_t x) { return (x + 255) / 256 * 256; }
@@ -401,6 +406,9 @@ struct tdec_ctx {
     ConsCache cons;                    // demapper constellation
     DevBuf spl_ck;                     // checkpoints of the state-per-lane SISO prototype (TDEC_SISO_SPL=1)
     DevBuf planes_w;                   // per-wave plane buffers of the fused demap + decode
+    DevBuf planes_rf;                  // per-wave plane buffers of the early-stop refill decoder (tdec_reserve_es_refill)
+    unsigned long long *d_rf = nullptr; // its {trips, refills} counters and, third, its row queue (zeroed before each launch)
+    bool rf_ran = false;               //   whether a refill launch has been queued on this handle
     DevBuf ll_ws, ll_st;               // small-batch decoders: extrinsic planes (frame: Le1 only), alpha / beta stores
     hipStream_t stream = nullptr;
     hipStream_t cstream = nullptr;     // uploads of the chunked host-pointer path (created on first use)
@@ -549,6 +557,7 @@ int tdec_create(int device, int n_couples, int period, const uint8_t *punct, int
     if (e == hipSuccess) e = hipMalloc(&h->d_dst, sizeof(int32_t) * dst.size());
     if (e == hipSuccess) e = hipMemcpy(h->d_dst, dst.data(), sizeof(int32_t) * dst.size(), hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMalloc(&h->d_tile_ctr, sizeof(int));
+    if (e == hipSuccess) e = hipMalloc(&h->d_rf, 3 * sizeof(unsigned long long));
     if (e == hipSuccess) e = hipMalloc(&h->d_tail, sizeof(unsigned));
     if (e == hipSuccess) e = hipMemset(h->d_tail, 0, sizeof(unsigned));
     if (e == hipSuccess && algo == TDEC_ALGO_MAXLOG) e = hipMalloc(&h->d_simd_prog, SIMD_PROG_BYTES);
@@ -697,6 +706,7 @@ void tdec_destroy(tdec_t *h) {
     hipFree(h->d_decl_n);
     hipFree(h->d_decl_ovf);
     hipFree(h->d_tile_ctr);
+    hipFree(h->d_rf);
     hipFree(h->d_tail);
     if (h->d_simd_prog) hipFree(h->d_simd_prog);
     hipFree(h->d_off);
@@ -715,6 +725,7 @@ void tdec_destroy(tdec_t *h) {
     h->cons.buf.release();
     h->spl_ck.release();
     h->planes_w.release();
+    h->planes_rf.release();
     h->ll_ws.release();
     h->ll_st.release();
     if (h->stream) hipStreamDestroy(h->stream);
@@ -1134,7 +1145,7 @@ static int ensure_es(tdec_t *h, int B) {
 // The body of the three tdec_decode_batch*_dev: de-puncture into the handle's own planes, then the mode's
 // tdec_decode_planes*_dev.  The tile modes take the batch whole and refuse one above tdec_reserve(); the early-stop
 // frame mode walks it in chunks of es_rows() and sizes the planes for one chunk on first use, like its workspace.
-enum DecodeMode { DEC_PLAIN, DEC_ES_FRAME, DEC_ES_TILE };
+enum DecodeMode { DEC_PLAIN, DEC_ES_FRAME, DEC_ES_TILE, DEC_ES_REFILL };
 static int decode_batch_dev(tdec_t *h, DecodeMode mode, int B, const float *d_llr, long llr_stride, int32_t *d_bits,
                             double *d_lfinal, int32_t *d_n_iter, void *stream) {
     if (mode != DEC_ES_FRAME && B > h->cap_batch) return fail(TDEC_ECAPACITY, "batch larger than tdec_reserve()");
@@ -1158,6 +1169,7 @@ static int decode_batch_dev(tdec_t *h, DecodeMode mode, int B, const float *d_ll
         if (!rc && mode == DEC_PLAIN) rc = tdec_decode_planes_dev(h, n, planes, bits, lfinal, stream);
         if (!rc && mode == DEC_ES_FRAME) rc = tdec_decode_planes_es_dev(h, n, planes, bits, lfinal, n_iter, stream);
         if (!rc && mode == DEC_ES_TILE) rc = tdec_decode_planes_es_tile_dev(h, n, planes, bits, lfinal, n_iter, stream);
+        if (!rc && mode == DEC_ES_REFILL) rc = tdec_decode_planes_es_refill_dev(h, n, planes, bits, lfinal, n_iter, stream);
         if (rc) return rc;
     }
     return 0;
@@ -1380,6 +1392,81 @@ int tdec_decode_batch_es_tile(tdec_t *h, int B, const float *llr, long llr_strid
                        [&](int n, const float *d_llr, int32_t *d_bits, double *d_lf) {
                            return tdec_decode_batch_es_tile_dev(h, n, d_llr, llr_stride, d_bits, d_lf, d_nit, h->stream);
                        });
+}
+
+// ---- early stop that refills finished lanes --------------------------------
+// k_turbo_decode_refill / k_turbo_decode_logmap_refill: one persistent wave per 64 lanes, every
+// lane taking the batch's next row when its codeword has ended.  The waves decode from plane
+// buffers of their own (planes_rf, one tile each), which only tdec_reserve_es_refill sizes:
+// a _dev call it did not cover is TDEC_ECAPACITY, and no _dev call allocates or waits.
+static size_t rf_planes_bytes(const tdec_t *h, int waves) { return (size_t)waves * tile_floats(h->N) * sizeof(float); }
+
+int tdec_reserve_es_refill(tdec_t *h, int max_batch) {
+    if (int rc = tdec_reserve(h, max_batch)) return rc;
+    if (max_batch == 0) return 0;
+    Guard g(h->device);
+    const int w = std::min(n_tiles_of(max_batch), h->max_waves);   // (tdec_reserve covers small batches without it)
+    if (w > h->ws_waves || rf_planes_bytes(h, w) > h->planes_rf.cap) quiesce(h);   // regrowth frees
+    int rc = ensure_ws(h, w);
+    if (!rc) rc = h->planes_rf.ensure(rf_planes_bytes(h, w));
+    return rc;
+}
+
+int tdec_decode_planes_es_refill_dev(tdec_t *h, int B, const float *d_planes, int32_t *d_bits, double *d_lfinal,
+                                     int32_t *d_n_iter, void *stream) {
+    CHECK_ARGS(h, B, d_planes, d_bits);
+    Guard g(h->device);
+    hipStream_t st = (hipStream_t)stream;
+    const int full = std::min(n_tiles_of(B), h->max_waves);
+    if (full > h->ws_waves || rf_planes_bytes(h, full) > h->planes_rf.cap)
+        return fail(TDEC_ECAPACITY, "workspace too small: call tdec_reserve_es_refill first");
+    int waves = full;
+    if (const char *pc = getenv("TDEC_ES_TILE_WAVES")) waves = std::max(1, std::min(waves, atoi(pc)));
+    // every wave claims once more than it is given rows: the queue counts to less than B + 64 * waves
+    if ((long)B + (long)WAVE * waves > 2147483647L) return fail(TDEC_EINVAL, "batch too large for the row queue");
+    if (int rc = order_on(h, st)) return rc;
+    HIPCHK(hipMemsetAsync(h->d_rf, 0, 3 * sizeof(unsigned long long), st));
+    h->rf_ran = true;
+    return launch_tiles(h, decode_refill_kernel(h->algo, h->N % win_of(h->algo) != 0), DEC_WAVES, B, waves, d_planes,
+                        d_bits, d_lfinal, (int *)(h->d_rf + 2), TL_ISSUE_PRIO, st, EsArgs{d_n_iter, h->prev_p},
+                        RefillArgs{(float *)h->planes_rf.p, h->d_rf});
+}
+
+int tdec_decode_batch_es_refill_dev(tdec_t *h, int B, const float *d_llr, long llr_stride, int32_t *d_bits,
+                                    double *d_lfinal, int32_t *d_n_iter, void *stream) {
+    CHECK_ARGS(h, B, d_llr, d_bits);   // the pointers first, then TDEC_ECAPACITY (as the _es_tile form)
+    if (std::min(n_tiles_of(B), h->max_waves) > h->ws_waves ||
+        rf_planes_bytes(h, std::min(n_tiles_of(B), h->max_waves)) > h->planes_rf.cap)
+        return fail(TDEC_ECAPACITY, "workspace too small: call tdec_reserve_es_refill first");   // before the de-puncture
+    return decode_batch_dev(h, DEC_ES_REFILL, B, d_llr, llr_stride, d_bits, d_lfinal, d_n_iter, stream);
+}
+
+int tdec_decode_batch_es_refill(tdec_t *h, int B, const float *llr, long llr_stride, int32_t *bits, double *lfinal,
+                                int32_t *n_iter) {
+    CHECK_ARGS(h, B, llr, bits, &llr_stride);
+    Guard g(h->device);
+    quiesce(h);
+    const int C = (int)std::min<long>(B, tile_host_chunk(h));
+    if (int rc = tdec_reserve_es_refill(h, C)) return rc;
+    if (int rc = n_iter ? h->h_nit.ensure((size_t)C * sizeof(int32_t)) : 0) return rc;
+    int32_t *d_nit = n_iter ? (int32_t *)h->h_nit.p : nullptr;
+    return host_chunks(h, B, C, llr, llr_stride, bits, lfinal, n_iter,
+                       [&](int n, const float *d_llr, int32_t *d_bits, double *d_lf) {
+                           return tdec_decode_batch_es_refill_dev(h, n, d_llr, llr_stride, d_bits, d_lf, d_nit, h->stream);
+                       });
+}
+
+int tdec_es_refill_stats(const tdec_t *h, long *trips, long *refills) {
+    if (!h || !trips || !refills) return fail(TDEC_EINVAL, "bad refill stats arguments");
+    *trips = *refills = 0;
+    if (!h->rf_ran) return 0;   // no refill launch yet
+    Guard g(h->device);
+    HIPCHK(hipDeviceSynchronize());
+    unsigned long long v[2];
+    HIPCHK(hipMemcpy(v, h->d_rf, sizeof(v), hipMemcpyDeviceToHost));
+    *trips = (long)v[0];
+    *refills = (long)v[1];
+    return 0;
 }
 
 // Host-pointer decode in chunks, so device memory stays bounded for any B:
@@ -2229,3 +2316,12 @@ int tdec_demap_batch(int device, int mod, int sign, const float *syms_iq, long n
     for (size_t i = 0; i < l64.size(); ++i) llr_out[i] = (float)l64[i];   // decode()'s f32 cast (:466)
     return 0;
 }
+
+// Last on purpose (see its declaration): the first mention of the refill kernels.
+namespace {
+const void *decode_refill_kernel(int algo, bool ragged) {
+    if (algo)
+        return ragged ? (const void *)k_turbo_decode_logmap_refill<true> : (const void *)k_turbo_decode_logmap_refill<false>;
+    return ragged ? (const void *)k_turbo_decode_refill<true> : (const void *)k_turbo_decode_refill<false>;
+}
+}  // namespace

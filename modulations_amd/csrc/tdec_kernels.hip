@@ -1718,6 +1718,257 @@ __global__ __launch_bounds__(DEC_BLOCK) __attribute__((amdgpu_waves_per_eu(DEC_W
                                                       2 * WAVE, es);
 }
 
+// ---- early stop that refills finished lanes (tdec_decode_*_es_refill*) ----
+// What the refill loop takes beyond DecodeArgs and EsArgs.
+struct RefillArgs {
+    float *planes_w = nullptr;             // [n_waves] x tile_floats(N): the plane buffer each wave decodes from
+    unsigned long long *stats = nullptr;   // {trips, refilled codewords} of the launch, zeroed before it
+};
+
+// 16 bits to the even positions of a word (the A signs of 16 couples; the B signs go one up).
+__device__ __forceinline__ uint32_t spread16(uint32_t x) {
+    x = (x | (x << 8)) & 0x00FF00FFu;
+    x = (x | (x << 4)) & 0x0F0F0F0Fu;
+    x = (x | (x << 2)) & 0x33333333u;
+    x = (x | (x << 1)) & 0x55555555u;
+    return x;
+}
+
+// The early-stop tile loop with the lane, not the tile, as the unit that is retired: a
+// lane whose codeword has ended takes the next undecoded codeword of the batch, so a
+// wave's trips follow the sum of the iteration counts instead of the per-tile maximum.
+// Per lane: `cw` (the row it decodes, -1: idle) and `lit` (its iteration index); `fin`
+// and `done` stay the wave-uniform masks of the tile loop, `done` also covering the idle
+// lanes.  The wave decodes from its own plane buffer, so the SISOs' reads stay the
+// coalesced TileIn / TileInPre reads.  At the top of every trip lane 0 claims
+// popcount(done) consecutive rows from the launch's counter (p.tile_ctr), the free lanes
+// take them in ascending lane order, and for each the wave copies the row's column of
+// the caller's planes into the lane's column, zeroes the lane's column of Le2 (iteration
+// 0's a-priori, read through the normal Le2[inv[k]] path) and writes D_0 into the lane's
+// previous-decision rows.  The decision loop is the tile loop's (duplicated: that
+// kernel's code must not change), with the row index taken from the lane.
+template <int ALGO, bool RAG, bool STAGED>
+__device__ __forceinline__ void turbo_decode_refill(const DecodeArgs &p, const int *__restrict__ perm,
+                                                    const int *__restrict__ inv, const int *__restrict__ used,
+                                                    float4 *lv, double2 *ll, uint32_t *epi, int epi_stride,
+                                                    const EsArgs &es, const RefillArgs &rf) {
+    const int lane = threadIdx.x & (WAVE - 1);
+    const int wave = __builtin_amdgcn_readfirstlane(blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6));
+    if (wave >= p.n_waves) return;
+    const int N = p.N;
+    const long NW = (long)N * WAVE;
+    const unsigned rs = (unsigned)p.row_lanes;
+    double2 *P1 = p.ws + (long)wave * WAVE * WS_G, *Le2 = P1 + (long)rows_of(N) * rs, *Le1 = Le2 + (long)rows_of(N) * rs;
+    const int nw = p.ck_rows;
+    float4 *ck = p.ck + (long)wave * WAVE * WS_G;
+    float4 *ring = ck + (long)nw * 4 * rs;
+    double2 *sink = p.aux + WAVE + (long)wave * WAVE;
+    float *base = rf.planes_w + (long)wave * tile_floats(N);
+    float4 *X = reinterpret_cast<float4 *>(base);
+    float2 *Z = reinterpret_cast<float2 *>(base + NW * 4);
+    uint32_t *pvw = es.prev + (long)wave * WAVE;
+    const int prow = (N + 15) >> 4;   // previous-decision rows
+    Prio pr;
+    if (p.simd_prog) {
+        const unsigned hw = __builtin_amdgcn_s_getreg((31 << 11) | 4);     // HW_REG_HW_ID
+        const unsigned xcc = __builtin_amdgcn_s_getreg((31 << 11) | 20);   // HW_REG_XCC_ID
+        const unsigned key = ((xcc & 7u) << 10) | (((hw >> 13) & 7u) << 7) | (((hw >> 12) & 1u) << 6) |
+                             (((hw >> 8) & 15u) << 2) | ((hw >> 4) & 3u);
+        pr.tab = p.simd_prog + key * 16;
+        pr.me = (int)(hw & 15u);
+    }
+    int cw = -1, lit = 0;
+    unsigned long long fin = 0, done = ~0ull;   // done: the lane's outputs are written, or it is idle
+    bool exhausted = false, first = true;
+    long trips = 0, refills = 0;
+    for (;;) {
+        // ---- refill: the free lanes take the next rows of the batch, in ascending lane order
+        if (done != 0 && !exhausted) {
+            const int want = __builtin_popcountll(done);
+            int q = 0;
+            if (lane == 0) q = atomicAdd(p.tile_ctr, want);
+            q = __builtin_amdgcn_readfirstlane(q);
+            exhausted = (long)q + want >= p.B;
+            const bool is_free = __builtin_amdgcn_inverse_ballot_w64(done);
+            const long idx = (long)q + __builtin_amdgcn_mbcnt_hi((unsigned)(done >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)done, 0u));
+            const bool take = is_free && idx < p.B;
+            const unsigned long long newm = __builtin_amdgcn_ballot_w64(take);
+            if (take) {
+                cw = (int)idx;
+                lit = 0;
+            }
+            // lanes of a decoding wave that never get a row (a free lane at the first claim stays free)
+            const unsigned long long zerom = first && newm != 0 ? done & ~newm : 0ull;
+            if ((newm | zerom) != 0) {
+                // the previous trip's stores into these columns (other lanes' instructions) come first
+                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+                for (unsigned long long m = newm; m; m &= m - 1) {
+                    const int l = __builtin_ctzll(m);
+                    const int row = __builtin_amdgcn_readlane(cw, l);
+                    const float *src = p.planes + (long)(row >> 6) * tile_floats(N);
+                    const float4 *sX = reinterpret_cast<const float4 *>(src) + (row & 63);
+                    const float2 *sZ = reinterpret_cast<const float2 *>(src + NW * 4) + (row & 63);
+                    uint32_t *pv = pvw + l;
+                    // lane j moves couple k0 + 64 u + j; four gathers in flight per lane
+                    for (int k0 = 0; k0 < N; k0 += 4 * WAVE) {
+                        float4 x[4];
+                        float2 z[4];
+#pragma unroll
+                        for (int u = 0; u < 4; ++u) {
+                            const int k = k0 + u * WAVE + lane;
+                            x[u] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+                            z[u] = make_float2(0.0f, 0.0f);
+                            if (k < N) {
+                                x[u] = at(sX, (unsigned)k * WAVE);
+                                z[u] = at(sZ, (unsigned)k * WAVE);
+                            }
+                        }
+#pragma unroll
+                        for (int u = 0; u < 4; ++u) {
+                            const int k = k0 + u * WAVE + lane;
+                            const bool on = k < N;
+                            if (on) {
+                                at(X, (unsigned)k * WAVE + l) = x[u];
+                                at(Z, (unsigned)k * WAVE + l) = z[u];
+                                at(Le2, wsrow(k, rs) + l) = make_double2(0.0, 0.0);
+                            }
+                            // D_0: the signs of the systematic channel LLRs, 16 couples per word
+                            const unsigned long long sa = __builtin_amdgcn_ballot_w64(on && x[u].x < 0.0f);
+                            const unsigned long long sb = __builtin_amdgcn_ballot_w64(on && x[u].y < 0.0f);
+                            const int g = lane & 3, r = ((k0 + u * WAVE) >> 4) + g;
+                            const uint32_t w = spread16((uint32_t)(sa >> (16 * g)) & 0xFFFFu) |
+                                               (spread16((uint32_t)(sb >> (16 * g)) & 0xFFFFu) << 1);
+                            if (lane < 4 && r < prow) at(pv, (unsigned)r * rs) = w;
+                        }
+                    }
+                }
+                if (zerom != 0 && __builtin_amdgcn_inverse_ballot_w64(zerom)) {   // an all-zero column, once
+                    for (int k = 0; k < N; ++k) {
+                        at(X, (unsigned)k * WAVE + lane) = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+                        at(Z, (unsigned)k * WAVE + lane) = make_float2(0.0f, 0.0f);
+                        at(Le2, wsrow(k, rs) + lane) = make_double2(0.0, 0.0);
+                    }
+                    for (int r = 0; r < prow; ++r) at(pvw, (unsigned)r * rs + lane) = 0u;
+                }
+                // the new columns were written by other lanes, and the vector L1 may hold their old
+                // lines: publish the stores, invalidate L1 (DemapPro::publish)
+                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+            }
+            done &= ~newm;
+            fin &= ~newm;
+            refills += __builtin_popcountll(newm);
+            first = false;
+        }
+        if (done == ~0ull) break;   // nothing left to decode (a free lane implies the queue is exhausted)
+        // the cap, per lane: a lane on its last allowed iteration ends here
+        fin |= __builtin_amdgcn_ballot_w64(lit >= p.iters - 1) & ~done;
+        ++trips;
+        {
+            const LaneSf sf{fin};
+            run_siso<ALGO, RAG, STAGED>(TileIn{X, Le2, inv, lane, rs}, TileOutPre{P1, Le1, lane, rs, used, sink}, N, ck,
+                                        ring, rs, lane, sf, lv, ll, pr);
+            pr.prog += PRIO_UNITS;
+            run_siso<ALGO, RAG, STAGED>(TileInPre{Z, P1, perm, lane, rs}, TileOut{Le2, lane, rs}, N, ck, ring, rs, lane,
+                                        sf, lv, ll, pr);
+            pr.prog += PRIO_UNITS;
+        }
+        // The decision loop of turbo_decode_tiles<ES>: the same loads, the same expression.
+        const unsigned long long emit = fin & ~done;   // lanes whose final iteration this was
+        const bool lane_emit = __builtin_amdgcn_inverse_ballot_w64(emit);
+        const bool lane_live = !__builtin_amdgcn_inverse_ballot_w64(done);
+        uint32_t *hb = epi + (threadIdx.x >> 6) * epi_stride;
+        uint32_t *pv = pvw + lane;
+        const long nb = 2L * N;
+        bool same = true;
+        for (int kc = 0; kc < N; kc += 32) {
+            uint32_t w0 = 0, w1 = 0;   // this iteration's decisions,
+            uint32_t q0 = 0, q1 = 0;   // the previous one's (D_0 from the refill)
+            double *lo = (p.lfinal && lane_emit) ? p.lfinal + (long)cw * nb : nullptr;
+            const int kn = min(32, N - kc);
+            const unsigned r0 = (unsigned)(kc >> 4) * rs, r1 = r0 + rs;   // rows of w0 / w1 (w1: kn > 16 only)
+            q0 = at(pv, r0);
+            if (kn > 16) q1 = at(pv, r1);
+            for (int kg = 0; kg < kn; kg += 8) {
+                float2 xa[8];
+                double2 la[8], le[8];
+#pragma unroll
+                for (int u = 0; u < 8; ++u) {
+                    const int k = min(kc + kg + u, N - 1);   // past the chunk: a valid row, unused
+                    const float4 x = at(X, k * WAVE + lane);
+                    xa[u] = make_float2(x.x, x.y);
+                    la[u] = at(Le2, wsrow(inv[k], rs) + lane);
+                    le[u] = at(Le1, wsrow(k, rs) + lane);
+                }
+#pragma unroll
+                for (int u = 0; u < 8; ++u) {
+                    const int kk = kg + u, k = kc + kk;
+                    if (kk >= kn) break;   // wave-uniform
+                    const double fa = ((double)xa[u].x + la[u].x) + le[u].x;
+                    const double fb = ((double)xa[u].y + la[u].y) + le[u].y;
+                    const uint32_t two = (fa < 0.0 ? 1u : 0u) | (fb < 0.0 ? 2u : 0u);
+                    if (kk < 16) w0 |= two << (2 * kk);
+                    else w1 |= two << (2 * (kk - 16));
+                    if (lo) *reinterpret_cast<double2 *>(lo + 2 * k) = make_double2(fa, fb);
+                }
+            }
+            same = same && w0 == q0 && w1 == q1;
+            if (lane_live) {   // a done lane stores nothing
+                at(pv, r0) = w0;
+                if (kn > 16) at(pv, r1) = w1;
+            }
+            if (emit == 0) continue;   // wave-uniform: no lane ends on this trip
+            hb[lane] = w0;
+            hb[WAVE + lane] = w1;
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            // the epilogue's 1 KiB-run writer, for the rows that end here; a row's index comes from its lane
+            const int per = (2 * kn + 3) / 4;
+            for (int t = lane; t < WAVE * per; t += WAVE) {   // (WAVE * per: every lane runs every round)
+                const int l = t / per, pc = t - l * per;
+                const long row = __builtin_amdgcn_ds_bpermute(l << 2, cw);
+                if (!((emit >> l) & 1)) continue;   // (idle lanes are never in emit)
+                const uint32_t w = hb[(pc >> 3) * WAVE + l] >> (4 * (pc & 7));
+                const int j = 4 * pc;
+                int32_t *dst = p.bits + row * nb + 2L * kc + j;
+                if (j + 4 <= 2 * kn && (nb & 3) == 0)
+                    *reinterpret_cast<int4 *>(dst) = make_int4(w & 1, (w >> 1) & 1, (w >> 2) & 1, (w >> 3) & 1);
+                else
+                    for (int e = 0; e < 4 && j + e < 2 * kn; ++e) dst[e] = (w >> e) & 1;
+            }
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        }
+        if (lane_emit && es.n_iter) es.n_iter[cw] = lit + 1;
+        if (lane_live) ++lit;
+        done |= emit;
+        fin = __builtin_amdgcn_ballot_w64(same) & ~done;   // agreed: the next iteration is the final one
+    }
+    if (pr.tab && lane == 0) __hip_atomic_store(pr.tab + pr.me, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (lane == 0 && rf.stats) {
+        atomicAdd(rf.stats, (unsigned long long)trips);
+        atomicAdd(rf.stats + 1, (unsigned long long)refills);
+    }
+}
+
+template <bool RAG>
+__global__ __launch_bounds__(DEC_BLOCK) __attribute__((amdgpu_waves_per_eu(DEC_WPE))) void k_turbo_decode_refill(
+    DecodeArgs p, const int *__restrict__ perm, const int *__restrict__ inv, const int *__restrict__ used, EsArgs es,
+    RefillArgs rf) {
+    __shared__ float4 lv[LDS_LV];
+    __shared__ double2 ll[LDS_STAGE];
+    turbo_decode_refill<0, RAG, true>(p, perm, inv, used, lv, ll, reinterpret_cast<uint32_t *>(lv), EPI_STRIDE_ML, es, rf);
+}
+template <bool RAG>
+__global__ __launch_bounds__(DEC_BLOCK) __attribute__((amdgpu_waves_per_eu(DEC_WPE))) void k_turbo_decode_logmap_refill(
+    DecodeArgs p, const int *__restrict__ perm, const int *__restrict__ inv, const int *__restrict__ used, EsArgs es,
+    RefillArgs rf) {
+    __shared__ uint32_t epi[DEC_WAVES * 2 * WAVE];
+    turbo_decode_refill<1, RAG, false>(p, perm, inv, used, nullptr, nullptr, epi, 2 * WAVE, es, rf);
+}
+
 // One SISO over B codewords given as [B][N] rows (the bcjr_max_log_map boundary).
 // Channel LLRs as float32 (Lc*) or, for the F64 kernels, float64 (Lc64*).
 struct SisoArgs {

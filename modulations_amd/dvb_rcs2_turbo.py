@@ -48,6 +48,14 @@ def _std_tables():
     return _TABLES
 
 
+# the early-stop entry points by es_decoder: host-pointer, device LLRs, device planes
+_ES_CALLS = {
+    "frame": ("tdec_decode_batch_es", "tdec_decode_batch_es_dev", "tdec_decode_planes_es_dev"),
+    "tile": ("tdec_decode_batch_es_tile", "tdec_decode_batch_es_tile_dev", "tdec_decode_planes_es_tile_dev"),
+    "refill": ("tdec_decode_batch_es_refill", "tdec_decode_batch_es_refill_dev", "tdec_decode_planes_es_refill_dev"),
+}
+
+
 class _Handle:
     """Owns one tdec_t (device-side codec state).
 
@@ -148,6 +156,13 @@ class DVBRCS2_Turbo:
                           retires a tile once all its codewords have stopped
                           (tdec_decode_*_es_tile*): for batches,
                           every block size, independent of TDEC_FRAME.
+                 'refill' the throughput decoder with finished lanes refilled: a
+                          lane whose codeword has stopped takes the batch's next
+                          one (tdec_decode_*_es_refill*), so a wave
+                          runs the sum of the counts, not each tile's maximum.  As
+                          'tile': batches, every block size, any TDEC_FRAME.
+                          reserve() also sizes one plane buffer per wave;
+                          refill_stats() reports the last launch's trips.
     """
 
     def __init__(self, N_couples, code_rate, iterations=8, *, algo="max-log", inv_perm="numpy",
@@ -176,8 +191,8 @@ class DVBRCS2_Turbo:
         self.n_coded = _t.coded_size(self.N, self.punct)
         self.device = _default_device() if device is None else device
         self.early_stop = bool(early_stop)
-        if es_decoder not in ("frame", "tile"):
-            raise ValueError(f"unknown es_decoder {es_decoder!r} ('frame' or 'tile')")
+        if not isinstance(es_decoder, str) or es_decoder not in _ES_CALLS:
+            raise ValueError(f"unknown es_decoder {es_decoder!r} ('frame', 'tile' or 'refill')")
         self.es_decoder = es_decoder
         if self.early_stop:
             self._require_early_stop()
@@ -186,9 +201,9 @@ class DVBRCS2_Turbo:
 
     def _require_early_stop(self):
         """ValueError where the early-stop entry points cannot serve this codec (a
-        host-side question: asked before any device work).  The tile decoder serves
-        every codec."""
-        if self.es_decoder == "tile":
+        host-side question: asked before any device work).  The tile and refill
+        decoders serve every codec."""
+        if self.es_decoder != "frame":
             return
         if not _n.lib().tdec_early_stop_available(int(self.N)):
             raise ValueError(f"early_stop=True needs the frame decoder, which is unavailable for N = {self.N} "
@@ -265,8 +280,8 @@ class DVBRCS2_Turbo:
         iters = np.full(B, self.iterations, np.int32) if return_iters else None
         if B and self.early_stop:
             self._require_early_stop()
-            h.call("tdec_decode_batch_es_tile" if self.es_decoder == "tile" else "tdec_decode_batch_es", B,
-                   _n.ptr(llr), llr.shape[1], _n.ptr(bits), _n.ptr(lf), _n.ptr(iters))
+            h.call(_ES_CALLS[self.es_decoder][0], B, _n.ptr(llr), llr.shape[1], _n.ptr(bits), _n.ptr(lf),
+                   _n.ptr(iters))
         elif B:
             h.call("tdec_decode_batch", B, _n.ptr(llr), llr.shape[1], _n.ptr(bits), _n.ptr(lf))
         res = (bits,) + ((lf,) if return_lfinal else ()) + ((iters,) if return_iters else ())
@@ -281,7 +296,19 @@ class DVBRCS2_Turbo:
 
     # -- device-resident API (torch tensors on this codec's GPU) -------------------------
     def reserve(self, max_batch):
-        self.handle.call("tdec_reserve", int(max_batch))
+        """Size the workspace for batches of up to max_batch codewords (with
+        early_stop and es_decoder='refill': the per-wave plane buffers too)."""
+        refill = self.early_stop and self.es_decoder == "refill"
+        self.handle.call("tdec_reserve_es_refill" if refill else "tdec_reserve", int(max_batch))
+
+    def refill_stats(self):
+        """(trips, refills) of this codec's most recent es_decoder='refill' launch,
+        summed over its waves (tdec_es_refill_stats; waits for the device): a trip
+        is one iteration of a wave's 64 lanes, a refill one codeword handed to a
+        lane.  (0, 0) before the first such launch."""
+        t, r = C.c_long(0), C.c_long(0)
+        self.handle.call("tdec_es_refill_stats", C.byref(t), C.byref(r))
+        return t.value, r.value
 
     def planes_bytes(self, B):
         return _n.lib().tdec_planes_bytes(self.handle.h, int(B))
@@ -345,8 +372,7 @@ class DVBRCS2_Turbo:
         if lfinal is not None:
             self._dev_check(lfinal, "lfinal", torch.float64, (B, self.k_info))
         if self.early_stop:
-            self.handle.call("tdec_decode_batch_es_tile_dev" if self.es_decoder == "tile"
-                             else "tdec_decode_batch_es_dev", B, _n.ptr(llr), llr.stride(0) if B > 1 else llr.shape[1],
+            self.handle.call(_ES_CALLS[self.es_decoder][1], B, _n.ptr(llr), llr.stride(0) if B > 1 else llr.shape[1],
                              _n.ptr(bits), _n.ptr(lfinal), _n.ptr(n_iter), self._stream(stream))
             return bits
         self.handle.call("tdec_decode_batch_dev", B, _n.ptr(llr), llr.stride(0) if B > 1 else llr.shape[1],
@@ -364,8 +390,7 @@ class DVBRCS2_Turbo:
         self._n_iter_check(n_iter, B)
         if self.early_stop:
             self._require_early_stop()
-            self.handle.call("tdec_decode_planes_es_tile_dev" if self.es_decoder == "tile"
-                             else "tdec_decode_planes_es_dev", B, _n.ptr(planes), _n.ptr(bits), _n.ptr(lfinal),
+            self.handle.call(_ES_CALLS[self.es_decoder][2], B, _n.ptr(planes), _n.ptr(bits), _n.ptr(lfinal),
                              _n.ptr(n_iter), self._stream(stream))
             return bits
         self.handle.call("tdec_decode_planes_dev", B, _n.ptr(planes), _n.ptr(bits), _n.ptr(lfinal),

@@ -82,8 +82,9 @@ class DevicePipeline:
     is stream-ordered and allocation free.
 
     A codec built with early_stop=True decodes through the early-stop frame
-    decoder, or with es_decoder="tile" through the early-stop tile decoder (two
-    launches, never fused); the iterations each codeword of the last batch ran
+    decoder, or with es_decoder="tile" / "refill" through the early-stop tile
+    decoders (two launches, never fused; the codec's reserve() sizes what its
+    decoder needs); the iterations each codeword of the last batch ran
     are in `n_iter` (int32 [B] on the device, first rows)."""
 
     def __init__(self, codec, mod, B, device, fused=False, overlap=False, gate=True):

@@ -16,10 +16,12 @@ the mean n_iter.
 throughput: the configs[2] shape (16QAM, N = 752 r = 1/3, valid-perm) at 2, 4 and 6 dB,
 device-resident planes: the tile decoder at 8 fixed iterations (tdec_decode_planes_dev;
 with --parent also the parent commit's, from its own library), the frame kernel with
-early stop (tdec_decode_planes_es_dev) and the tile decoder with early stop
-(tdec_decode_planes_es_tile_dev), interleaved round by round, HIP events:
-median, min and max ms of --reps rounds, the mean n_iter and the mean over tiles of the
-tile's largest n_iter (the iterations the tile decoder runs)."""
+early stop (tdec_decode_planes_es_dev), the tile decoder with early stop
+(tdec_decode_planes_es_tile_dev) and the tile decoder that refills
+finished lanes (tdec_decode_planes_es_refill_dev, §8.3), interleaved round by round, HIP
+events: median, min and max ms of --reps rounds, the mean n_iter, the mean over tiles of
+the tile's largest n_iter (the iterations the tile decoder runs) and the refill decoder's
+trips per wave (tdec_es_refill_stats of its last launch)."""
 import argparse
 import ctypes as C
 import json
@@ -124,7 +126,9 @@ def throughput(a):
     planes = torch.empty(plain.planes_bytes(B) // 4, dtype=torch.float32, device=dev)
     plain.reserve(B)
     tile.reserve(B)
-    names = ["tile_8_iterations", "frame_early_stop", "tile_early_stop"]
+    refill = M.DVBRCS2_Turbo(752, "1/3", interleaver="valid-perm", early_stop=True, es_decoder="refill")
+    refill.reserve(B)
+    names = ["tile_8_iterations", "frame_early_stop", "tile_early_stop", "refill_early_stop"]
     bits = {k: torch.empty((B, plain.k_info), dtype=torch.int32, device=dev) for k in names}
     nit = {k: torch.zeros(B, dtype=torch.int32, device=dev) for k in names[1:]}
     st = torch.cuda.current_stream()
@@ -132,7 +136,9 @@ def throughput(a):
            "frame_early_stop": lambda: frame.decode_planes_device(planes, B, bits["frame_early_stop"],
                                                                   n_iter=nit["frame_early_stop"]),
            "tile_early_stop": lambda: tile.decode_planes_device(planes, B, bits["tile_early_stop"],
-                                                                n_iter=nit["tile_early_stop"])}
+                                                                n_iter=nit["tile_early_stop"]),
+           "refill_early_stop": lambda: refill.decode_planes_device(planes, B, bits["refill_early_stop"],
+                                                                    n_iter=nit["refill_early_stop"])}
     if par:   # the parent commit's fixed tile decoder, from its own library
         hp = make_handle(par, plain)
         assert par.tdec_reserve(hp, B) == 0, par.tdec_last_error()
@@ -164,7 +170,13 @@ def throughput(a):
                # the iterations a tile runs: the work the tile decoder actually does
                "mean_tile_max_n_iter": float(nt.view(-1, 64).max(1).values.double().mean()),
                "rows_where_bits_differ_from_fixed": int((bits["tile_8_iterations"]
-                                                         != bits["tile_early_stop"]).any(1).sum())}
+                                                         != bits["tile_early_stop"]).any(1).sum()),
+               "refill_vs_tile_rows_differing": int(((bits["refill_early_stop"] != bits["tile_early_stop"]).any(1)
+                                                     | (nit["refill_early_stop"] != nt)).sum())}
+        trips, refills = refill.refill_stats()
+        waves = min(B // 64, refill_waves(refill))
+        rec["refill_trips"], rec["refill_refills"], rec["refill_waves"] = trips, refills, waves
+        rec["refill_trips_per_wave"] = round(trips / waves, 2)
         if not a.skip_frame:
             rec["tile_vs_frame_rows_differing"] = int(((bits["frame_early_stop"] != bits["tile_early_stop"]).any(1)
                                                       | (nit["frame_early_stop"] != nt)).sum())
@@ -176,6 +188,16 @@ def throughput(a):
     if par:
         par.tdec_destroy(hp)
     print(json.dumps(out, indent=1))
+
+
+def refill_waves(codec):
+    """Persistent waves a large refill launch runs: the resident waves of the decode kernel
+    (two per SIMD, eight per CU: its 256 VGPRs and 20 KiB of LDS per wave), or
+    TDEC_ES_TILE_WAVES."""
+    import torch
+    full = 8 * torch.cuda.get_device_properties(codec.device).multi_processor_count
+    cap = os.environ.get("TDEC_ES_TILE_WAVES")
+    return max(1, min(full, int(cap))) if cap else full
 
 
 def main():
