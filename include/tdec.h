@@ -217,6 +217,19 @@ int tdec_demap_dev(int device, const void *d_syms, int sym_f64, long n_sym, cons
 int tdec_demap(int device, const void *syms, int sym_f64, long n_sym, const void *cons, int cons_f64, int M,
                int bps, double noise_var, int div_f32, int sign, double *llr);
 
+/* Log-MAP (exact log-sum) soft demapper (build-defined, no reference
+ * counterpart): with d_i = |s - c_i|^2 and nv = max(noise_var,
+ * 0.005),
+ *   llr_b = sign * clip(log sum_{bit_b(i)=1} exp(-d_i/nv) - log sum_{bit_b(i)=0} exp(-d_i/nv), -30, +30)
+ * of which the demapper above is the max-log approximation.  Same arguments,
+ * dtype rule, sign and output as tdec_demap_dev / tdec_demap, without div_f32
+ * (the result is defined by a tolerance, not by numpy's operation order);
+ * a NaN or infinite symbol gives NaN for each of its bits. */
+int tdec_demap_logmap_dev(int device, const void *d_syms, int sym_f64, long n_sym, const void *cons, int cons_f64,
+                          int M, int bps, double noise_var, int sign, double *d_llr, void *stream);
+int tdec_demap_logmap(int device, const void *syms, int sym_f64, long n_sym, const void *cons, int cons_f64, int M,
+                      int bps, double noise_var, int sign, double *llr);
+
 /* The fixed-signature demapper of SURVEY §8(b) over the reference's built-in
  * Gray constellations (BPSK/QPSK/8PSK/16QAM: test_sdr_with_coding.py:25-100;
  * 64QAM/256QAM: sdr_modem.py:168-207): compute_llr(syms, mod, noise_var)
@@ -241,6 +254,10 @@ int tdec_constellation(int mod, double *iq, int *is_f64);
  * does (:466).  Writes the plane buffer consumed by tdec_decode_planes_dev. */
 int tdec_demap_planes_dev(tdec_t *h, int B, const float *d_syms, int S, const void *cons, int cons_f64, int M,
                           int bps, double noise_var, int div_f32, float *d_planes, void *stream);
+/* The same planes from the log-MAP demapper (tdec_demap_logmap_dev with
+ * sign = -1, rounded to f32). */
+int tdec_demap_planes_logmap_dev(tdec_t *h, int B, const float *d_syms, int S, const void *cons, int cons_f64,
+                                 int M, int bps, double noise_var, float *d_planes, void *stream);
 
 /* Fused soft demap + turbo decode (one launch): what tdec_demap_planes_dev +
  * tdec_decode_planes_dev compute, bit for bit, with each persistent decoder wave

@@ -36,6 +36,7 @@ EXPORTS = (
     "tdec_decode_batch_es_tile", "tdec_decode_planes_es_tile_dev", "tdec_decode_batch_es_tile_dev",
     "tdec_reserve_es_refill", "tdec_decode_batch_es_refill", "tdec_decode_planes_es_refill_dev",
     "tdec_decode_batch_es_refill_dev", "tdec_es_refill_stats",
+    "tdec_demap_logmap_dev", "tdec_demap_logmap", "tdec_demap_planes_logmap_dev",
 )
 
 _lib = None
@@ -105,6 +106,15 @@ def _declare(L):
                              C.c_int, C.c_int, _vp]
     L.tdec_demap_planes_dev.argtypes = [_vp, C.c_int, _vp, C.c_int, _vp, C.c_int, C.c_int, C.c_int, C.c_double,
                                         C.c_int, _vp, _vp]
+    if hasattr(L, "tdec_demap_logmap_dev"):   # (A/B tools also load older builds without the log-MAP demapper)
+        L.tdec_demap_logmap_dev.argtypes = [C.c_int, _vp, C.c_int, C.c_long, _vp, C.c_int, C.c_int, C.c_int,
+                                            C.c_double, C.c_int, _vp, _vp]
+        L.tdec_demap_logmap.argtypes = [C.c_int, _vp, C.c_int, C.c_long, _vp, C.c_int, C.c_int, C.c_int, C.c_double,
+                                        C.c_int, _vp]
+        L.tdec_demap_planes_logmap_dev.argtypes = [_vp, C.c_int, _vp, C.c_int, _vp, C.c_int, C.c_int, C.c_int,
+                                                   C.c_double, _vp, _vp]
+        for f in (L.tdec_demap_logmap_dev, L.tdec_demap_logmap, L.tdec_demap_planes_logmap_dev):
+            f.restype = C.c_int
     L.tdec_encode_dev.argtypes = [_vp, C.c_int, _vp, _vp, _vp]
     L.tdec_demap_batch.argtypes = [C.c_int, C.c_int, C.c_int, _vp, C.c_long, C.c_float, _vp]
     L.tdec_constellation.argtypes = [C.c_int, _vp, C.POINTER(C.c_int)]

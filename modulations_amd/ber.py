@@ -15,7 +15,7 @@ only those int64 counters are all-reduced.  Finished points are written to
 §5).  The file records the sweep's configuration and the generator version;
 a rerun into it with any other configuration (modulation, block size, rate,
 algorithm, iterations, interleaver, codewords per point, base seed, early
-stop and its decoder) or generator is refused instead of mixing two data streams, and each point's
+stop and its decoder, demapper) or generator is refused instead of mixing two data streams, and each point's
 generator key is derived from its Eb/N0 value (not its index in --ebn0), so a
 resumed sweep over a different grid regenerates exactly the same data.
 """
@@ -51,6 +51,8 @@ def sweep_config(a, inv_perm=None):
         cfg["early_stop"] = True
         if getattr(a, "es_decoder", "frame") != "frame":   # (absent at the default, for the same reason)
             cfg["es_decoder"] = a.es_decoder
+    if getattr(a, "demap", "max-log") != "max-log":   # (absent at the default, for the same reason)
+        cfg["demap"] = a.demap
     if inv_perm is not None:
         cfg["inv_perm_digest"] = interleaver_digest(inv_perm)
     return cfg
@@ -136,6 +138,9 @@ def arg_parser():
     ap.add_argument("--es-decoder", choices=["frame", "tile", "refill"], default="frame",
                     help="with --early-stop: the frame decoder (default), the throughput tile decoder, or "
                          "the tile decoder that refills finished lanes")
+    ap.add_argument("--demap", choices=["max-log", "log-map"], default="max-log",
+                    help="the soft demapper in front of the decoder: the reference's max-log, or the exact "
+                         "log-sum it approximates")
     ap.add_argument("--out", default=None)
     ap.add_argument("--dist-backend", default="nccl", help="nccl (= RCCL) on the node; gloo to rehearse")
     ap.add_argument("--all-on-device0", action="store_true", help="every rank on GPU 0 (rehearsal on a 1-GPU box)")
@@ -183,7 +188,7 @@ def main(argv=None):
                             device=device.index, early_stop=a.early_stop, es_decoder=a.es_decoder)
     if world > 1:   # every rank must decode with the same de-interleaver
         S.check_same_interleaver(codec.inv_perm, dist, device if a.dist_backend == "nccl" else "cpu")
-    pipe = DevicePipeline(codec, a.mod, a.batch, device)
+    pipe = DevicePipeline(codec, a.mod, a.batch, device, demap=a.demap)
     results = list(done.values())
     # one untimed batch first: code-object loading and first-launch costs stay out of
     # the first point's figures
@@ -212,6 +217,8 @@ def main(argv=None):
                "step_ms": sum(t[0] for t in times), "decode_ms": sum(t[1] for t in times),
                "step_codewords_per_s": count / max(1e-9, sum(t[0] for t in times) * 1e-3),
                "decode_codewords_per_s": count / max(1e-9, sum(t[1] for t in times) * 1e-3)}
+        if a.demap != "max-log":
+            rec["demap"] = a.demap
         if a.early_stop:
             h = [int(x) for x in cnt[3:].tolist()]
             rec["early_stop"] = True

@@ -313,13 +313,21 @@ static DemapCfg demap_cfg(int M, int div_f32, int sign, double noise_var, int se
     return DemapCfg{M, div_f32, sign, nv, sep, dm_nv_fast(nv)};
 }
 
+// 1 / (nv ln 2): the log-MAP demapper's exponents in bits, once per launch
+static double demap_lm_scale(const DemapCfg &c) { return 1.0 / (c.nv * 0.693147180559945309417); }
+
 template <typename T, typename S>
-int launch_demap(int bps, const S *d_syms, long n_sym, const T *d_cons, DemapCfg c, double *d_llr,
+int launch_demap(bool lm, int bps, const S *d_syms, long n_sym, const T *d_cons, DemapCfg c, double *d_llr,
                         hipStream_t st) {
     const dim3 grid((unsigned)((n_sym + BLOCK - 1) / BLOCK));
+    const double scale = demap_lm_scale(c);
     switch (bps) {
-#define CASE(K) \
-    case K: hipLaunchKernelGGL((k_demap<T, S, K>), grid, dim3(BLOCK), 0, st, d_syms, n_sym, d_cons, c, d_llr); break;
+#define CASE(K)                                                                                                      \
+    case K:                                                                                                          \
+        if (lm) hipLaunchKernelGGL((k_demap_lm<T, S, K>), grid, dim3(BLOCK), 0, st, d_syms, n_sym, d_cons, c, scale, \
+                                   d_llr);                                                                           \
+        else hipLaunchKernelGGL((k_demap<T, S, K>), grid, dim3(BLOCK), 0, st, d_syms, n_sym, d_cons, c, d_llr);      \
+        break;
         CASE(1) CASE(2) CASE(3) CASE(4) CASE(5) CASE(6) CASE(7) CASE(8)
 #undef CASE
     default: return fail(TDEC_EINVAL, "bps must be 1..8");
@@ -1897,8 +1905,9 @@ int tdec_siso_batch_f64(tdec_t *h, int B, const double *LcA, const double *LcB, 
     return siso_batch_impl<double>(h, B, LcA, LcB, LcW, LcY, LaA, LaB, sf, LeA, LeB);
 }
 
-int tdec_demap_dev(int device, const void *d_syms, int sym_f64, long n_sym, const void *cons, int cons_f64, int M,
-                   int bps, double noise_var, int div_f32, int sign, double *d_llr, void *stream) {
+// The flat demappers' entry (lm: the log-MAP kernels; div_f32 is the max-log path's alone)
+static int demap_dev(bool lm, int device, const void *d_syms, int sym_f64, long n_sym, const void *cons, int cons_f64,
+                     int M, int bps, double noise_var, int div_f32, int sign, double *d_llr, void *stream) {
     if (!d_syms || !cons || !d_llr || n_sym < 0) return fail(TDEC_EINVAL, "bad demap arguments");
     if (int rc = check_demap_args(M, bps)) return rc;
     if (n_sym == 0) return 0;
@@ -1931,14 +1940,26 @@ int tdec_demap_dev(int device, const void *d_syms, int sym_f64, long n_sym, cons
     DevBuf &tb = cc.buf;
     const DemapCfg c = demap_cfg(M, div_f32, sign, noise_var, cc.sep);
     if (f64) {
-        if (sym_f64) return launch_demap<double, double>(bps, (const double *)d_syms, n_sym, (const double *)tb.p, c, d_llr, st);
-        return launch_demap<double, float>(bps, (const float *)d_syms, n_sym, (const double *)tb.p, c, d_llr, st);
+        if (sym_f64) return launch_demap<double, double>(lm, bps, (const double *)d_syms, n_sym, (const double *)tb.p, c, d_llr, st);
+        return launch_demap<double, float>(lm, bps, (const float *)d_syms, n_sym, (const double *)tb.p, c, d_llr, st);
     }
-    return launch_demap<float, float>(bps, (const float *)d_syms, n_sym, (const float *)tb.p, c, d_llr, st);
+    return launch_demap<float, float>(lm, bps, (const float *)d_syms, n_sym, (const float *)tb.p, c, d_llr, st);
 }
 
-int tdec_demap(int device, const void *syms, int sym_f64, long n_sym, const void *cons, int cons_f64, int M, int bps,
-               double noise_var, int div_f32, int sign, double *llr) {
+int tdec_demap_dev(int device, const void *d_syms, int sym_f64, long n_sym, const void *cons, int cons_f64, int M,
+                   int bps, double noise_var, int div_f32, int sign, double *d_llr, void *stream) {
+    return demap_dev(false, device, d_syms, sym_f64, n_sym, cons, cons_f64, M, bps, noise_var, div_f32, sign, d_llr,
+                     stream);
+}
+
+int tdec_demap_logmap_dev(int device, const void *d_syms, int sym_f64, long n_sym, const void *cons, int cons_f64,
+                          int M, int bps, double noise_var, int sign, double *d_llr, void *stream) {
+    return demap_dev(true, device, d_syms, sym_f64, n_sym, cons, cons_f64, M, bps, noise_var, 0, sign, d_llr, stream);
+}
+
+// The host-pointer forms: symbols up, the device entry on a stream of its own, LLRs down
+static int demap_host(bool lm, int device, const void *syms, int sym_f64, long n_sym, const void *cons, int cons_f64,
+                      int M, int bps, double noise_var, int div_f32, int sign, double *llr) {
     if (!syms || !cons || !llr || n_sym < 0) return fail(TDEC_EINVAL, "bad demap arguments");
     if (int rc = check_demap_args(M, bps)) return rc;
     if (n_sym == 0) return 0;
@@ -1954,14 +1975,24 @@ int tdec_demap(int device, const void *syms, int sym_f64, long n_sym, const void
     HIPCHK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
     int rc = 0;
     if (hipMemcpyAsync(ds, syms, ns, hipMemcpyHostToDevice, st) != hipSuccess) rc = fail(TDEC_EHIP, "memcpy");
-    if (!rc) rc = tdec_demap_dev(device, ds, sym_f64, n_sym, cons, cons_f64, M, bps, noise_var, div_f32, sign,
-                                 (double *)dl, st);
+    if (!rc) rc = demap_dev(lm, device, ds, sym_f64, n_sym, cons, cons_f64, M, bps, noise_var, div_f32, sign,
+                            (double *)dl, st);
     if (!rc && hipMemcpyAsync(llr, dl, nl, hipMemcpyDeviceToHost, st) != hipSuccess) rc = fail(TDEC_EHIP, "memcpy");
     if (!rc && hipStreamSynchronize(st) != hipSuccess) rc = fail(TDEC_EHIP, "demap failed");
     hipStreamDestroy(st);
     hipFree(ds);
     hipFree(dl);
     return rc;
+}
+
+int tdec_demap(int device, const void *syms, int sym_f64, long n_sym, const void *cons, int cons_f64, int M, int bps,
+               double noise_var, int div_f32, int sign, double *llr) {
+    return demap_host(false, device, syms, sym_f64, n_sym, cons, cons_f64, M, bps, noise_var, div_f32, sign, llr);
+}
+
+int tdec_demap_logmap(int device, const void *syms, int sym_f64, long n_sym, const void *cons, int cons_f64, int M,
+                      int bps, double noise_var, int sign, double *llr) {
+    return demap_host(true, device, syms, sym_f64, n_sym, cons, cons_f64, M, bps, noise_var, 0, sign, llr);
 }
 
 int tdec_selftest(int device, int which, long long n, unsigned long long seed, long long *mismatches) {
@@ -2070,6 +2101,42 @@ int tdec_demap_planes_dev(tdec_t *h, int B, const float *d_syms, int S, const vo
         CASE(1) CASE(2) CASE(3) CASE(4) CASE(5) CASE(6) CASE(7) CASE(8)
 #undef CASE
 #undef LAUNCH_PLANES
+    default: return fail(TDEC_EINVAL, "bps must be 1..8");
+    }
+    HIPCHK(hipGetLastError());
+    return mark_used(h, st);
+}
+
+int tdec_demap_planes_logmap_dev(tdec_t *h, int B, const float *d_syms, int S, const void *cons, int cons_f64, int M,
+                                 int bps, double noise_var, float *d_planes, void *stream) {
+    if (!h || B < 0 || !cons) return fail(TDEC_EINVAL, "bad demap arguments");
+    if (int rc = check_demap_args(M, bps)) return rc;
+    if (B == 0) return 0;
+    if (!d_syms || !d_planes || S <= 0) return fail(TDEC_EINVAL, "bad demap arguments");
+    Guard g(h->device);
+    hipStream_t st = (hipStream_t)stream;
+    if (int rc = order_on(h, st)) return rc;   // the table below may still be read on another stream
+    if (int rc = h->cons.upload(cons, cons_f64, M, bps, cons_f64 != 0, st)) return rc;
+    const DemapCfg c = demap_cfg(M, 0, -1, noise_var, h->cons.sep);
+    const double scale = demap_lm_scale(c);
+    const long n_avail = std::min<long>((long)S * bps, h->llr_len);   // LLRs the symbols provide
+    const int chunks = (h->N + dm_kc(bps) - 1) / dm_kc(bps);
+    const long n_items = (long)n_tiles_of(B) * chunks;
+    const dim3 grid((unsigned)n_items);   // one block per item
+    switch (bps) {
+#define CASE(K)                                                                                                     \
+    case K:                                                                                                         \
+        if (cons_f64)                                                                                               \
+            hipLaunchKernelGGL((k_demap_planes_lm<double, K>), grid, dim3(BLOCK), 0, st, B, h->N, S, d_syms,         \
+                               (const double *)h->cons.buf.p, c, scale, (const int *)h->d_src, (const int *)h->d_off, \
+                               n_avail, d_planes, n_items);                                                         \
+        else                                                                                                        \
+            hipLaunchKernelGGL((k_demap_planes_lm<float, K>), grid, dim3(BLOCK), 0, st, B, h->N, S, d_syms,          \
+                               (const float *)h->cons.buf.p, c, scale, (const int *)h->d_src, (const int *)h->d_off,  \
+                               n_avail, d_planes, n_items);                                                         \
+        break;
+        CASE(1) CASE(2) CASE(3) CASE(4) CASE(5) CASE(6) CASE(7) CASE(8)
+#undef CASE
     default: return fail(TDEC_EINVAL, "bps must be 1..8");
     }
     HIPCHK(hipGetLastError());

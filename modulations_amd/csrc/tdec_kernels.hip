@@ -2990,6 +2990,197 @@ __global__ __launch_bounds__(BLOCK) void k_demap_fix(int B, int N, int S, const 
     }
 }
 
+// ---- log-MAP (exact log-sum) soft demapper (build-defined) -------------
+//   d_i = |s - c_i|^2,  L_b,v = log sum_{i : bit_b(i) = v} exp(-d_i / nv),
+//   llr_b = sign * clip(L_b,1 - L_b,0, -30, +30)
+// with the max-log path's nv floor, clip and sign; the max-log demapper is this
+// formula's max-log approximation.  Evaluated in base 2: x_i = d_i * scale with
+// scale = 1 / (nv ln 2) (one host division per launch), every term against the
+// smallest x_i (the largest term is exactly 1, no cut-off), and
+// llr = ln 2 * (log2 S_1 - log2 S_0): the shift cancels.  f32 arithmetic uses
+// v_exp_f32 / v_log_f32 (hw_exp2 / hw_log2, quarter-rate VALU), f64 arithmetic the
+// library's exp2 / log2.  Tolerance-defined (DESIGN.md §9 has the error model and the
+// measured constant), not pinned to numpy: no decline list and no fix-up kernel.
+// A half no point of the table carries, or one whose terms all underflow, gives
+// log2 0 = -inf and so +-30.  NaN or infinite symbols give NaN (inf - inf).
+template <typename T> __device__ __forceinline__ T lm_exp2(T x);
+template <> __device__ __forceinline__ float lm_exp2<float>(float x) { return hw_exp2(x); }
+template <> __device__ __forceinline__ double lm_exp2<double>(double x) { return exp2(x); }
+template <typename T> __device__ __forceinline__ T lm_log2(T x);
+template <> __device__ __forceinline__ float lm_log2<float>(float x) { return hw_log2(x); }
+template <> __device__ __forceinline__ double lm_log2<double>(double x) { return log2(x); }
+template <typename T> __device__ __forceinline__ T lm_min(T a, T b);   // minNum: a NaN operand is dropped
+template <> __device__ __forceinline__ float lm_min<float>(float a, float b) { return __builtin_fminf(a, b); }
+template <> __device__ __forceinline__ double lm_min<double>(double a, double b) { return __builtin_fmin(a, b); }
+
+template <typename T> __device__ __forceinline__ double lm_llr(T s0, T s1, const DemapCfg &c) {
+    T v = (lm_log2<T>(s1) - lm_log2<T>(s0)) * (T)0.693147180559945309417;
+    if (v == v) v = v < (T)-30 ? (T)-30 : (v > (T)30 ? (T)30 : v);
+    return (double)(c.sign < 0 ? -v : v);
+}
+
+// The two sums of every label bit (MSB first) over the 2^K terms e[label]: the
+// halves of e are the leading bit's sums; folding one half onto the other
+// marginalises that bit and leaves the same problem with K - 1 bits
+// (36 additions for K = 4 instead of 56).  e is consumed.
+template <typename T, int K> __device__ __forceinline__ void lm_bit_sums(T (&e)[1 << K], T (&s0)[K], T (&s1)[K]) {
+#pragma unroll
+    for (int b = 0; b < K; ++b) {
+        const int h = 1 << (K - 1 - b);
+        T a0 = e[0], a1 = e[h];
+#pragma unroll
+        for (int j = 1; j < h; ++j) {
+            a0 += e[j];
+            a1 += e[h + j];
+        }
+        s0[b] = a0;
+        s1[b] = a1;
+#pragma unroll
+        for (int j = 0; j < h; ++j) e[j] += e[h + j];
+    }
+}
+
+// Separable square QAM (DemapCfg::sep, point (a, q) = levI[a] + j levQ[q]):
+// exp(-d / nv) = exp(-dI / nv) exp(-dQ / nv), so a sum over a half of the grid that
+// an I bit selects is (sum over that bit's half of the I levels) x (sum over all Q
+// levels), and the second factor cancels in L_b,1 - L_b,0: each axis' K bits need
+// that axis' 2^K exponentials only (256QAM: 32 + 16 logarithms per symbol, against
+// 256 + 16 for the scan).  A non-finite coordinate must reach the other axis'
+// bits too (every d_i is NaN or inf then): it is added to both axes' shifts.
+template <typename T, int BPS>
+__device__ __forceinline__ void lm_sym_sep(T sr, T si, const T *cons, const DemapCfg &c, T scale, double (&out)[BPS]) {
+    constexpr int K = BPS / 2, L = 1 << K;
+    const T *lev = cons + 2 * c.M;
+    const T poison = (sr - sr) + (si - si);   // 0, or NaN for a NaN / infinite symbol
+#pragma unroll
+    for (int ax = 0; ax < 2; ++ax) {
+        const T s = ax ? si : sr;
+        T x[L], e[L], xm = (T)INFINITY;
+#pragma unroll
+        for (int a = 0; a < L; ++a) {
+            const T dz = s - lev[ax * L + a];   // LDS, the same address in every lane: a broadcast read
+            x[a] = dz * dz * scale;
+            xm = lm_min<T>(xm, x[a]);
+        }
+        xm += poison;
+#pragma unroll
+        for (int a = 0; a < L; ++a) e[a] = lm_exp2<T>(xm - x[a]);
+        T s0[K], s1[K];
+        lm_bit_sums<T, K>(e, s0, s1);
+#pragma unroll
+        for (int b = 0; b < K; ++b) out[ax * K + b] = lm_llr<T>(s0[b], s1[b], c);
+    }
+}
+
+// Any other table: two passes over its M points (the smallest x, then the terms),
+// so no distance array is kept; up to 16 points the passes unroll and share the x.
+template <typename T, int BPS, int M = (1 << BPS), int UNROLL = (M <= 16 ? M : 8)>
+__device__ __forceinline__ void lm_sym_scan(T sr, T si, const T *cons, const DemapCfg &c, T scale, double (&out)[BPS]) {
+    auto x_at = [&](int m) -> T {
+        const T dx = sr - cons[2 * m], dy = si - cons[2 * m + 1];
+        return (dx * dx + dy * dy) * scale;
+    };
+    T xm = (T)INFINITY;   // stays inf for a NaN symbol: inf - NaN below
+#pragma unroll UNROLL
+    for (int m = 0; m < M; ++m) {
+        if (M > 2 && m >= c.M) break;
+        xm = lm_min<T>(xm, x_at(m));
+    }
+    T s0[BPS], s1[BPS];
+#pragma unroll
+    for (int b = 0; b < BPS; ++b) s0[b] = s1[b] = (T)0;
+#pragma unroll UNROLL
+    for (int m = 0; m < M; ++m) {
+        if (M > 2 && m >= c.M) break;
+        const T e = lm_exp2<T>(xm - x_at(m));
+#pragma unroll
+        for (int b = 0; b < BPS; ++b) {
+            if ((m >> (BPS - 1 - b)) & 1) s1[b] += e;
+            else s0[b] += e;
+        }
+    }
+#pragma unroll
+    for (int b = 0; b < BPS; ++b) out[b] = lm_llr<T>(s0[b], s1[b], c);
+}
+
+template <typename T, int BPS>
+__device__ __forceinline__ void demap_lm_sym(T sr, T si, const T *cons, const DemapCfg &c, T scale, double (&out)[BPS]) {
+    if constexpr (BPS >= 4 && BPS % 2 == 0) {
+        if (c.sep) return lm_sym_sep<T, BPS>(sr, si, cons, c, scale, out);
+    }
+    lm_sym_scan<T, BPS>(sr, si, cons, c, scale, out);
+}
+
+// k_demap's launch shape: one symbol per thread, f64 LLRs
+template <typename T, typename S, int BPS>
+__global__ __launch_bounds__(BLOCK) void k_demap_lm(const S *syms, long n_sym, const T *cons_g, DemapCfg c, double scale,
+                                                   double *llr) {
+    __shared__ T cons[DM_TAB];
+    load_table<T, BPS>(cons, cons_g, c);
+    __syncthreads();
+    const long s = (long)blockIdx.x * BLOCK + threadIdx.x;
+    if (s >= n_sym) return;
+    double v[BPS];
+    demap_lm_sym<T, BPS>((T)syms[2 * s], (T)syms[2 * s + 1], cons, c, (T)scale, v);
+#pragma unroll
+    for (int b = 0; b < BPS; ++b) llr[s * BPS + b] = v[b];
+}
+
+// k_demap_planes' items, LDS tile and plane layout (its phase 2 verbatim, so
+// tdec_decode_planes_dev consumes these planes unchanged) around demap_lm_sym;
+// no split and no prefetch: the symbol's work is the transcendentals.
+template <typename T, int BPS>
+__global__ __launch_bounds__(BLOCK) void k_demap_planes_lm(int B, int N, int S, const float *syms, const T *cons_g,
+                                                          DemapCfg c, double scale, const int *__restrict__ src,
+                                                          const int *__restrict__ off, long n_avail, float *planes,
+                                                          long n_items) {
+    __shared__ T cons[DM_TAB];
+    constexpr int KC = dm_kc(BPS), LD = 6 * KC + 2 * BPS + 1;
+    __shared__ float L[WAVE * LD];
+    load_table<T, BPS>(cons, cons_g, c);
+    const int chunks = (N + KC - 1) / KC;
+    const T sc = (T)scale;
+    __syncthreads();
+    for (long item = blockIdx.x; item < n_items; item += gridDim.x) {
+        const long tile = item / chunks;
+        const int k0 = (int)(item % chunks) * KC;
+        const int k1 = min(N, k0 + KC);
+        const long j0 = off[k0], j1 = off[k1];
+        const long s0 = j0 / BPS, s1 = (j1 + BPS - 1) / BPS;        // symbols covering [j0, j1)
+        const int ns = (int)(s1 - s0);
+        for (int t = threadIdx.x; t < WAVE * ns; t += BLOCK) {      // consecutive threads: consecutive symbols
+            const int ln = t / ns, sx = t - ln * ns;
+            const long cw = tile * WAVE + ln, s = s0 + sx;
+            if (cw >= B || s >= S) continue;
+            const float2 z = *reinterpret_cast<const float2 *>(syms + 2 * (cw * S + s));
+            double v[BPS];
+            demap_lm_sym<T, BPS>((T)z.x, (T)z.y, cons, c, sc, v);
+#pragma unroll
+            for (int b = 0; b < BPS; ++b) L[ln * LD + b * ns + sx] = (float)v[b];
+        }
+        float *base = planes + tile * tile_floats(N);
+        __syncthreads();
+        for (int t = threadIdx.x; t < WAVE * (k1 - k0) * 2; t += BLOCK) {
+            const int lane = t & (WAVE - 1);
+            const int q = __builtin_amdgcn_readfirstlane(t >> 6);   // (step, half): wave-uniform
+            const int k = k0 + q / 2, half = q & 1;
+            const long cw = tile * WAVE + lane;
+            const int nc = half ? 2 : 4;
+            float v[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll
+            for (int cc = 0; cc < 4; ++cc) {
+                if (cc >= nc) break;
+                const int j = src[(long)(half ? 6 + cc : cc) * N + k];
+                const int col = j >= 0 ? (j % BPS) * ns + (int)(j / BPS - s0) : 0;
+                v[cc] = (j >= 0 && j < n_avail && cw < B) ? L[lane * LD + col] : 0.0f;
+            }
+            if (half == 0) reinterpret_cast<float4 *>(base)[(long)k * WAVE + lane] = make_float4(v[0], v[1], v[2], v[3]);
+            else reinterpret_cast<float2 *>(base + (long)N * WAVE * 4)[(long)k * WAVE + lane] = make_float2(v[0], v[1]);
+        }
+        __syncthreads();   // L is rewritten by the next item: its reads done everywhere
+    }
+}
+
 // ---- fused demap + decode ------------------------------------------------------------
 // Each persistent decoder wave demaps its next 64-codeword tile itself (the same
 // operations as k_demap_planes, so the planes are bit-identical) into a plane

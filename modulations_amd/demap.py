@@ -9,6 +9,11 @@ rules: the arithmetic is complex128 when the symbols or the constellation are
 (QPSK's constellation is, because qpsk_mod divides by np.sqrt(2)), and the
 final division stays float32 when noise_var ends up a Python float.
 ``sign=-1`` gives the decoder convention (positive for bit 0).
+
+``algo="log-map"`` selects the exact log-sum demapper (build-defined, DESIGN.md
+section 9), of which the reference's is the max-log approximation: the same
+noise-variance floor, clip, sign and dtype rule, defined by a tolerance instead
+of numpy's operation order.
 """
 from __future__ import annotations
 
@@ -109,8 +114,19 @@ def demap_mode(syms_dtype, cons_dtype, noise_var):
     return f64, div_f32, float(nv)
 
 
-def compute_llr(syms, mod_type, noise_var, sign=+1, device=0):
-    """Max-log soft demapper (reference test_sdr_with_coding.py:200-225) on the GPU."""
+ALGOS = ("max-log", "log-map")
+
+
+def check_algo(algo):
+    if algo not in ALGOS:
+        raise ValueError(f"demapper algo must be one of {ALGOS}, not {algo!r}")
+    return algo == "log-map"
+
+
+def compute_llr(syms, mod_type, noise_var, sign=+1, device=0, algo="max-log"):
+    """Soft demapper on the GPU: max-log (reference test_sdr_with_coding.py:200-225)
+    or, with algo="log-map", the exact log-sum it approximates."""
+    lm = check_algo(algo)
     m = MODULATIONS[mod_type]
     cons = _cons(mod_type)
     syms = np.asarray(syms)
@@ -120,17 +136,21 @@ def compute_llr(syms, mod_type, noise_var, sign=+1, device=0):
     f64, div_f32, nv = demap_mode(syms.dtype, cons.dtype, noise_var)
     c = np.ascontiguousarray(cons.astype(np.complex128 if f64 else np.complex64))
     out = np.zeros(len(syms) * m['bps'])
-    if len(syms):
+    if len(syms) and lm:
+        _n.check(_n.lib().tdec_demap_logmap(device, _n.ptr(syms), int(syms.dtype == np.complex128), len(syms),
+                                            _n.ptr(c), int(f64), len(c), m['bps'], nv, int(sign), _n.ptr(out)))
+    elif len(syms):
         _n.check(_n.lib().tdec_demap(device, _n.ptr(syms), int(syms.dtype == np.complex128), len(syms),
                                      _n.ptr(c), int(f64), len(c), m['bps'], nv, int(div_f32), int(sign),
                                      _n.ptr(out)))
     return out
 
 
-def compute_llr_device(syms, mod_type, noise_var, out=None, sign=+1, stream=None):
+def compute_llr_device(syms, mod_type, noise_var, out=None, sign=+1, stream=None, algo="max-log"):
     """compute_llr over a device tensor of complex symbols (complex64/complex128 or
     a float [..., 2] view); returns a float64 device tensor."""
     import torch
+    lm = check_algo(algo)
     m = MODULATIONS[mod_type]
     cons = _cons(mod_type)
     sym_f64 = syms.dtype in (torch.complex128, torch.float64)
@@ -147,6 +167,10 @@ def compute_llr_device(syms, mod_type, noise_var, out=None, sign=+1, stream=None
     if out.dtype != torch.float64 or not out.is_contiguous() or out.numel() < n_sym * m['bps'] or out.device != syms.device:
         raise ValueError("out must be a contiguous float64 tensor of n_sym*bps elements on the symbols' device")
     st = _n.stream_ptr(stream) if stream is not None else torch.cuda.current_stream(dev).cuda_stream
-    _n.check(_n.lib().tdec_demap_dev(dev, _n.ptr(syms), int(sym_f64), n_sym, _n.ptr(c), int(f64),
-                                     len(c), m['bps'], nv, int(div_f32), int(sign), _n.ptr(out), st))
+    if lm:
+        _n.check(_n.lib().tdec_demap_logmap_dev(dev, _n.ptr(syms), int(sym_f64), n_sym, _n.ptr(c), int(f64),
+                                                len(c), m['bps'], nv, int(sign), _n.ptr(out), st))
+    else:
+        _n.check(_n.lib().tdec_demap_dev(dev, _n.ptr(syms), int(sym_f64), n_sym, _n.ptr(c), int(f64),
+                                         len(c), m['bps'], nv, int(div_f32), int(sign), _n.ptr(out), st))
     return out

@@ -412,8 +412,12 @@ class DVBRCS2_Turbo:
         throughput decode has handed out its last tiles (tdec_tail_gate)."""
         self.handle.call("tdec_tail_gate", self._stream(stream))
 
-    def demap_planes_device(self, syms, constellation, bps, noise_var, planes, div_f32=False, stream=None):
-        """Fused soft demap (decoder sign) + de-puncture of complex64 symbols [B, S]."""
+    def demap_planes_device(self, syms, constellation, bps, noise_var, planes, div_f32=False, stream=None,
+                            algo="max-log"):
+        """Fused soft demap (decoder sign) + de-puncture of complex64 symbols [B, S];
+        algo="log-map": the exact log-sum demapper (div_f32 has no meaning there)."""
+        from .demap import check_algo
+        lm = check_algo(algo)
         cons = np.ascontiguousarray(np.asarray(constellation))
         f64 = cons.dtype == np.complex128
         cons = cons.astype(np.complex128 if f64 else np.complex64)
@@ -423,6 +427,10 @@ class DVBRCS2_Turbo:
         B, S = syms.shape[0], syms.shape[1]
         if planes.numel() * 4 < self.planes_bytes(B):
             raise ValueError("planes buffer smaller than planes_bytes(B)")
+        if lm:
+            self.handle.call("tdec_demap_planes_logmap_dev", B, _n.ptr(syms), S, _n.ptr(cons), int(f64), len(cons),
+                             bps, float(noise_var), _n.ptr(planes), self._stream(stream))
+            return planes
         self.handle.call("tdec_demap_planes_dev", B, _n.ptr(syms), S, _n.ptr(cons), int(f64), len(cons), bps,
                          float(noise_var), int(div_f32), _n.ptr(planes), self._stream(stream))
         return planes

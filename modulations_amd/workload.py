@@ -85,15 +85,22 @@ class DevicePipeline:
     decoder, or with es_decoder="tile" / "refill" through the early-stop tile
     decoders (two launches, never fused; the codec's reserve() sizes what its
     decoder needs); the iterations each codeword of the last batch ran
-    are in `n_iter` (int32 [B] on the device, first rows)."""
+    are in `n_iter` (int32 [B] on the device, first rows).
 
-    def __init__(self, codec, mod, B, device, fused=False, overlap=False, gate=True):
+    demap="log-map" demaps with the exact log-sum demapper
+    (tdec_demap_planes_logmap_dev) in front of either decoder algorithm; there
+    is no fused kernel for it, so fused=True runs the two launches."""
+
+    def __init__(self, codec, mod, B, device, fused=False, overlap=False, gate=True, demap="max-log"):
         import torch
         self.codec, self.mod, self.B = codec, mod, B
         self.bps = D.MODULATIONS[mod]["bps"]
         self.cons = D.constellation(mod)
+        self.demap = demap
+        lm = D.check_algo(demap)
         self.early_stop = bool(getattr(codec, "early_stop", False))
-        self.fused = bool(fused) and not self.early_stop and codec.fused_available(self.cons, self.bps)
+        self.fused = (bool(fused) and not lm and not self.early_stop
+                      and codec.fused_available(self.cons, self.bps))
         self.overlap = bool(overlap) and not self.fused
         if self.fused:
             codec.reserve_fused(B)
@@ -144,7 +151,7 @@ class DevicePipeline:
             if self.gate:
                 self.codec.tail_gate(sd)                # batch i-1's decode is in its tail
             self.demapper.demap_planes_device(syms, self.cons, self.bps, nve, self.planes_db[b], div_f32=div32,
-                                              stream=sd)
+                                              stream=sd, algo=self.demap)
             self.demap_done[b].record(sd)
             sk.wait_stream(stream)                      # earlier readers of bits on the caller's stream
             sk.wait_event(self.demap_done[b])
@@ -163,7 +170,7 @@ class DevicePipeline:
             self.codec.demap_decode_device(syms, self.cons, self.bps, nve, bits, div_f32=div32, stream=stream)
         else:
             self.codec.demap_planes_device(syms, self.cons, self.bps, nve, self.planes, div_f32=div32,
-                                           stream=stream)
+                                           stream=stream, algo=self.demap)
             if events is not None:
                 events[0].record(stream)
             self.codec.decode_planes_device(self.planes, syms.shape[0], bits, stream=stream, **es)
