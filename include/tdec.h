@@ -259,6 +259,45 @@ int tdec_demap_planes_dev(tdec_t *h, int B, const float *d_syms, int S, const vo
 int tdec_demap_planes_logmap_dev(tdec_t *h, int B, const float *d_syms, int S, const void *cons, int cons_f64,
                                  int M, int bps, double noise_var, float *d_planes, void *stream);
 
+/* Per-row noise variance: a receiver estimates each burst's noise
+ * variance from that burst's own symbols (test_sdr_with_coding.py:459-471), so a
+ * batch of B bursts has B values.  These calls keep them in device memory, one
+ * f64 per row of the [B][S] symbols, so estimate -> demap -> decode is queued on
+ * one stream with no host round trip.
+ *
+ * tdec_noise_var_dev: the decision-directed estimate of :459-467 for each row of
+ * complex64 symbols (build-defined: the f64 mean, where numpy's is an f32
+ * pairwise mean):
+ *   d_nv[r] = max_py(mean_s min_m |s - c_m|^2, floor),  max_py(a, b) = (b > a) ? b : a
+ * (Python's max(nv, 0.02): a NaN mean stays NaN; a NaN or infinite symbol makes
+ * its row's value NaN).  The minimum is taken over dx*dx + dy*dy of the f64
+ * differences; a row's value does not depend on B.
+ *
+ * tdec_demap_rows_dev / _logmap_dev: tdec_demap_dev / tdec_demap_logmap_dev
+ * over B rows of S symbols, row r with noise_var = d_noise_var[r] (floored at
+ * 0.005 on the device as the scalar calls floor it on the host); d_llr is
+ * f64[B][S * bps].  tdec_demap_planes_nv_dev / _logmap_nv_dev: the same for
+ * tdec_demap_planes_dev / tdec_demap_planes_logmap_dev (same ordering on the
+ * handle, table upload and decline list; after tdec_reserve they neither
+ * allocate nor synchronise).  Row r of each is, bit for bit, row r of the scalar
+ * call given noise_var = d_noise_var[r]; a NaN value gives that row NaN LLRs.
+ * Conventions as the scalar calls: B = 0 is a no-op, null or negative arguments
+ * are TDEC_EINVAL.  The handle-less calls share tdec_demap_dev's table cache.
+ * There is no per-row form of the one-launch tdec_demap_decode_dev below: it
+ * measured slower than the two launches and is not the default. */
+int tdec_noise_var_dev(int device, const float *d_syms, int B, int S, const void *cons, int cons_f64, int M,
+                       double floor, double *d_nv, void *stream);
+int tdec_demap_rows_dev(int device, const void *d_syms, int sym_f64, int B, int S, const void *cons, int cons_f64,
+                        int M, int bps, const double *d_noise_var, int div_f32, int sign, double *d_llr,
+                        void *stream);
+int tdec_demap_rows_logmap_dev(int device, const void *d_syms, int sym_f64, int B, int S, const void *cons,
+                               int cons_f64, int M, int bps, const double *d_noise_var, int sign, double *d_llr,
+                               void *stream);
+int tdec_demap_planes_nv_dev(tdec_t *h, int B, const float *d_syms, int S, const void *cons, int cons_f64, int M,
+                             int bps, const double *d_noise_var, int div_f32, float *d_planes, void *stream);
+int tdec_demap_planes_logmap_nv_dev(tdec_t *h, int B, const float *d_syms, int S, const void *cons, int cons_f64,
+                                    int M, int bps, const double *d_noise_var, float *d_planes, void *stream);
+
 /* Fused soft demap + turbo decode (one launch): what tdec_demap_planes_dev +
  * tdec_decode_planes_dev compute, bit for bit, with each persistent decoder wave
  * demapping its own next tile into a per-wave plane buffer.  Instantiated for

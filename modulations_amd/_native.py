@@ -37,6 +37,8 @@ EXPORTS = (
     "tdec_reserve_es_refill", "tdec_decode_batch_es_refill", "tdec_decode_planes_es_refill_dev",
     "tdec_decode_batch_es_refill_dev", "tdec_es_refill_stats",
     "tdec_demap_logmap_dev", "tdec_demap_logmap", "tdec_demap_planes_logmap_dev",
+    "tdec_noise_var_dev", "tdec_demap_rows_dev", "tdec_demap_rows_logmap_dev", "tdec_demap_planes_nv_dev",
+    "tdec_demap_planes_logmap_nv_dev",
 )
 
 _lib = None
@@ -114,6 +116,19 @@ def _declare(L):
         L.tdec_demap_planes_logmap_dev.argtypes = [_vp, C.c_int, _vp, C.c_int, _vp, C.c_int, C.c_int, C.c_int,
                                                    C.c_double, _vp, _vp]
         for f in (L.tdec_demap_logmap_dev, L.tdec_demap_logmap, L.tdec_demap_planes_logmap_dev):
+            f.restype = C.c_int
+    if hasattr(L, "tdec_noise_var_dev"):   # (A/B tools also load older builds without the per-row noise variance)
+        L.tdec_noise_var_dev.argtypes = [C.c_int, _vp, C.c_int, C.c_int, _vp, C.c_int, C.c_int, C.c_double, _vp, _vp]
+        L.tdec_demap_rows_dev.argtypes = [C.c_int, _vp, C.c_int, C.c_int, C.c_int, _vp, C.c_int, C.c_int, C.c_int,
+                                          _vp, C.c_int, C.c_int, _vp, _vp]
+        L.tdec_demap_rows_logmap_dev.argtypes = [C.c_int, _vp, C.c_int, C.c_int, C.c_int, _vp, C.c_int, C.c_int,
+                                                 C.c_int, _vp, C.c_int, _vp, _vp]
+        L.tdec_demap_planes_nv_dev.argtypes = [_vp, C.c_int, _vp, C.c_int, _vp, C.c_int, C.c_int, C.c_int, _vp,
+                                               C.c_int, _vp, _vp]
+        L.tdec_demap_planes_logmap_nv_dev.argtypes = [_vp, C.c_int, _vp, C.c_int, _vp, C.c_int, C.c_int, C.c_int,
+                                                      _vp, _vp, _vp]
+        for f in (L.tdec_noise_var_dev, L.tdec_demap_rows_dev, L.tdec_demap_rows_logmap_dev,
+                  L.tdec_demap_planes_nv_dev, L.tdec_demap_planes_logmap_nv_dev):
             f.restype = C.c_int
     L.tdec_encode_dev.argtypes = [_vp, C.c_int, _vp, _vp, _vp]
     L.tdec_demap_batch.argtypes = [C.c_int, C.c_int, C.c_int, _vp, C.c_long, C.c_float, _vp]

@@ -1905,15 +1905,9 @@ int tdec_siso_batch_f64(tdec_t *h, int B, const double *LcA, const double *LcB, 
     return siso_batch_impl<double>(h, B, LcA, LcB, LcW, LcY, LaA, LaB, sf, LeA, LeB);
 }
 
-// The flat demappers' entry (lm: the log-MAP kernels; div_f32 is the max-log path's alone)
-static int demap_dev(bool lm, int device, const void *d_syms, int sym_f64, long n_sym, const void *cons, int cons_f64,
-                     int M, int bps, double noise_var, int div_f32, int sign, double *d_llr, void *stream) {
-    if (!d_syms || !cons || !d_llr || n_sym < 0) return fail(TDEC_EINVAL, "bad demap arguments");
-    if (int rc = check_demap_args(M, bps)) return rc;
-    if (n_sym == 0) return 0;
-    Guard g(device);
-    const bool f64 = sym_f64 || cons_f64;
-    hipStream_t st = (hipStream_t)stream;
+// The handle-less calls' device table (the caller holds the device's Guard)
+static int cached_table(int device, const void *cons, int cons_f64, int M, int bps, bool f64, hipStream_t st,
+                        ConsCache **out) {
     // Tables are cached per (thread, device) by content and never overwritten
     // while another stream may still read them: a new table takes a fresh slot;
     // only when all slots are taken is the oldest reused, after a device-wide
@@ -1935,8 +1929,22 @@ static int demap_dev(bool lm, int device, const void *d_syms, int sym_f64, long 
             hit = &v[next_victim[device & 15]++ % SLOTS];
         }
     }
+    *out = hit;
+    return hit->upload(cons, cons_f64, M, bps, f64, st);
+}
+
+// The flat demappers' entry (lm: the log-MAP kernels; div_f32 is the max-log path's alone)
+static int demap_dev(bool lm, int device, const void *d_syms, int sym_f64, long n_sym, const void *cons, int cons_f64,
+                     int M, int bps, double noise_var, int div_f32, int sign, double *d_llr, void *stream) {
+    if (!d_syms || !cons || !d_llr || n_sym < 0) return fail(TDEC_EINVAL, "bad demap arguments");
+    if (int rc = check_demap_args(M, bps)) return rc;
+    if (n_sym == 0) return 0;
+    Guard g(device);
+    const bool f64 = sym_f64 || cons_f64;
+    hipStream_t st = (hipStream_t)stream;
+    ConsCache *hit = nullptr;
+    if (int rc = cached_table(device, cons, cons_f64, M, bps, f64, st, &hit)) return rc;
     ConsCache &cc = *hit;
-    if (int rc = cc.upload(cons, cons_f64, M, bps, f64, st)) return rc;
     DevBuf &tb = cc.buf;
     const DemapCfg c = demap_cfg(M, div_f32, sign, noise_var, cc.sep);
     if (f64) {
@@ -2392,3 +2400,178 @@ const void *decode_refill_kernel(int algo, bool ragged) {
     return ragged ? (const void *)k_turbo_decode_refill<true> : (const void *)k_turbo_decode_refill<false>;
 }
 }  // namespace
+
+// ---- per-row noise variance ---------------------------------------------
+// Behind the refill kernels for the same reason: the ROWNV instantiations and
+// k_noise_var are first named here, so they follow every older kernel in the code object.
+namespace {
+template <typename T, typename S>
+int launch_demap_rows(bool lm, int bps, const S *d_syms, long n_sym, const T *d_cons, DemapCfg c, RowNv<true> rn,
+                      double *d_llr, hipStream_t st) {
+    const dim3 grid((unsigned)((n_sym + BLOCK - 1) / BLOCK));
+    switch (bps) {
+#define CASE(K)                                                                                                      \
+    case K:                                                                                                          \
+        if (lm) hipLaunchKernelGGL((k_demap_lm<T, S, K, true>), grid, dim3(BLOCK), 0, st, d_syms, n_sym, d_cons, c,  \
+                                   0.0, d_llr, rn);                                                                  \
+        else hipLaunchKernelGGL((k_demap<T, S, K, true>), grid, dim3(BLOCK), 0, st, d_syms, n_sym, d_cons, c, d_llr, \
+                                rn);                                                                                 \
+        break;
+        CASE(1) CASE(2) CASE(3) CASE(4) CASE(5) CASE(6) CASE(7) CASE(8)
+#undef CASE
+    default: return fail(TDEC_EINVAL, "bps must be 1..8");
+    }
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+// tdec_demap_dev / tdec_demap_logmap_dev over [B][S] symbols with noise_var[row] (c.nv is the kernels' to fill)
+int demap_rows_dev(bool lm, int device, const void *d_syms, int sym_f64, int B, int S, const void *cons, int cons_f64,
+                   int M, int bps, const double *d_nv, int div_f32, int sign, double *d_llr, void *stream) {
+    if (!d_syms || !cons || !d_llr || !d_nv || B < 0 || S < 0) return fail(TDEC_EINVAL, "bad demap arguments");
+    if (int rc = check_demap_args(M, bps)) return rc;
+    if (B == 0 || S == 0) return 0;
+    Guard g(device);
+    const bool f64 = sym_f64 || cons_f64;
+    hipStream_t st = (hipStream_t)stream;
+    ConsCache *cc = nullptr;
+    if (int rc = cached_table(device, cons, cons_f64, M, bps, f64, st, &cc)) return rc;
+    const DemapCfg c = demap_cfg(M, div_f32, sign, 0.0, cc->sep);
+    const RowNv<true> rn{d_nv, S};
+    const long n_sym = (long)B * S;
+    if (f64) {
+        if (sym_f64)
+            return launch_demap_rows<double, double>(lm, bps, (const double *)d_syms, n_sym, (const double *)cc->buf.p, c, rn, d_llr, st);
+        return launch_demap_rows<double, float>(lm, bps, (const float *)d_syms, n_sym, (const double *)cc->buf.p, c, rn, d_llr, st);
+    }
+    return launch_demap_rows<float, float>(lm, bps, (const float *)d_syms, n_sym, (const float *)cc->buf.p, c, rn, d_llr, st);
+}
+
+struct PlanesNv {
+    tdec_t *h;
+    int B, S;
+    const float *d_syms;
+    DemapCfg c;
+    long n_avail, n_items, n_tiles;
+    float *P;
+    DemapDecl dd;
+    RowNv<true> rn;
+    hipStream_t st;
+    bool split, lm;
+};
+
+template <typename TT, int K> void launch_planes_nv(const PlanesNv &a) {
+    tdec_t *h = a.h;
+    const dim3 grid((unsigned)a.n_items);   // one block per item
+    const dim3 fgrid((unsigned)std::max<long>(1, std::min<long>(a.n_tiles, 1024)));
+    const TT *tab = (const TT *)h->cons.buf.p;
+    if (a.lm) {
+        hipLaunchKernelGGL((k_demap_planes_lm<TT, K, true>), grid, dim3(BLOCK), 0, a.st, a.B, h->N, a.S, a.d_syms, tab, a.c,
+                           0.0, (const int *)h->d_src, (const int *)h->d_off, a.n_avail, a.P, a.n_items, a.rn);
+        return;
+    }
+    if constexpr (dm_split(K)) {
+        if (a.split) {
+            hipLaunchKernelGGL((k_demap_planes<TT, K, true, true>), grid, dim3(BLOCK), 0, a.st, a.B, h->N, a.S, a.d_syms,
+                               tab, a.c, (const int *)h->d_src, (const int *)h->d_off, a.n_avail, a.P, a.n_items, a.dd,
+                               a.rn);
+            hipLaunchKernelGGL((k_demap_fix<TT, K, true>), fgrid, dim3(BLOCK), 0, a.st, a.B, h->N, a.S, a.d_syms, tab, a.c,
+                               (const int *)h->d_dst, a.n_avail, a.P, a.dd, a.n_tiles, a.rn);
+            return;
+        }
+    }
+    hipLaunchKernelGGL((k_demap_planes<TT, K, false, true>), grid, dim3(BLOCK), 0, a.st, a.B, h->N, a.S, a.d_syms, tab, a.c,
+                       (const int *)h->d_src, (const int *)h->d_off, a.n_avail, a.P, a.n_items, a.dd, a.rn);
+}
+
+// tdec_demap_planes_dev / tdec_demap_planes_logmap_dev with noise_var[row]: the same
+// ordering, table upload, decline-list sizing and capture rule
+int demap_planes_nv(bool lm, tdec_t *h, int B, const float *d_syms, int S, const void *cons, int cons_f64, int M, int bps,
+                    const double *d_nv, int div_f32, float *d_planes, void *stream) {
+    if (!h || B < 0 || !cons) return fail(TDEC_EINVAL, "bad demap arguments");
+    if (int rc = check_demap_args(M, bps)) return rc;
+    if (B == 0) return 0;
+    if (!d_syms || !d_planes || !d_nv || S <= 0) return fail(TDEC_EINVAL, "bad demap arguments");
+    Guard g(h->device);
+    hipStream_t st = (hipStream_t)stream;
+    if (int rc = order_on(h, st)) return rc;   // the table below may still be read on another stream
+    if (int rc = h->cons.upload(cons, cons_f64, M, bps, cons_f64 != 0, st)) return rc;
+    const int chunks = (h->N + dm_kc(bps) - 1) / dm_kc(bps);
+    PlanesNv a{h, B, S, d_syms, demap_cfg(M, lm ? 0 : div_f32, -1, 0.0, h->cons.sep),
+               std::min<long>((long)S * bps, h->llr_len), (long)n_tiles_of(B) * chunks, n_tiles_of(B), d_planes,
+               DemapDecl{h->d_decl, h->d_decl_n, h->d_decl_ovf, DM_DECL_CAP}, RowNv<true>{d_nv, S}, st,
+               !lm && dm_split_table(bps, h->cons.sep), lm};
+    if (a.split) {   // the decline list: sized by tdec_reserve
+        if (h->decl_tiles < a.n_tiles) {
+            if (capturing(st)) return fail(TDEC_ECAPACITY, "demap batch larger than tdec_reserve() (stream capture)");
+            quiesce(h);
+            if (int rc = ensure_decl(h, a.n_tiles)) return rc;
+        }
+        a.dd = DemapDecl{h->d_decl, h->d_decl_n, h->d_decl_ovf, DM_DECL_CAP};
+        HIPCHK(hipMemsetAsync(h->d_decl_n, 0, sizeof(unsigned), st));
+        HIPCHK(hipMemsetAsync(h->d_decl_ovf, 0, (size_t)a.n_tiles, st));
+    }
+    switch (bps) {
+#define CASE(K)                                    \
+    case K:                                        \
+        if (cons_f64) launch_planes_nv<double, K>(a); \
+        else launch_planes_nv<float, K>(a);        \
+        break;
+        CASE(1) CASE(2) CASE(3) CASE(4) CASE(5) CASE(6) CASE(7) CASE(8)
+#undef CASE
+    default: return fail(TDEC_EINVAL, "bps must be 1..8");
+    }
+    HIPCHK(hipGetLastError());
+    return mark_used(h, st);
+}
+}  // namespace
+
+extern "C" {
+
+int tdec_noise_var_dev(int device, const float *d_syms, int B, int S, const void *cons, int cons_f64, int M,
+                       double floor, double *d_nv, void *stream) {
+    if (B < 0 || !cons) return fail(TDEC_EINVAL, "bad noise_var arguments");
+    int bps = 1;
+    while (bps < 8 && (1 << bps) < M) ++bps;
+    if (int rc = check_demap_args(M, bps)) return rc;
+    if (B == 0) return 0;
+    if (!d_syms || !d_nv || S <= 0) return fail(TDEC_EINVAL, "bad noise_var arguments");
+    Guard g(device);
+    hipStream_t st = (hipStream_t)stream;
+    ConsCache *cc = nullptr;
+    if (int rc = cached_table(device, cons, cons_f64, M, bps, cons_f64 != 0, st, &cc)) return rc;
+    if (cons_f64)
+        hipLaunchKernelGGL(k_noise_var<double>, dim3((unsigned)B), dim3(BLOCK), 0, st, d_syms, S,
+                           (const double *)cc->buf.p, M, floor, d_nv);
+    else
+        hipLaunchKernelGGL(k_noise_var<float>, dim3((unsigned)B), dim3(BLOCK), 0, st, d_syms, S,
+                           (const float *)cc->buf.p, M, floor, d_nv);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+int tdec_demap_rows_dev(int device, const void *d_syms, int sym_f64, int B, int S, const void *cons, int cons_f64,
+                        int M, int bps, const double *d_noise_var, int div_f32, int sign, double *d_llr,
+                        void *stream) {
+    return demap_rows_dev(false, device, d_syms, sym_f64, B, S, cons, cons_f64, M, bps, d_noise_var, div_f32, sign,
+                          d_llr, stream);
+}
+
+int tdec_demap_rows_logmap_dev(int device, const void *d_syms, int sym_f64, int B, int S, const void *cons,
+                               int cons_f64, int M, int bps, const double *d_noise_var, int sign, double *d_llr,
+                               void *stream) {
+    return demap_rows_dev(true, device, d_syms, sym_f64, B, S, cons, cons_f64, M, bps, d_noise_var, 0, sign, d_llr,
+                          stream);
+}
+
+int tdec_demap_planes_nv_dev(tdec_t *h, int B, const float *d_syms, int S, const void *cons, int cons_f64, int M,
+                             int bps, const double *d_noise_var, int div_f32, float *d_planes, void *stream) {
+    return demap_planes_nv(false, h, B, d_syms, S, cons, cons_f64, M, bps, d_noise_var, div_f32, d_planes, stream);
+}
+
+int tdec_demap_planes_logmap_nv_dev(tdec_t *h, int B, const float *d_syms, int S, const void *cons, int cons_f64,
+                                    int M, int bps, const double *d_noise_var, float *d_planes, void *stream) {
+    return demap_planes_nv(true, h, B, d_syms, S, cons, cons_f64, M, bps, d_noise_var, 0, d_planes, stream);
+}
+
+}  // extern "C"

@@ -2058,6 +2058,23 @@ struct DemapCfg {
     int nv_fast;               // nv in [2^-8, 2^16]: the unscaled f32 / f64 division (dm_fast)
 };
 __host__ __device__ inline int dm_nv_fast(double nv) { return nv >= 0x1p-8 && nv <= 0x1p16; }
+// Per-row noise variance (ROWNV): the demap kernels' last argument.
+// Empty for the scalar kernels, whose DemapCfg carries the launch's one value; with
+// ROWNV a device vector, one value per row of [B][S] symbols, from which each thread
+// forms its symbol's configuration with the host's own expressions (demap_cfg /
+// demap_lm_scale, tdec_api.hip), so row r is row r of the scalar launch with nvs[r].
+template <bool ROWNV> struct RowNv {};
+template <> struct RowNv<true> {
+    const double *nvs;         // device, [B]
+    long S;                    // symbols per row (the flat kernels' row = symbol / S)
+};
+__device__ __forceinline__ DemapCfg row_cfg(const DemapCfg &c, double x) {
+    DemapCfg r = c;
+    r.nv = (0.005 > x) ? 0.005 : x;   // a NaN x stays NaN, as on the host
+    r.nv_fast = dm_nv_fast(r.nv);
+    return r;
+}
+__device__ __forceinline__ double row_lm_scale(const DemapCfg &c) { return 1.0 / (c.nv * 0.693147180559945309417); }
 // LDS table: 2*M point coordinates (+ 2 * 2^(bps/2) axis levels in label order; for a
 // uniform grid labelled through gray[], sep == 2, + the levels in position order, 4
 // parameters and the 2 * K * 2^K neighbour positions of sym_llrs_gray)
@@ -2689,15 +2706,20 @@ template <typename T, int BPS> __device__ __forceinline__ void load_table(T *con
     for (int i = threadIdx.x; i < n; i += BLOCK) cons[i] = cons_g[i];
 }
 
-template <typename T, typename S, int BPS>
-__global__ __launch_bounds__(BLOCK) void k_demap(const S *syms, long n_sym, const T *cons_g, DemapCfg c, double *llr) {
+template <typename T, typename S, int BPS, bool ROWNV = false>
+__global__ __launch_bounds__(BLOCK) void k_demap(const S *syms, long n_sym, const T *cons_g, DemapCfg c, double *llr,
+                                                RowNv<ROWNV> rn = {}) {
     __shared__ T cons[DM_TAB];
     load_table<T, BPS>(cons, cons_g, c);
     __syncthreads();
     const long s = (long)blockIdx.x * BLOCK + threadIdx.x;
     if (s >= n_sym) return;
     double v[BPS];
-    demap_sym<T, BPS>((T)syms[2 * s], (T)syms[2 * s + 1], cons, c, v);
+    if constexpr (ROWNV) {
+        demap_sym<T, BPS>((T)syms[2 * s], (T)syms[2 * s + 1], cons, row_cfg(c, rn.nvs[s / rn.S]), v);
+    } else {
+        demap_sym<T, BPS>((T)syms[2 * s], (T)syms[2 * s + 1], cons, c, v);
+    }
 #pragma unroll
     for (int b = 0; b < BPS; ++b) llr[s * BPS + b] = v[b];
 }
@@ -2844,11 +2866,36 @@ __device__ __forceinline__ bool demap_fast(T sr, T si, const T *cons, const Dema
     else return c.sep && sym_llrs_sep<T, BPS, F32OUT>(sr, si, cons, c, out);
 }
 
-template <typename T, int BPS, bool SPLIT = false>
+// ROWNV: neighbouring threads of an item belong to different rows of the tile, so
+// each symbol's configuration comes from its row's value (row_nv: the tile's 64
+// values staged in LDS once per item, or one load per symbol; DESIGN.md §10 has both
+// measured).
+#ifndef DM_ROWNV_LDS
+#define DM_ROWNV_LDS 0
+#endif
+__device__ __forceinline__ double *row_nv_tile() {
+    __shared__ double nvl[WAVE];
+    return nvl;
+}
+// stage the tile's values (before the item's first symbol; the item's closing barrier
+// orders the next item's staging after this item's reads)
+__device__ __forceinline__ void row_nv_stage(const RowNv<true> &rn, long tile, int B) {
+    if constexpr (DM_ROWNV_LDS) {
+        const long cw = tile * WAVE + threadIdx.x;
+        if (threadIdx.x < WAVE) row_nv_tile()[threadIdx.x] = cw < B ? rn.nvs[cw] : 0.0;
+        __syncthreads();
+    }
+}
+__device__ __forceinline__ double row_nv(const RowNv<true> &rn, int ln, long cw) {   // cw < B
+    if constexpr (DM_ROWNV_LDS) return row_nv_tile()[ln];
+    else return rn.nvs[cw];
+}
+
+template <typename T, int BPS, bool SPLIT = false, bool ROWNV = false>
 __global__ __launch_bounds__(BLOCK) void k_demap_planes(int B, int N, int S, const float *syms, const T *cons_g,
                                                        DemapCfg c, const int *__restrict__ src,
                                                        const int *__restrict__ off, long n_avail, float *planes,
-                                                       long n_items, DemapDecl dd) {
+                                                       long n_items, DemapDecl dd, RowNv<ROWNV> rn = {}) {
     __shared__ T cons[DM_TAB];
     // couples per item, LDS row stride (odd); the tile by label bit (column b * ns +
     // symbol: the 64 lanes of a phase-1 store hit 64 banks, 1.5-4 % faster on every
@@ -2883,6 +2930,7 @@ __global__ __launch_bounds__(BLOCK) void k_demap_planes(int B, int N, int S, con
         // measured faster; QPSK and 64 / 256QAM slower)
         constexpr bool PF = BPS == 3 || BPS == 4;
         float2 zn = PF ? sym_at(T0, lane, si) : make_float2(0.0f, 0.0f);
+        if constexpr (ROWNV) row_nv_stage(rn, tile, B);
         for (int t = T0; t < nt; t += BLOCK) {
             const int ln = lane, sx = si;
             lane += dq;
@@ -2899,7 +2947,11 @@ __global__ __launch_bounds__(BLOCK) void k_demap_planes(int B, int N, int S, con
             double v[BPS];
             if constexpr (SPLIT) {
                 bool dec = false;
-                if (live) dec = !demap_fast<T, BPS, DM_F32OUT>((T)zc.x, (T)zc.y, cons, c, v);
+                if constexpr (ROWNV) {
+                    if (live) dec = !demap_fast<T, BPS, DM_F32OUT>((T)zc.x, (T)zc.y, cons, row_cfg(c, row_nv(rn, ln, cw)), v);
+                } else {
+                    if (live) dec = !demap_fast<T, BPS, DM_F32OUT>((T)zc.x, (T)zc.y, cons, c, v);
+                }
                 // declined symbols go to the list for k_demap_fix (which rewrites their
                 // plane entries): one atomic per wave, entries by lane rank
                 const unsigned long long m = __ballot(dec);
@@ -2918,7 +2970,11 @@ __global__ __launch_bounds__(BLOCK) void k_demap_planes(int B, int N, int S, con
                 if (!live || dec) continue;
             } else {
                 if (!live) continue;
-                demap_sym<T, BPS, DM_F32OUT>((T)zc.x, (T)zc.y, cons, c, v);
+                if constexpr (ROWNV) {
+                    demap_sym<T, BPS, DM_F32OUT>((T)zc.x, (T)zc.y, cons, row_cfg(c, row_nv(rn, ln, cw)), v);
+                } else {
+                    demap_sym<T, BPS, DM_F32OUT>((T)zc.x, (T)zc.y, cons, c, v);
+                }
             }
 #pragma unroll
             for (int b = 0; b < BPS; ++b) L[ln * LD + b * ns + sx] = (float)v[b];
@@ -2968,10 +3024,10 @@ __device__ __forceinline__ void dm_fix_symbol(long cw, long s, int N, int S, con
         else base[(long)N * WAVE * 4 + ((long)k * WAVE + lane) * 2 + (cc - 6)] = (float)v[b];
     }
 }
-template <typename T, int BPS>
+template <typename T, int BPS, bool ROWNV = false>
 __global__ __launch_bounds__(BLOCK) void k_demap_fix(int B, int N, int S, const float *syms, const T *cons_g,
                                                     DemapCfg c, const int *__restrict__ dst, long n_avail,
-                                                    float *planes, DemapDecl dd, long n_tiles) {
+                                                    float *planes, DemapDecl dd, long n_tiles, RowNv<ROWNV> rn = {}) {
     __shared__ T cons[DM_TAB];
     load_table<T, BPS>(cons, cons_g, c);
     __syncthreads();
@@ -2979,13 +3035,21 @@ __global__ __launch_bounds__(BLOCK) void k_demap_fix(int B, int N, int S, const 
     for (unsigned i = blockIdx.x * BLOCK + threadIdx.x; i < n; i += gridDim.x * BLOCK) {
         const int2 e = dd.list[i];
         if (dd.ovf[e.x / WAVE]) continue;   // redone below
-        dm_fix_symbol<T, BPS>(e.x, e.y, N, S, syms, cons, c, dst, n_avail, planes);
+        if constexpr (ROWNV) {
+            dm_fix_symbol<T, BPS>(e.x, e.y, N, S, syms, cons, row_cfg(c, rn.nvs[e.x]), dst, n_avail, planes);
+        } else {
+            dm_fix_symbol<T, BPS>(e.x, e.y, N, S, syms, cons, c, dst, n_avail, planes);
+        }
     }
     for (long t = blockIdx.x; t < n_tiles; t += gridDim.x) {
         if (!dd.ovf[t]) continue;
         for (long i = threadIdx.x; i < (long)WAVE * S; i += BLOCK) {
             const long cw = t * WAVE + i / S;
-            if (cw < B) dm_fix_symbol<T, BPS>(cw, i % S, N, S, syms, cons, c, dst, n_avail, planes);
+            if constexpr (ROWNV) {
+                if (cw < B) dm_fix_symbol<T, BPS>(cw, i % S, N, S, syms, cons, row_cfg(c, rn.nvs[cw]), dst, n_avail, planes);
+            } else {
+                if (cw < B) dm_fix_symbol<T, BPS>(cw, i % S, N, S, syms, cons, c, dst, n_avail, planes);
+            }
         }
     }
 }
@@ -3112,16 +3176,21 @@ __device__ __forceinline__ void demap_lm_sym(T sr, T si, const T *cons, const De
 }
 
 // k_demap's launch shape: one symbol per thread, f64 LLRs
-template <typename T, typename S, int BPS>
+template <typename T, typename S, int BPS, bool ROWNV = false>
 __global__ __launch_bounds__(BLOCK) void k_demap_lm(const S *syms, long n_sym, const T *cons_g, DemapCfg c, double scale,
-                                                   double *llr) {
+                                                   double *llr, RowNv<ROWNV> rn = {}) {
     __shared__ T cons[DM_TAB];
     load_table<T, BPS>(cons, cons_g, c);
     __syncthreads();
     const long s = (long)blockIdx.x * BLOCK + threadIdx.x;
     if (s >= n_sym) return;
     double v[BPS];
-    demap_lm_sym<T, BPS>((T)syms[2 * s], (T)syms[2 * s + 1], cons, c, (T)scale, v);
+    if constexpr (ROWNV) {
+        const DemapCfg rc = row_cfg(c, rn.nvs[s / rn.S]);
+        demap_lm_sym<T, BPS>((T)syms[2 * s], (T)syms[2 * s + 1], cons, rc, (T)row_lm_scale(rc), v);
+    } else {
+        demap_lm_sym<T, BPS>((T)syms[2 * s], (T)syms[2 * s + 1], cons, c, (T)scale, v);
+    }
 #pragma unroll
     for (int b = 0; b < BPS; ++b) llr[s * BPS + b] = v[b];
 }
@@ -3129,11 +3198,11 @@ __global__ __launch_bounds__(BLOCK) void k_demap_lm(const S *syms, long n_sym, c
 // k_demap_planes' items, LDS tile and plane layout (its phase 2 verbatim, so
 // tdec_decode_planes_dev consumes these planes unchanged) around demap_lm_sym;
 // no split and no prefetch: the symbol's work is the transcendentals.
-template <typename T, int BPS>
+template <typename T, int BPS, bool ROWNV = false>
 __global__ __launch_bounds__(BLOCK) void k_demap_planes_lm(int B, int N, int S, const float *syms, const T *cons_g,
                                                           DemapCfg c, double scale, const int *__restrict__ src,
                                                           const int *__restrict__ off, long n_avail, float *planes,
-                                                          long n_items) {
+                                                          long n_items, RowNv<ROWNV> rn = {}) {
     __shared__ T cons[DM_TAB];
     constexpr int KC = dm_kc(BPS), LD = 6 * KC + 2 * BPS + 1;
     __shared__ float L[WAVE * LD];
@@ -3148,13 +3217,19 @@ __global__ __launch_bounds__(BLOCK) void k_demap_planes_lm(int B, int N, int S, 
         const long j0 = off[k0], j1 = off[k1];
         const long s0 = j0 / BPS, s1 = (j1 + BPS - 1) / BPS;        // symbols covering [j0, j1)
         const int ns = (int)(s1 - s0);
+        if constexpr (ROWNV) row_nv_stage(rn, tile, B);
         for (int t = threadIdx.x; t < WAVE * ns; t += BLOCK) {      // consecutive threads: consecutive symbols
             const int ln = t / ns, sx = t - ln * ns;
             const long cw = tile * WAVE + ln, s = s0 + sx;
             if (cw >= B || s >= S) continue;
             const float2 z = *reinterpret_cast<const float2 *>(syms + 2 * (cw * S + s));
             double v[BPS];
-            demap_lm_sym<T, BPS>((T)z.x, (T)z.y, cons, c, sc, v);
+            if constexpr (ROWNV) {
+                const DemapCfg rc = row_cfg(c, row_nv(rn, ln, cw));
+                demap_lm_sym<T, BPS>((T)z.x, (T)z.y, cons, rc, (T)row_lm_scale(rc), v);
+            } else {
+                demap_lm_sym<T, BPS>((T)z.x, (T)z.y, cons, c, sc, v);
+            }
 #pragma unroll
             for (int b = 0; b < BPS; ++b) L[ln * LD + b * ns + sx] = (float)v[b];
         }
@@ -3178,6 +3253,50 @@ __global__ __launch_bounds__(BLOCK) void k_demap_planes_lm(int B, int N, int S, 
             else reinterpret_cast<float2 *>(base + (long)N * WAVE * 4)[(long)k * WAVE + lane] = make_float2(v[0], v[1]);
         }
         __syncthreads();   // L is rewritten by the next item: its reads done everywhere
+    }
+}
+
+// ---- per-row noise variance estimate (build-defined) -------------------
+// The decision-directed estimate of test_sdr_with_coding.py:459-467, one value per
+// row of [B][S] complex64 symbols:
+//   e_s = min_m (dx*dx + dy*dy), dx / dy the f64 differences of the f32 symbol and
+//   table point m (the first minimum in label order: the hard decision re-mapped),
+//   nv[r] = max_py(sum_s e_s / S, floor),  max_py(a, b) = (b > a) ? b : a
+// (a NaN mean stays NaN, Python's max(nv, 0.02)).  A NaN or infinite symbol makes its
+// e_s, and so its row's estimate, NaN.  One block per row; the f64 sum has a fixed
+// order (thread t adds symbols t, t + BLOCK, ... in turn, the 64 partial sums of a wave
+// fold by an xor butterfly, thread 0 adds the four wave sums in order), so a row's
+// value depends on neither B nor the grid.
+template <typename T>
+__global__ __launch_bounds__(BLOCK) void k_noise_var(const float *syms, int S, const T *cons_g, int M, double floor_nv,
+                                                    double *nv) {
+    __shared__ double cons[2 * 256];
+    __shared__ double part[BLOCK / WAVE];
+    for (int i = threadIdx.x; i < 2 * M; i += BLOCK) cons[i] = (double)cons_g[i];
+    __syncthreads();
+    const float *row = syms + 2 * (long)blockIdx.x * S;
+    double acc = 0.0;
+    for (int s = threadIdx.x; s < S; s += BLOCK) {
+        const float2 z = *reinterpret_cast<const float2 *>(row + 2 * s);
+        const double sr = (double)z.x, si = (double)z.y;
+        double e = INFINITY;
+        for (int m = 0; m < M; ++m) {
+            const double dx = sr - cons[2 * m], dy = si - cons[2 * m + 1];
+            const double d = dx * dx + dy * dy;
+            if (d < e) e = d;
+        }
+        acc += e + ((sr - sr) + (si - si));   // + 0, or NaN for a NaN / infinite symbol
+    }
+#pragma unroll
+    for (int o = WAVE / 2; o > 0; o >>= 1) acc += __shfl_xor(acc, o);
+    if ((threadIdx.x & (WAVE - 1)) == 0) part[threadIdx.x / WAVE] = acc;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double sum = part[0];
+#pragma unroll
+        for (int w = 1; w < BLOCK / WAVE; ++w) sum += part[w];
+        const double mean = sum / (double)S;
+        nv[blockIdx.x] = (floor_nv > mean) ? floor_nv : mean;
     }
 }
 

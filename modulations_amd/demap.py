@@ -146,15 +146,64 @@ def compute_llr(syms, mod_type, noise_var, sign=+1, device=0, algo="max-log"):
     return out
 
 
+def _rows_check(syms, nv, name="noise_var"):
+    """A per-row noise variance: a contiguous float64 [B] tensor on the device of the
+    2-D [B, S] complex symbols.  Refused here, before any device call."""
+    import torch
+    if not isinstance(syms, torch.Tensor) or syms.dim() != 2 or not syms.is_complex():
+        raise ValueError(f"a per-row {name} needs 2-D [B, S] complex symbols")
+    if nv.dtype != torch.float64:
+        raise TypeError(f"{name} must be torch.float64, got {nv.dtype}")
+    if tuple(nv.shape) != (syms.shape[0],) or not nv.is_contiguous():
+        raise ValueError(f"{name} must be a contiguous tensor of shape ({syms.shape[0]},), got {tuple(nv.shape)}")
+    if nv.device.type != "cuda" or nv.device != syms.device:
+        raise ValueError(f"{name} must be on the symbols' HIP device")
+
+
+def estimate_noise_var_device(syms, mod_type, floor=0.02, out=None, stream=None):
+    """The receiver's decision-directed noise variance (test_sdr_with_coding.py:459-467:
+    hard decision, re-map, mean |rx - const|^2, max(nv, 0.02)) of each row of complex64
+    [B, S] device symbols: a float64 [B] tensor on their device, stream-ordered, for
+    compute_llr_device / demap_planes_device / DevicePipeline.run to read in place.
+    Build-defined: the f64 mean of the f64 squared distances."""
+    import torch
+    cons = _cons(mod_type)
+    if not isinstance(syms, torch.Tensor) or syms.dtype != torch.complex64:
+        raise TypeError(f"syms must be a torch.complex64 tensor, got {getattr(syms, 'dtype', type(syms))}")
+    if syms.dim() != 2 or syms.shape[1] < 1:
+        raise ValueError("syms must be 2-D [B, S] with S >= 1")
+    if syms.device.type != "cuda" or not syms.is_contiguous():
+        raise ValueError("syms must be a contiguous tensor on a HIP device")
+    B, S = syms.shape
+    if out is None:
+        out = torch.empty(B, dtype=torch.float64, device=syms.device)
+    else:
+        _rows_check(syms, out, "out")
+    f64 = cons.dtype == np.complex128
+    c = np.ascontiguousarray(cons.astype(np.complex128 if f64 else np.complex64))
+    dev = syms.device.index or 0
+    st = _n.stream_ptr(stream) if stream is not None else torch.cuda.current_stream(dev).cuda_stream
+    _n.check(_n.lib().tdec_noise_var_dev(dev, _n.ptr(syms), B, S, _n.ptr(c), int(f64), len(c), float(floor),
+                                         _n.ptr(out), st))
+    return out
+
+
 def compute_llr_device(syms, mod_type, noise_var, out=None, sign=+1, stream=None, algo="max-log"):
     """compute_llr over a device tensor of complex symbols (complex64/complex128 or
-    a float [..., 2] view); returns a float64 device tensor."""
+    a float [..., 2] view); returns a float64 device tensor.  noise_var: a scalar, or
+    a float64 [B] device tensor with 2-D [B, S] symbols (row r demapped with
+    noise_var[r], read on the device: no host round trip); the result is then [B, S*bps]."""
     import torch
     lm = check_algo(algo)
     m = MODULATIONS[mod_type]
     cons = _cons(mod_type)
+    rows = isinstance(noise_var, torch.Tensor)
+    if rows:
+        _rows_check(syms, noise_var)
     sym_f64 = syms.dtype in (torch.complex128, torch.float64)
     n_sym = syms.numel() // (1 if syms.is_complex() else 2)
+    if rows:   # the division's dtype: what a numpy float64 scalar gives (as DevicePipeline.run treats its scalar)
+        noise_var, nvt = np.float64(1.0), noise_var
     f64, div_f32, nv = demap_mode(np.complex128 if sym_f64 else np.complex64, cons.dtype, noise_var)
     c = np.ascontiguousarray(cons.astype(np.complex128 if f64 else np.complex64))
     if syms.device.type != "cuda" or not syms.is_contiguous():
@@ -163,10 +212,20 @@ def compute_llr_device(syms, mod_type, noise_var, out=None, sign=+1, stream=None
         raise TypeError(f"unsupported symbol dtype {syms.dtype}")
     dev = syms.device.index or 0
     if out is None:
-        out = torch.empty(n_sym * m['bps'], dtype=torch.float64, device=syms.device)
+        out = torch.empty((syms.shape[0], syms.shape[1] * m['bps']) if rows else n_sym * m['bps'],
+                          dtype=torch.float64, device=syms.device)
     if out.dtype != torch.float64 or not out.is_contiguous() or out.numel() < n_sym * m['bps'] or out.device != syms.device:
         raise ValueError("out must be a contiguous float64 tensor of n_sym*bps elements on the symbols' device")
     st = _n.stream_ptr(stream) if stream is not None else torch.cuda.current_stream(dev).cuda_stream
+    if rows:
+        B, S = syms.shape
+        if lm:
+            _n.check(_n.lib().tdec_demap_rows_logmap_dev(dev, _n.ptr(syms), int(sym_f64), B, S, _n.ptr(c), int(f64),
+                                                         len(c), m['bps'], _n.ptr(nvt), int(sign), _n.ptr(out), st))
+        else:
+            _n.check(_n.lib().tdec_demap_rows_dev(dev, _n.ptr(syms), int(sym_f64), B, S, _n.ptr(c), int(f64), len(c),
+                                                  m['bps'], _n.ptr(nvt), int(div_f32), int(sign), _n.ptr(out), st))
+        return out
     if lm:
         _n.check(_n.lib().tdec_demap_logmap_dev(dev, _n.ptr(syms), int(sym_f64), n_sym, _n.ptr(c), int(f64),
                                                 len(c), m['bps'], nv, int(sign), _n.ptr(out), st))

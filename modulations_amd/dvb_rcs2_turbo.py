@@ -415,18 +415,31 @@ class DVBRCS2_Turbo:
     def demap_planes_device(self, syms, constellation, bps, noise_var, planes, div_f32=False, stream=None,
                             algo="max-log"):
         """Fused soft demap (decoder sign) + de-puncture of complex64 symbols [B, S];
-        algo="log-map": the exact log-sum demapper (div_f32 has no meaning there)."""
+        algo="log-map": the exact log-sum demapper (div_f32 has no meaning there).
+        noise_var: a scalar, or a float64 [B] tensor on this codec's device (row r
+        demapped with noise_var[r], read on the device)."""
         from .demap import check_algo
         lm = check_algo(algo)
         cons = np.ascontiguousarray(np.asarray(constellation))
         f64 = cons.dtype == np.complex128
         cons = cons.astype(np.complex128 if f64 else np.complex64)
         import torch
+        rows = isinstance(noise_var, torch.Tensor)
+        if rows:
+            self._dev_check(noise_var, "noise_var", torch.float64, (len(syms),))
         self._dev_check(syms, "syms", torch.complex64)
         self._dev_check(planes, "planes", torch.float32)
         B, S = syms.shape[0], syms.shape[1]
         if planes.numel() * 4 < self.planes_bytes(B):
             raise ValueError("planes buffer smaller than planes_bytes(B)")
+        if rows and lm:
+            self.handle.call("tdec_demap_planes_logmap_nv_dev", B, _n.ptr(syms), S, _n.ptr(cons), int(f64), len(cons),
+                             bps, _n.ptr(noise_var), _n.ptr(planes), self._stream(stream))
+            return planes
+        if rows:
+            self.handle.call("tdec_demap_planes_nv_dev", B, _n.ptr(syms), S, _n.ptr(cons), int(f64), len(cons), bps,
+                             _n.ptr(noise_var), int(div_f32), _n.ptr(planes), self._stream(stream))
+            return planes
         if lm:
             self.handle.call("tdec_demap_planes_logmap_dev", B, _n.ptr(syms), S, _n.ptr(cons), int(f64), len(cons),
                              bps, float(noise_var), _n.ptr(planes), self._stream(stream))

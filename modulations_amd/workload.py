@@ -89,7 +89,11 @@ class DevicePipeline:
 
     demap="log-map" demaps with the exact log-sum demapper
     (tdec_demap_planes_logmap_dev) in front of either decoder algorithm; there
-    is no fused kernel for it, so fused=True runs the two launches."""
+    is no fused kernel for it, so fused=True runs the two launches.
+
+    run() also takes a per-row noise variance, a float64 [B] device tensor, on the
+    two-launch and overlap paths; a pipeline built with fused=True
+    refuses it, the fused kernel having no per-row form."""
 
     def __init__(self, codec, mod, B, device, fused=False, overlap=False, gate=True, demap="max-log"):
         import torch
@@ -99,6 +103,7 @@ class DevicePipeline:
         self.demap = demap
         lm = D.check_algo(demap)
         self.early_stop = bool(getattr(codec, "early_stop", False))
+        self.fused_asked = bool(fused)
         self.fused = (bool(fused) and not lm and not self.early_stop
                       and codec.fused_available(self.cons, self.bps))
         self.overlap = bool(overlap) and not self.fused
@@ -133,12 +138,23 @@ class DevicePipeline:
         for work queued on `stream` afterwards).  With overlap=True, `syms_ready`
         (an event after which `syms` is valid) lets the demap start before the
         previous batch's decode has finished; without it the demap waits for
-        everything queued on `stream`, i.e. no overlap."""
-        _, div32, nve = D.demap_mode(np.complex64, self.cons.dtype, np.float64(noise_var))
+        everything queued on `stream`, i.e. no overlap.
+
+        noise_var: a scalar, or a float64 [B] tensor on the symbols' device with one
+        value per row (demap.estimate_noise_var_device queued on the same stream
+        gives it), which the demapper reads on the device."""
+        import torch
+        if isinstance(noise_var, torch.Tensor):
+            if self.fused_asked:
+                raise ValueError("a per-row noise_var tensor needs the two-launch pipeline: the fused "
+                                 "demap+decode kernel has no per-row form (fused=True)")
+            _, div32, _ = D.demap_mode(np.complex64, self.cons.dtype, np.float64(1.0))
+            nve = noise_var
+        else:
+            _, div32, nve = D.demap_mode(np.complex64, self.cons.dtype, np.float64(noise_var))
         bits = self.bits[:syms.shape[0]]          # the first rows: a contiguous view
         es = {"n_iter": self.n_iter[:syms.shape[0]]} if self.early_stop else {}
         if self.overlap:
-            import torch
             stream = torch.cuda.current_stream() if stream is None else stream
             b = self.step & 1
             sd, sk = self.s_demap, self.s_decode

@@ -1,0 +1,103 @@
+#!/usr/bin/env python3
+"""Cost of the per-row noise variance path, in one process with HIP
+events: tdec_demap_planes_dev against tdec_demap_planes_nv_dev with every row
+carrying the same value (so both write the same planes, which is checked), max-log
+and log-MAP, interleaved round by round in both orders, plus the estimator
+(tdec_noise_var_dev) on the same symbols.
+
+  python tools/demap_rownv_measure.py [--mods 16QAM 256QAM --batch 1048576 --rounds 5] [--out f.json]
+
+TDEC_LIB_VARIANT=<name> measures a side-by-side build (build.py --variant), e.g. the
+LDS staging of a tile's 64 values (-DDM_ROWNV_LDS=1)."""
+import argparse
+import json
+import os
+import sys
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+from modulations_amd import demap as D  # noqa: E402
+from modulations_amd import dvb_rcs2_turbo as M  # noqa: E402
+from modulations_amd.workload import make_symbols  # noqa: E402
+
+
+def stats(t):
+    return {"median": float(np.median(t)), "min": float(np.min(t)), "max": float(np.max(t))}
+
+
+def measure(mod, a, dev):
+    est = torch.empty(a.batch, dtype=torch.float64, device=dev)
+    codec = M.DVBRCS2_Turbo(a.n, a.rate, interleaver="valid-perm", device=0)
+    B = a.batch
+    _, syms, n0 = make_symbols(codec, B, mod, a.ebn0, 99, dev, want_info=False)
+    cons = D.constellation(mod)
+    bps = D.MODULATIONS[mod]["bps"]
+    _, div32, nve = D.demap_mode(np.complex64, cons.dtype, np.float64(n0))
+    nvt = torch.full((B,), nve, dtype=torch.float64, device=dev)
+    codec.reserve(B)
+    planes = torch.empty(codec.planes_bytes(B) // 4, dtype=torch.float32, device=dev)
+    st = torch.cuda.current_stream()
+    variants = [(algo, kind) for algo in ("max-log", "log-map") for kind in ("scalar", "per-row")]
+    times = {f"{algo} {kind}": [] for algo, kind in variants}
+    times["estimator"] = []
+    sums = {}
+
+    def timed(fn):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record(st)
+        fn()
+        e1.record(st)
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1)
+
+    for r in range(2 * a.rounds + 1):                  # round 0 untimed; odd rounds forward, even rounds reversed
+        for algo, kind in (variants if r % 2 else variants[::-1]):
+            nv = nvt if kind == "per-row" else nve
+            t = timed(lambda: codec.demap_planes_device(syms, cons, bps, nv, planes, div_f32=div32, algo=algo))
+            if r:
+                times[f"{algo} {kind}"].append(t)
+            else:                                      # the same planes from both forms
+                sums[(algo, kind)] = planes.view(torch.int32).sum(dtype=torch.int64).item()
+        t = timed(lambda: D.estimate_noise_var_device(syms, mod, out=est))
+        if r:
+            times["estimator"].append(t)
+    for algo in ("max-log", "log-map"):
+        assert sums[(algo, "scalar")] == sums[(algo, "per-row")], f"{mod} {algo}: planes differ"
+    ms = {k: stats(t) for k, t in times.items()}
+    rec = {"mod": mod, "n_couples": a.n, "rate": a.rate, "codewords": B, "symbols": int(syms.numel()),
+           "ebn0_db": a.ebn0, "noise_var": nve, "rounds_each_order": a.rounds,
+           "lib": os.environ.get("TDEC_LIB_VARIANT", "libtdec"), "ms": ms,
+           "ratio_per_row_over_scalar": {algo: ms[f"{algo} per-row"]["median"] / ms[f"{algo} scalar"]["median"]
+                                         for algo in ("max-log", "log-map")},
+           "scalar_spread": {algo: (ms[f"{algo} scalar"]["max"] - ms[f"{algo} scalar"]["min"]) /
+                             ms[f"{algo} scalar"]["median"] for algo in ("max-log", "log-map")}}
+    print(json.dumps(rec), flush=True)
+    return rec
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--mods", nargs="+", default=["16QAM", "256QAM"])
+    ap.add_argument("--n", type=int, default=752)
+    ap.add_argument("--rate", default="1/3")
+    ap.add_argument("--batch", type=int, default=1 << 20)
+    ap.add_argument("--rounds", type=int, default=5)
+    ap.add_argument("--ebn0", type=float, default=2.0)
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args()
+    dev = torch.device("cuda", 0)
+    recs = []
+    for m in a.mods:
+        recs.append(measure(m, a, dev))
+        torch.cuda.empty_cache()
+    if a.out:
+        with open(a.out, "w") as f:
+            json.dump(recs, f, indent=1)
+
+
+if __name__ == "__main__":
+    main()
