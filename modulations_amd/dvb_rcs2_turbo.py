@@ -151,7 +151,8 @@ class DVBRCS2_Turbo:
                  outputs are the same bit for bit):
                  'frame' (default)  one codeword per workgroup: the lowest latency
                           per call; ValueError where the frame decoder is
-                          unavailable (TDEC_FRAME=0, N > 805).
+                          unavailable (TDEC_FRAME=0; every block size of the
+                          tables fits it, N = 848 with Le2 in global scratch).
                  'tile'   the throughput decoder (64 codewords per wave), which
                           retires a tile once all its codewords have stopped
                           (tdec_decode_*_es_tile*): for batches,

@@ -86,6 +86,13 @@ def set_trans(tables=None):
     L.orc_set_trans(et.ctypes.data, int(elo), et.size, lt.ctypes.data, int(llo), lt.size)
 
 
+def trans_pinned():
+    """Whether set_trans() currently pins the log-MAP primitives to a device's
+    tables (a log-MAP result computed then differs from one computed with the
+    correctly rounded primitives: callers that cache results key on this)."""
+    return _trans_keep is not None
+
+
 def trellis():
     t = np.zeros((5, 16, 4), np.int32)
     G = np.zeros((4, 4), np.int32)

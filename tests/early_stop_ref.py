@@ -75,12 +75,21 @@ def decode_early_stop_batch(llr, n, punct, iterations, perm, inv_perm, tables, a
             np.array([r[2] for r in rows], np.int32))
 
 
-def bpsk_llrs(codec, rng, B, ebn0_db):
-    """BPSK LLRs 2y / sigma^2 (decoder sign: bit 0 -> +1) of B random codewords of
-    `codec` at Eb/N0 = ebn0_db: (info bits [B, 2N], float32 llr [B, n_coded])."""
-    info = rng.integers(0, 2, (B, codec.k_info))
-    coded = codec.encode_batch(info)
-    r = codec.k_info / coded.shape[1]
+def bpsk_channel(coded, k_info, rng, ebn0_db):
+    """BPSK LLRs 2y / sigma^2 (decoder sign: bit 0 -> +1) of the codewords `coded`
+    [B, n] over AWGN at Eb/N0 = ebn0_db (a number, or one value per row [B]):
+    float32 [B, n]."""
+    r = k_info / coded.shape[1]
+    if not np.isscalar(ebn0_db):
+        ebn0_db = np.asarray(ebn0_db, np.float64)[:, None]
     sigma2 = 1.0 / (2.0 * r * 10.0 ** (ebn0_db / 10.0))
     y = (1.0 - 2.0 * coded) + rng.standard_normal(coded.shape) * np.sqrt(sigma2)
-    return info, (2.0 * y / sigma2).astype(np.float32)
+    return (2.0 * y / sigma2).astype(np.float32)
+
+
+def bpsk_llrs(codec, rng, B, ebn0_db):
+    """bpsk_channel of B random codewords of `codec` at Eb/N0 = ebn0_db:
+    (info bits [B, 2N], float32 llr [B, n_coded])."""
+    info = rng.integers(0, 2, (B, codec.k_info))
+    coded = codec.encode_batch(info)
+    return info, bpsk_channel(coded, codec.k_info, rng, ebn0_db)

@@ -18,6 +18,10 @@ Which inverse interleaver a vector used is recorded per file
 build's canonical pin; ``inv_default`` is what this container's numpy
 (2.2.6, AVX-512) returns for the reference's unstable argsort.
 
+The full-decode vectors here cover 7 of the 28 (N, rate) codecs;
+tests/golden/make_golden_matrix.py (decode_matrix.npz) decodes two codewords
+of every one, reusing this module's helpers.
+
 Usage:  python tests/golden/make_golden.py   (takes a few minutes)
 """
 import os

@@ -98,6 +98,59 @@ def test_encode_golden(G_encode):
             assert np.array_equal(O.encode(b, n, punct["period"], pm, T.interleaver(n), t, G), c), key
 
 
+# ---- every codec of the tables (tests/golden/make_golden_matrix.py) -----------------------
+MATRIX = [(n, rate) for n in T.INTERLEAVER_PARAMS for rate in T.PUNCTURE_PATTERNS]
+MATRIX_NAMES = ("info", "coded", "llr", "bits", "lfinal", "inv")
+
+
+def _mkey(n, rate):
+    return f"{n}_{rate.replace('/', '_')}"
+
+
+@pytest.fixture(scope="module")
+def G_matrix():
+    return golden("decode_matrix")
+
+
+def test_matrix_golden_covers_exactly_the_codec_table(G_matrix):
+    assert len(MATRIX) == 28
+    want = {f"{name}_{_mkey(n, rate)}" for n, rate in MATRIX for name in MATRIX_NAMES}
+    assert set(G_matrix.files) == want
+
+
+@pytest.mark.parametrize("n,rate", MATRIX, ids=[_mkey(*c) for c in MATRIX])
+def test_matrix_decode_golden(G_matrix, n, rate):
+    """oracle.decode_batch equals the reference's decode() on every (N, rate): two
+    codewords (QPSK over AWGN at 1 and 3 dB), rows as long as the de-puncture walk."""
+    g, key = G_matrix, _mkey(n, rate)
+    t, _ = O.trellis()
+    punct = T.PUNCTURE_PATTERNS[rate]
+    perm = T.interleaver(n)
+    assert np.array_equal(g[f"inv_{key}"], T.inverse_interleaver(perm, "stable"))
+    llr = g[f"llr_{key}"]
+    assert llr.dtype == np.float32 and llr.shape == (2, T.consumed_size(n, punct))
+    bits, lf = O.decode_batch(llr, n, punct["period"], T.puncture_matrix(punct), 8, perm, g[f"inv_{key}"], t,
+                              want_lfinal=True)
+    assert np.array_equal(bits, g[f"bits_{key}"])
+    assert np.array_equal(lf, g[f"lfinal_{key}"])
+    assert not np.isnan(lf).any()   # (== on NaN would be vacuous)
+
+
+@pytest.mark.parametrize("n,rate", MATRIX, ids=[_mkey(*c) for c in MATRIX])
+def test_matrix_encode_golden(G_matrix, n, rate):
+    """oracle.encode and the library's host encoder (tdec_encode_host) equal the
+    reference's encode() on every (N, rate), at encode()'s own length."""
+    from modulations_amd import dvb_rcs2_turbo as M
+    g, key = G_matrix, _mkey(n, rate)
+    t, G = O.trellis()
+    punct = T.PUNCTURE_PATTERNS[rate]
+    info, coded = g[f"info_{key}"], g[f"coded_{key}"]
+    for b, c in zip(info, coded):
+        assert np.array_equal(O.encode(b, n, punct["period"], T.puncture_matrix(punct), T.interleaver(n), t, G), c)
+    got = M.DVBRCS2_Turbo(n, rate).encode_batch(info)
+    assert got.dtype == np.int32 and np.array_equal(got, coded)
+
+
 @pytest.mark.parametrize("mod,bps", [("BPSK", 1), ("QPSK", 2), ("8PSK", 3), ("16QAM", 4)])
 def test_demap_golden(G_demap, mod, bps):
     g = G_demap
