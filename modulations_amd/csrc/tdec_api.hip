@@ -316,26 +316,6 @@ static DemapCfg demap_cfg(int M, int div_f32, int sign, double noise_var, int se
 // 1 / (nv ln 2): the log-MAP demapper's exponents in bits, once per launch
 static double demap_lm_scale(const DemapCfg &c) { return 1.0 / (c.nv * 0.693147180559945309417); }
 
-template <typename T, typename S>
-int launch_demap(bool lm, int bps, const S *d_syms, long n_sym, const T *d_cons, DemapCfg c, double *d_llr,
-                        hipStream_t st) {
-    const dim3 grid((unsigned)((n_sym + BLOCK - 1) / BLOCK));
-    const double scale = demap_lm_scale(c);
-    switch (bps) {
-#define CASE(K)                                                                                                      \
-    case K:                                                                                                          \
-        if (lm) hipLaunchKernelGGL((k_demap_lm<T, S, K>), grid, dim3(BLOCK), 0, st, d_syms, n_sym, d_cons, c, scale, \
-                                   d_llr);                                                                           \
-        else hipLaunchKernelGGL((k_demap<T, S, K>), grid, dim3(BLOCK), 0, st, d_syms, n_sym, d_cons, c, d_llr);      \
-        break;
-        CASE(1) CASE(2) CASE(3) CASE(4) CASE(5) CASE(6) CASE(7) CASE(8)
-#undef CASE
-    default: return fail(TDEC_EINVAL, "bps must be 1..8");
-    }
-    HIPCHK(hipGetLastError());
-    return 0;
-}
-
 int check_demap_args(int M, int bps) {
     if (bps < 1 || bps > 8 || M < 1 || M > (1 << bps) || M > 256) return fail(TDEC_EINVAL, "bad constellation size");
     return 0;
@@ -1905,9 +1885,17 @@ int tdec_siso_batch_f64(tdec_t *h, int B, const double *LcA, const double *LcB, 
     return siso_batch_impl<double>(h, B, LcA, LcB, LcW, LcY, LaA, LaB, sf, LeA, LeB);
 }
 
+}  // extern "C"
+
+// ---- demapper entry points ------------------------------------------
+// Templates on ROWNV (noise_var per launch, or noise_var[row] read on the device).  Kernel
+// templates are emitted in the order this file first names them; the ROWNV = true
+// instantiations are first named at the end of this file.
+namespace {
+
 // The handle-less calls' device table (the caller holds the device's Guard)
-static int cached_table(int device, const void *cons, int cons_f64, int M, int bps, bool f64, hipStream_t st,
-                        ConsCache **out) {
+int cached_table(int device, const void *cons, int cons_f64, int M, int bps, bool f64, hipStream_t st,
+                 ConsCache **out) {
     // Tables are cached per (thread, device) by content and never overwritten
     // while another stream may still read them: a new table takes a fresh slot;
     // only when all slots are taken is the oldest reused, after a device-wide
@@ -1933,41 +1921,58 @@ static int cached_table(int device, const void *cons, int cons_f64, int M, int b
     return hit->upload(cons, cons_f64, M, bps, f64, st);
 }
 
-// The flat demappers' entry (lm: the log-MAP kernels; div_f32 is the max-log path's alone)
-static int demap_dev(bool lm, int device, const void *d_syms, int sym_f64, long n_sym, const void *cons, int cons_f64,
-                     int M, int bps, double noise_var, int div_f32, int sign, double *d_llr, void *stream) {
-    if (!d_syms || !cons || !d_llr || n_sym < 0) return fail(TDEC_EINVAL, "bad demap arguments");
+// k_demap / k_demap_lm (lm) over n_sym symbols.  With ROWNV the kernels form each row's
+// configuration from rn, and the launch's log-MAP scale is not read: 0.0
+template <typename T, typename S, bool ROWNV>
+int launch_demap(bool lm, int bps, const S *d_syms, long n_sym, const T *d_cons, DemapCfg c, RowNv<ROWNV> rn,
+                 double *d_llr, hipStream_t st) {
+    const dim3 grid((unsigned)((n_sym + BLOCK - 1) / BLOCK));
+    const double scale = ROWNV ? 0.0 : demap_lm_scale(c);
+    switch (bps) {
+#define CASE(K)                                                                                                      \
+    case K:                                                                                                          \
+        if (lm) hipLaunchKernelGGL((k_demap_lm<T, S, K, ROWNV>), grid, dim3(BLOCK), 0, st, d_syms, n_sym, d_cons, c, \
+                                   scale, d_llr, rn);                                                                \
+        else hipLaunchKernelGGL((k_demap<T, S, K, ROWNV>), grid, dim3(BLOCK), 0, st, d_syms, n_sym, d_cons, c,       \
+                                d_llr, rn);                                                                          \
+        break;
+        CASE(1) CASE(2) CASE(3) CASE(4) CASE(5) CASE(6) CASE(7) CASE(8)
+#undef CASE
+    default: return fail(TDEC_EINVAL, "bps must be 1..8");
+    }
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+// The flat demappers' entry over [B][S] symbols: B = 1 and noise_var for the scalar calls,
+// d_nv[row] with ROWNV (c.nv is then the kernels' to fill).  lm: the log-MAP kernels;
+// div_f32 is the max-log path's alone
+template <bool ROWNV>
+int demap_dev(bool lm, int device, const void *d_syms, int sym_f64, long B, long S, const void *cons, int cons_f64,
+              int M, int bps, double noise_var, const double *d_nv, int div_f32, int sign, double *d_llr,
+              void *stream) {
+    if (!d_syms || !cons || !d_llr || (ROWNV && !d_nv) || B < 0 || S < 0)
+        return fail(TDEC_EINVAL, "bad demap arguments");
     if (int rc = check_demap_args(M, bps)) return rc;
-    if (n_sym == 0) return 0;
+    if (B == 0 || S == 0) return 0;
     Guard g(device);
     const bool f64 = sym_f64 || cons_f64;
     hipStream_t st = (hipStream_t)stream;
-    ConsCache *hit = nullptr;
-    if (int rc = cached_table(device, cons, cons_f64, M, bps, f64, st, &hit)) return rc;
-    ConsCache &cc = *hit;
-    DevBuf &tb = cc.buf;
-    const DemapCfg c = demap_cfg(M, div_f32, sign, noise_var, cc.sep);
-    if (f64) {
-        if (sym_f64) return launch_demap<double, double>(lm, bps, (const double *)d_syms, n_sym, (const double *)tb.p, c, d_llr, st);
-        return launch_demap<double, float>(lm, bps, (const float *)d_syms, n_sym, (const double *)tb.p, c, d_llr, st);
-    }
-    return launch_demap<float, float>(lm, bps, (const float *)d_syms, n_sym, (const float *)tb.p, c, d_llr, st);
-}
-
-int tdec_demap_dev(int device, const void *d_syms, int sym_f64, long n_sym, const void *cons, int cons_f64, int M,
-                   int bps, double noise_var, int div_f32, int sign, double *d_llr, void *stream) {
-    return demap_dev(false, device, d_syms, sym_f64, n_sym, cons, cons_f64, M, bps, noise_var, div_f32, sign, d_llr,
-                     stream);
-}
-
-int tdec_demap_logmap_dev(int device, const void *d_syms, int sym_f64, long n_sym, const void *cons, int cons_f64,
-                          int M, int bps, double noise_var, int sign, double *d_llr, void *stream) {
-    return demap_dev(true, device, d_syms, sym_f64, n_sym, cons, cons_f64, M, bps, noise_var, 0, sign, d_llr, stream);
+    ConsCache *cc = nullptr;
+    if (int rc = cached_table(device, cons, cons_f64, M, bps, f64, st, &cc)) return rc;
+    const DemapCfg c = demap_cfg(M, lm ? 0 : div_f32, sign, ROWNV ? 0.0 : noise_var, cc->sep);
+    RowNv<ROWNV> rn{};
+    if constexpr (ROWNV) rn = {d_nv, S};
+    const void *tab = cc->buf.p;
+    if (f64 && sym_f64)
+        return launch_demap(lm, bps, (const double *)d_syms, B * S, (const double *)tab, c, rn, d_llr, st);
+    if (f64) return launch_demap(lm, bps, (const float *)d_syms, B * S, (const double *)tab, c, rn, d_llr, st);
+    return launch_demap(lm, bps, (const float *)d_syms, B * S, (const float *)tab, c, rn, d_llr, st);
 }
 
 // The host-pointer forms: symbols up, the device entry on a stream of its own, LLRs down
-static int demap_host(bool lm, int device, const void *syms, int sym_f64, long n_sym, const void *cons, int cons_f64,
-                      int M, int bps, double noise_var, int div_f32, int sign, double *llr) {
+int demap_host(bool lm, int device, const void *syms, int sym_f64, long n_sym, const void *cons, int cons_f64,
+               int M, int bps, double noise_var, int div_f32, int sign, double *llr) {
     if (!syms || !cons || !llr || n_sym < 0) return fail(TDEC_EINVAL, "bad demap arguments");
     if (int rc = check_demap_args(M, bps)) return rc;
     if (n_sym == 0) return 0;
@@ -1983,14 +1988,122 @@ static int demap_host(bool lm, int device, const void *syms, int sym_f64, long n
     HIPCHK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
     int rc = 0;
     if (hipMemcpyAsync(ds, syms, ns, hipMemcpyHostToDevice, st) != hipSuccess) rc = fail(TDEC_EHIP, "memcpy");
-    if (!rc) rc = demap_dev(lm, device, ds, sym_f64, n_sym, cons, cons_f64, M, bps, noise_var, div_f32, sign,
-                            (double *)dl, st);
+    if (!rc) rc = demap_dev<false>(lm, device, ds, sym_f64, 1, n_sym, cons, cons_f64, M, bps, noise_var, nullptr,
+                                   div_f32, sign, (double *)dl, st);
     if (!rc && hipMemcpyAsync(llr, dl, nl, hipMemcpyDeviceToHost, st) != hipSuccess) rc = fail(TDEC_EHIP, "memcpy");
     if (!rc && hipStreamSynchronize(st) != hipSuccess) rc = fail(TDEC_EHIP, "demap failed");
     hipStreamDestroy(st);
     hipFree(ds);
     hipFree(dl);
     return rc;
+}
+
+// The handle's table, for a launch on st.  Ordered on the handle first: the table may still
+// be read on another stream, and a new one overwrites it
+int handle_table(tdec_t *h, const void *cons, int cons_f64, int M, int bps, hipStream_t st) {
+    if (int rc = order_on(h, st)) return rc;
+    return h->cons.upload(cons, cons_f64, M, bps, cons_f64 != 0, st);
+}
+
+// One plane-demapper launch over (64-codeword tile, dm_kc-couple chunk) items, a block each:
+// k_demap_planes_lm (lm), k_demap_planes<SPLIT> + k_demap_fix (split tables) or k_demap_planes
+template <typename TT, int K, bool ROWNV>
+void launch_planes(bool lm, bool split, tdec_t *h, int B, int S, const float *d_syms, DemapCfg c, float *P,
+                   RowNv<ROWNV> rn, hipStream_t st) {
+    const long n_avail = std::min<long>((long)S * K, h->llr_len);   // LLRs the symbols provide
+    const long n_tiles = n_tiles_of(B), n_items = n_tiles * ((h->N + dm_kc(K) - 1) / dm_kc(K));
+    const dim3 grid((unsigned)n_items), fgrid((unsigned)std::max<long>(1, std::min<long>(n_tiles, 1024)));
+    const TT *tab = (const TT *)h->cons.buf.p;
+    const int *src = h->d_src, *off = h->d_off, *dst = h->d_dst;
+    const DemapDecl dd{h->d_decl, h->d_decl_n, h->d_decl_ovf, DM_DECL_CAP};
+    if (lm) {   // the scale per launch; with ROWNV the kernel forms each row's: 0.0
+        hipLaunchKernelGGL((k_demap_planes_lm<TT, K, ROWNV>), grid, dim3(BLOCK), 0, st, B, h->N, S, d_syms, tab, c,
+                           ROWNV ? 0.0 : demap_lm_scale(c), src, off, n_avail, P, n_items, rn);
+        return;
+    }
+    if constexpr (dm_split(K)) {
+        if (split) {
+            hipLaunchKernelGGL((k_demap_planes<TT, K, true, ROWNV>), grid, dim3(BLOCK), 0, st, B, h->N, S, d_syms, tab, c,
+                               src, off, n_avail, P, n_items, dd, rn);
+            hipLaunchKernelGGL((k_demap_fix<TT, K, ROWNV>), fgrid, dim3(BLOCK), 0, st, B, h->N, S, d_syms, tab, c, dst,
+                               n_avail, P, dd, n_tiles, rn);
+            return;
+        }
+    }
+    hipLaunchKernelGGL((k_demap_planes<TT, K, false, ROWNV>), grid, dim3(BLOCK), 0, st, B, h->N, S, d_syms, tab, c, src,
+                       off, n_avail, P, n_items, dd, rn);
+}
+
+// The plane demappers' entry: noise_var, or d_nv[row] with ROWNV (c.nv is then the kernels'
+// to fill).  lm: the log-MAP kernels, which have no div_f32 and no decline list
+template <bool ROWNV>
+int demap_planes(bool lm, tdec_t *h, int B, const float *d_syms, int S, const void *cons, int cons_f64, int M, int bps,
+                 double noise_var, const double *d_nv, int div_f32, float *d_planes, void *stream) {
+    if (!h || B < 0 || !cons) return fail(TDEC_EINVAL, "bad demap arguments");
+    if (int rc = check_demap_args(M, bps)) return rc;
+    if (B == 0) return 0;
+    if (!d_syms || !d_planes || (ROWNV && !d_nv) || S <= 0) return fail(TDEC_EINVAL, "bad demap arguments");
+    Guard g(h->device);
+    hipStream_t st = (hipStream_t)stream;
+    if (int rc = handle_table(h, cons, cons_f64, M, bps, st)) return rc;
+    const DemapCfg c = demap_cfg(M, lm ? 0 : div_f32, -1, ROWNV ? 0.0 : noise_var, h->cons.sep);
+    RowNv<ROWNV> rn{};
+    if constexpr (ROWNV) rn = {d_nv, S};
+    const bool split = !lm && dm_split_table(bps, h->cons.sep);
+    if (split) {   // the decline list: sized by tdec_reserve / tdec_reserve_fused
+        const long n_tiles = n_tiles_of(B);
+        if (h->decl_tiles < n_tiles) {
+            // an unreserved batch: allocate here, outside any stream capture (hipFree
+            // synchronises the device, and a captured graph must not hold a buffer
+            // freed by a later regrowth)
+            if (capturing(st)) return fail(TDEC_ECAPACITY, "demap batch larger than tdec_reserve() (stream capture)");
+            quiesce(h);
+            if (int rc = ensure_decl(h, n_tiles)) return rc;
+        }
+        HIPCHK(hipMemsetAsync(h->d_decl_n, 0, sizeof(unsigned), st));
+        HIPCHK(hipMemsetAsync(h->d_decl_ovf, 0, (size_t)n_tiles, st));
+    }
+    switch (bps) {
+#define CASE(K)                                                                                       \
+    case K:                                                                                           \
+        if (cons_f64) launch_planes<double, K>(lm, split, h, B, S, d_syms, c, d_planes, rn, st);      \
+        else launch_planes<float, K>(lm, split, h, B, S, d_syms, c, d_planes, rn, st);                \
+        break;
+        CASE(1) CASE(2) CASE(3) CASE(4) CASE(5) CASE(6) CASE(7) CASE(8)
+#undef CASE
+    default: return fail(TDEC_EINVAL, "bps must be 1..8");
+    }
+    HIPCHK(hipGetLastError());
+    return mark_used(h, st);
+}
+
+// launch_planes names a log-MAP kernel in front of each max-log one, which is the order of
+// the per-row kernels in the code object.  The scalar max-log kernels are older than the
+// log-MAP demapper and stand in front of all its kernels there, so they are named here
+// first, in that order, and every kernel keeps its place (nothing calls this).
+template <typename TT, int K> void name_scalar_maxlog_planes() {
+    if constexpr (dm_split(K)) (void)k_demap_planes<TT, K, true>, (void)k_demap_fix<TT, K>;
+    (void)k_demap_planes<TT, K, false>;
+}
+[[maybe_unused]] void scalar_maxlog_planes_first() {
+#define CASE(K) name_scalar_maxlog_planes<double, K>(), name_scalar_maxlog_planes<float, K>();
+    CASE(1) CASE(2) CASE(3) CASE(4) CASE(5) CASE(6) CASE(7) CASE(8)
+#undef CASE
+}
+}  // namespace
+
+extern "C" {
+
+int tdec_demap_dev(int device, const void *d_syms, int sym_f64, long n_sym, const void *cons, int cons_f64, int M,
+                   int bps, double noise_var, int div_f32, int sign, double *d_llr, void *stream) {
+    return demap_dev<false>(false, device, d_syms, sym_f64, 1, n_sym, cons, cons_f64, M, bps, noise_var, nullptr,
+                            div_f32, sign, d_llr, stream);
+}
+
+int tdec_demap_logmap_dev(int device, const void *d_syms, int sym_f64, long n_sym, const void *cons, int cons_f64,
+                          int M, int bps, double noise_var, int sign, double *d_llr, void *stream) {
+    return demap_dev<false>(true, device, d_syms, sym_f64, 1, n_sym, cons, cons_f64, M, bps, noise_var, nullptr, 0,
+                            sign, d_llr, stream);
 }
 
 int tdec_demap(int device, const void *syms, int sym_f64, long n_sym, const void *cons, int cons_f64, int M, int bps,
@@ -2044,111 +2157,13 @@ int tdec_selftest_trans(int device, int which, uint32_t lo_bits, long long n, fl
 
 int tdec_demap_planes_dev(tdec_t *h, int B, const float *d_syms, int S, const void *cons, int cons_f64, int M,
                           int bps, double noise_var, int div_f32, float *d_planes, void *stream) {
-    if (!h || B < 0 || !cons) return fail(TDEC_EINVAL, "bad demap arguments");
-    if (int rc = check_demap_args(M, bps)) return rc;
-    if (B == 0) return 0;
-    if (!d_syms || !d_planes || S <= 0) return fail(TDEC_EINVAL, "bad demap arguments");
-    Guard g(h->device);
-    hipStream_t st = (hipStream_t)stream;
-    if (int rc = order_on(h, st)) return rc;   // the table below may still be read on another stream
-    if (int rc = h->cons.upload(cons, cons_f64, M, bps, cons_f64 != 0, st)) return rc;
-    const DemapCfg c = demap_cfg(M, div_f32, -1, noise_var, h->cons.sep);
-    const long n_avail = std::min<long>((long)S * bps, h->llr_len);   // LLRs the symbols provide
-    const int chunks = (h->N + dm_kc(bps) - 1) / dm_kc(bps);
-    const long n_items = (long)n_tiles_of(B) * chunks;   // (64-codeword tile, dm_kc-couple chunk) pairs
-    float *P = d_planes;
-    const long n_tiles = n_tiles_of(B);
-    DemapDecl dd{h->d_decl, h->d_decl_n, h->d_decl_ovf, DM_DECL_CAP};
-    const bool split = dm_split_table(bps, h->cons.sep);
-    if (split) {   // the decline list: sized by tdec_reserve / tdec_reserve_fused
-        if (h->decl_tiles < n_tiles) {
-            // an unreserved batch: allocate here, outside any stream capture (hipFree
-            // synchronises the device, and a captured graph must not hold a buffer
-            // freed by a later regrowth)
-            if (capturing(st)) return fail(TDEC_ECAPACITY, "demap batch larger than tdec_reserve() (stream capture)");
-            quiesce(h);
-            if (int rc = ensure_decl(h, n_tiles)) return rc;
-        }
-        dd = DemapDecl{h->d_decl, h->d_decl_n, h->d_decl_ovf, DM_DECL_CAP};
-        HIPCHK(hipMemsetAsync(h->d_decl_n, 0, sizeof(unsigned), st));
-        HIPCHK(hipMemsetAsync(h->d_decl_ovf, 0, (size_t)n_tiles, st));
-    }
-    const dim3 grid((unsigned)n_items);   // one block per item
-    const dim3 fgrid((unsigned)std::max<long>(1, std::min<long>(n_tiles, 1024)));
-    switch (bps) {
-#define LAUNCH_PLANES(TT, K, SP, F64)                                                                     \
-    hipLaunchKernelGGL((k_demap_planes<TT, K, SP>), grid, dim3(BLOCK),                                  \
-                       0, st, B, h->N, S, d_syms, (const TT *)h->cons.buf.p, c, (const int *)h->d_src,          \
-                       (const int *)h->d_off, n_avail, P, n_items, dd)
-#define CASE(K)                                                                                              \
-    case K:                                                                                                  \
-        if (cons_f64) {                                                                                      \
-            if constexpr (dm_split(K)) {                                                                     \
-                if (split) {                                                                                 \
-                    LAUNCH_PLANES(double, K, dm_split(K), 1);                                                \
-                    hipLaunchKernelGGL((k_demap_fix<double, K>), fgrid, dim3(BLOCK), 0, st, B, h->N, S, d_syms, \
-                                       (const double *)h->cons.buf.p, c, (const int *)h->d_dst, n_avail, P, dd, \
-                                       n_tiles);                                                             \
-                    break;                                                                                   \
-                }                                                                                            \
-            }                                                                                                \
-            LAUNCH_PLANES(double, K, false, 1);                                                              \
-        } else {                                                                                             \
-            if constexpr (dm_split(K)) {                                                                     \
-                if (split) {                                                                                 \
-                    LAUNCH_PLANES(float, K, dm_split(K), 0);                                                 \
-                    hipLaunchKernelGGL((k_demap_fix<float, K>), fgrid, dim3(BLOCK), 0, st, B, h->N, S, d_syms,  \
-                                       (const float *)h->cons.buf.p, c, (const int *)h->d_dst, n_avail, P, dd,  \
-                                       n_tiles);                                                             \
-                    break;                                                                                   \
-                }                                                                                            \
-            }                                                                                                \
-            LAUNCH_PLANES(float, K, false, 0);                                                               \
-        }                                                                                                    \
-        break;
-        CASE(1) CASE(2) CASE(3) CASE(4) CASE(5) CASE(6) CASE(7) CASE(8)
-#undef CASE
-#undef LAUNCH_PLANES
-    default: return fail(TDEC_EINVAL, "bps must be 1..8");
-    }
-    HIPCHK(hipGetLastError());
-    return mark_used(h, st);
+    return demap_planes<false>(false, h, B, d_syms, S, cons, cons_f64, M, bps, noise_var, nullptr, div_f32, d_planes,
+                               stream);
 }
 
 int tdec_demap_planes_logmap_dev(tdec_t *h, int B, const float *d_syms, int S, const void *cons, int cons_f64, int M,
                                  int bps, double noise_var, float *d_planes, void *stream) {
-    if (!h || B < 0 || !cons) return fail(TDEC_EINVAL, "bad demap arguments");
-    if (int rc = check_demap_args(M, bps)) return rc;
-    if (B == 0) return 0;
-    if (!d_syms || !d_planes || S <= 0) return fail(TDEC_EINVAL, "bad demap arguments");
-    Guard g(h->device);
-    hipStream_t st = (hipStream_t)stream;
-    if (int rc = order_on(h, st)) return rc;   // the table below may still be read on another stream
-    if (int rc = h->cons.upload(cons, cons_f64, M, bps, cons_f64 != 0, st)) return rc;
-    const DemapCfg c = demap_cfg(M, 0, -1, noise_var, h->cons.sep);
-    const double scale = demap_lm_scale(c);
-    const long n_avail = std::min<long>((long)S * bps, h->llr_len);   // LLRs the symbols provide
-    const int chunks = (h->N + dm_kc(bps) - 1) / dm_kc(bps);
-    const long n_items = (long)n_tiles_of(B) * chunks;
-    const dim3 grid((unsigned)n_items);   // one block per item
-    switch (bps) {
-#define CASE(K)                                                                                                     \
-    case K:                                                                                                         \
-        if (cons_f64)                                                                                               \
-            hipLaunchKernelGGL((k_demap_planes_lm<double, K>), grid, dim3(BLOCK), 0, st, B, h->N, S, d_syms,         \
-                               (const double *)h->cons.buf.p, c, scale, (const int *)h->d_src, (const int *)h->d_off, \
-                               n_avail, d_planes, n_items);                                                         \
-        else                                                                                                        \
-            hipLaunchKernelGGL((k_demap_planes_lm<float, K>), grid, dim3(BLOCK), 0, st, B, h->N, S, d_syms,          \
-                               (const float *)h->cons.buf.p, c, scale, (const int *)h->d_src, (const int *)h->d_off,  \
-                               n_avail, d_planes, n_items);                                                         \
-        break;
-        CASE(1) CASE(2) CASE(3) CASE(4) CASE(5) CASE(6) CASE(7) CASE(8)
-#undef CASE
-    default: return fail(TDEC_EINVAL, "bps must be 1..8");
-    }
-    HIPCHK(hipGetLastError());
-    return mark_used(h, st);
+    return demap_planes<false>(true, h, B, d_syms, S, cons, cons_f64, M, bps, noise_var, nullptr, 0, d_planes, stream);
 }
 
 }  // extern "C"
@@ -2265,8 +2280,7 @@ int tdec_demap_decode_dev(tdec_t *h, int B, const float *d_syms, int S, const vo
     if (waves > h->ws_waves || 2 * (size_t)waves * tile_floats(h->N) * sizeof(float) > h->planes_w.cap)
         return fail(TDEC_ECAPACITY, "workspace too small: call tdec_reserve_fused first");
     hipStream_t st = (hipStream_t)stream;
-    if (int rc = order_on(h, st)) return rc;
-    if (int rc = h->cons.upload(cons, cons_f64, M, bps, cons_f64 != 0, st)) return rc;
+    if (int rc = handle_table(h, cons, cons_f64, M, bps, st)) return rc;
     const FusedDemapArgs fa{d_syms, S, std::min<long>((long)S * bps, h->llr_len), (const int *)h->d_src,
                             (const int *)h->d_off, (float *)h->planes_w.p,
                             demap_cfg(M, div_f32, -1, noise_var, h->cons.sep), h->cons.buf.p};
@@ -2402,131 +2416,35 @@ const void *decode_refill_kernel(int algo, bool ragged) {
 }  // namespace
 
 // ---- per-row noise variance ---------------------------------------------
-// Behind the refill kernels for the same reason: the ROWNV instantiations and
-// k_noise_var are first named here, so they follow every older kernel in the code object.
-namespace {
-template <typename T, typename S>
-int launch_demap_rows(bool lm, int bps, const S *d_syms, long n_sym, const T *d_cons, DemapCfg c, RowNv<true> rn,
-                      double *d_llr, hipStream_t st) {
-    const dim3 grid((unsigned)((n_sym + BLOCK - 1) / BLOCK));
-    switch (bps) {
-#define CASE(K)                                                                                                      \
-    case K:                                                                                                          \
-        if (lm) hipLaunchKernelGGL((k_demap_lm<T, S, K, true>), grid, dim3(BLOCK), 0, st, d_syms, n_sym, d_cons, c,  \
-                                   0.0, d_llr, rn);                                                                  \
-        else hipLaunchKernelGGL((k_demap<T, S, K, true>), grid, dim3(BLOCK), 0, st, d_syms, n_sym, d_cons, c, d_llr, \
-                                rn);                                                                                 \
-        break;
-        CASE(1) CASE(2) CASE(3) CASE(4) CASE(5) CASE(6) CASE(7) CASE(8)
-#undef CASE
-    default: return fail(TDEC_EINVAL, "bps must be 1..8");
-    }
-    HIPCHK(hipGetLastError());
-    return 0;
-}
-
-// tdec_demap_dev / tdec_demap_logmap_dev over [B][S] symbols with noise_var[row] (c.nv is the kernels' to fill)
-int demap_rows_dev(bool lm, int device, const void *d_syms, int sym_f64, int B, int S, const void *cons, int cons_f64,
-                   int M, int bps, const double *d_nv, int div_f32, int sign, double *d_llr, void *stream) {
-    if (!d_syms || !cons || !d_llr || !d_nv || B < 0 || S < 0) return fail(TDEC_EINVAL, "bad demap arguments");
-    if (int rc = check_demap_args(M, bps)) return rc;
-    if (B == 0 || S == 0) return 0;
-    Guard g(device);
-    const bool f64 = sym_f64 || cons_f64;
-    hipStream_t st = (hipStream_t)stream;
-    ConsCache *cc = nullptr;
-    if (int rc = cached_table(device, cons, cons_f64, M, bps, f64, st, &cc)) return rc;
-    const DemapCfg c = demap_cfg(M, div_f32, sign, 0.0, cc->sep);
-    const RowNv<true> rn{d_nv, S};
-    const long n_sym = (long)B * S;
-    if (f64) {
-        if (sym_f64)
-            return launch_demap_rows<double, double>(lm, bps, (const double *)d_syms, n_sym, (const double *)cc->buf.p, c, rn, d_llr, st);
-        return launch_demap_rows<double, float>(lm, bps, (const float *)d_syms, n_sym, (const double *)cc->buf.p, c, rn, d_llr, st);
-    }
-    return launch_demap_rows<float, float>(lm, bps, (const float *)d_syms, n_sym, (const float *)cc->buf.p, c, rn, d_llr, st);
-}
-
-struct PlanesNv {
-    tdec_t *h;
-    int B, S;
-    const float *d_syms;
-    DemapCfg c;
-    long n_avail, n_items, n_tiles;
-    float *P;
-    DemapDecl dd;
-    RowNv<true> rn;
-    hipStream_t st;
-    bool split, lm;
-};
-
-template <typename TT, int K> void launch_planes_nv(const PlanesNv &a) {
-    tdec_t *h = a.h;
-    const dim3 grid((unsigned)a.n_items);   // one block per item
-    const dim3 fgrid((unsigned)std::max<long>(1, std::min<long>(a.n_tiles, 1024)));
-    const TT *tab = (const TT *)h->cons.buf.p;
-    if (a.lm) {
-        hipLaunchKernelGGL((k_demap_planes_lm<TT, K, true>), grid, dim3(BLOCK), 0, a.st, a.B, h->N, a.S, a.d_syms, tab, a.c,
-                           0.0, (const int *)h->d_src, (const int *)h->d_off, a.n_avail, a.P, a.n_items, a.rn);
-        return;
-    }
-    if constexpr (dm_split(K)) {
-        if (a.split) {
-            hipLaunchKernelGGL((k_demap_planes<TT, K, true, true>), grid, dim3(BLOCK), 0, a.st, a.B, h->N, a.S, a.d_syms,
-                               tab, a.c, (const int *)h->d_src, (const int *)h->d_off, a.n_avail, a.P, a.n_items, a.dd,
-                               a.rn);
-            hipLaunchKernelGGL((k_demap_fix<TT, K, true>), fgrid, dim3(BLOCK), 0, a.st, a.B, h->N, a.S, a.d_syms, tab, a.c,
-                               (const int *)h->d_dst, a.n_avail, a.P, a.dd, a.n_tiles, a.rn);
-            return;
-        }
-    }
-    hipLaunchKernelGGL((k_demap_planes<TT, K, false, true>), grid, dim3(BLOCK), 0, a.st, a.B, h->N, a.S, a.d_syms, tab, a.c,
-                       (const int *)h->d_src, (const int *)h->d_off, a.n_avail, a.P, a.n_items, a.dd, a.rn);
-}
-
-// tdec_demap_planes_dev / tdec_demap_planes_logmap_dev with noise_var[row]: the same
-// ordering, table upload, decline-list sizing and capture rule
-int demap_planes_nv(bool lm, tdec_t *h, int B, const float *d_syms, int S, const void *cons, int cons_f64, int M, int bps,
-                    const double *d_nv, int div_f32, float *d_planes, void *stream) {
-    if (!h || B < 0 || !cons) return fail(TDEC_EINVAL, "bad demap arguments");
-    if (int rc = check_demap_args(M, bps)) return rc;
-    if (B == 0) return 0;
-    if (!d_syms || !d_planes || !d_nv || S <= 0) return fail(TDEC_EINVAL, "bad demap arguments");
-    Guard g(h->device);
-    hipStream_t st = (hipStream_t)stream;
-    if (int rc = order_on(h, st)) return rc;   // the table below may still be read on another stream
-    if (int rc = h->cons.upload(cons, cons_f64, M, bps, cons_f64 != 0, st)) return rc;
-    const int chunks = (h->N + dm_kc(bps) - 1) / dm_kc(bps);
-    PlanesNv a{h, B, S, d_syms, demap_cfg(M, lm ? 0 : div_f32, -1, 0.0, h->cons.sep),
-               std::min<long>((long)S * bps, h->llr_len), (long)n_tiles_of(B) * chunks, n_tiles_of(B), d_planes,
-               DemapDecl{h->d_decl, h->d_decl_n, h->d_decl_ovf, DM_DECL_CAP}, RowNv<true>{d_nv, S}, st,
-               !lm && dm_split_table(bps, h->cons.sep), lm};
-    if (a.split) {   // the decline list: sized by tdec_reserve
-        if (h->decl_tiles < a.n_tiles) {
-            if (capturing(st)) return fail(TDEC_ECAPACITY, "demap batch larger than tdec_reserve() (stream capture)");
-            quiesce(h);
-            if (int rc = ensure_decl(h, a.n_tiles)) return rc;
-        }
-        a.dd = DemapDecl{h->d_decl, h->d_decl_n, h->d_decl_ovf, DM_DECL_CAP};
-        HIPCHK(hipMemsetAsync(h->d_decl_n, 0, sizeof(unsigned), st));
-        HIPCHK(hipMemsetAsync(h->d_decl_ovf, 0, (size_t)a.n_tiles, st));
-    }
-    switch (bps) {
-#define CASE(K)                                    \
-    case K:                                        \
-        if (cons_f64) launch_planes_nv<double, K>(a); \
-        else launch_planes_nv<float, K>(a);        \
-        break;
-        CASE(1) CASE(2) CASE(3) CASE(4) CASE(5) CASE(6) CASE(7) CASE(8)
-#undef CASE
-    default: return fail(TDEC_EINVAL, "bps must be 1..8");
-    }
-    HIPCHK(hipGetLastError());
-    return mark_used(h, st);
-}
-}  // namespace
-
+// Behind the refill kernels for the same reason: the ROWNV instantiations of the demapper
+// entries above and k_noise_var are first named here, in this order, so they follow every
+// older kernel in the code object.
 extern "C" {
+
+int tdec_demap_rows_dev(int device, const void *d_syms, int sym_f64, int B, int S, const void *cons, int cons_f64,
+                        int M, int bps, const double *d_noise_var, int div_f32, int sign, double *d_llr,
+                        void *stream) {
+    return demap_dev<true>(false, device, d_syms, sym_f64, B, S, cons, cons_f64, M, bps, 0.0, d_noise_var, div_f32, sign,
+                           d_llr, stream);
+}
+
+int tdec_demap_rows_logmap_dev(int device, const void *d_syms, int sym_f64, int B, int S, const void *cons,
+                               int cons_f64, int M, int bps, const double *d_noise_var, int sign, double *d_llr,
+                               void *stream) {
+    return demap_dev<true>(true, device, d_syms, sym_f64, B, S, cons, cons_f64, M, bps, 0.0, d_noise_var, 0, sign, d_llr,
+                           stream);
+}
+
+int tdec_demap_planes_nv_dev(tdec_t *h, int B, const float *d_syms, int S, const void *cons, int cons_f64, int M,
+                             int bps, const double *d_noise_var, int div_f32, float *d_planes, void *stream) {
+    return demap_planes<true>(false, h, B, d_syms, S, cons, cons_f64, M, bps, 0.0, d_noise_var, div_f32, d_planes,
+                              stream);
+}
+
+int tdec_demap_planes_logmap_nv_dev(tdec_t *h, int B, const float *d_syms, int S, const void *cons, int cons_f64,
+                                    int M, int bps, const double *d_noise_var, float *d_planes, void *stream) {
+    return demap_planes<true>(true, h, B, d_syms, S, cons, cons_f64, M, bps, 0.0, d_noise_var, 0, d_planes, stream);
+}
 
 int tdec_noise_var_dev(int device, const float *d_syms, int B, int S, const void *cons, int cons_f64, int M,
                        double floor, double *d_nv, void *stream) {
@@ -2548,30 +2466,6 @@ int tdec_noise_var_dev(int device, const float *d_syms, int B, int S, const void
                            (const float *)cc->buf.p, M, floor, d_nv);
     HIPCHK(hipGetLastError());
     return 0;
-}
-
-int tdec_demap_rows_dev(int device, const void *d_syms, int sym_f64, int B, int S, const void *cons, int cons_f64,
-                        int M, int bps, const double *d_noise_var, int div_f32, int sign, double *d_llr,
-                        void *stream) {
-    return demap_rows_dev(false, device, d_syms, sym_f64, B, S, cons, cons_f64, M, bps, d_noise_var, div_f32, sign,
-                          d_llr, stream);
-}
-
-int tdec_demap_rows_logmap_dev(int device, const void *d_syms, int sym_f64, int B, int S, const void *cons,
-                               int cons_f64, int M, int bps, const double *d_noise_var, int sign, double *d_llr,
-                               void *stream) {
-    return demap_rows_dev(true, device, d_syms, sym_f64, B, S, cons, cons_f64, M, bps, d_noise_var, 0, sign, d_llr,
-                          stream);
-}
-
-int tdec_demap_planes_nv_dev(tdec_t *h, int B, const float *d_syms, int S, const void *cons, int cons_f64, int M,
-                             int bps, const double *d_noise_var, int div_f32, float *d_planes, void *stream) {
-    return demap_planes_nv(false, h, B, d_syms, S, cons, cons_f64, M, bps, d_noise_var, div_f32, d_planes, stream);
-}
-
-int tdec_demap_planes_logmap_nv_dev(tdec_t *h, int B, const float *d_syms, int S, const void *cons, int cons_f64,
-                                    int M, int bps, const double *d_noise_var, float *d_planes, void *stream) {
-    return demap_planes_nv(true, h, B, d_syms, S, cons, cons_f64, M, bps, d_noise_var, 0, d_planes, stream);
 }
 
 }  // extern "C"

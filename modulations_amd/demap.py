@@ -217,19 +217,9 @@ def compute_llr_device(syms, mod_type, noise_var, out=None, sign=+1, stream=None
     if out.dtype != torch.float64 or not out.is_contiguous() or out.numel() < n_sym * m['bps'] or out.device != syms.device:
         raise ValueError("out must be a contiguous float64 tensor of n_sym*bps elements on the symbols' device")
     st = _n.stream_ptr(stream) if stream is not None else torch.cuda.current_stream(dev).cuda_stream
-    if rows:
-        B, S = syms.shape
-        if lm:
-            _n.check(_n.lib().tdec_demap_rows_logmap_dev(dev, _n.ptr(syms), int(sym_f64), B, S, _n.ptr(c), int(f64),
-                                                         len(c), m['bps'], _n.ptr(nvt), int(sign), _n.ptr(out), st))
-        else:
-            _n.check(_n.lib().tdec_demap_rows_dev(dev, _n.ptr(syms), int(sym_f64), B, S, _n.ptr(c), int(f64), len(c),
-                                                  m['bps'], _n.ptr(nvt), int(div_f32), int(sign), _n.ptr(out), st))
-        return out
-    if lm:
-        _n.check(_n.lib().tdec_demap_logmap_dev(dev, _n.ptr(syms), int(sym_f64), n_sym, _n.ptr(c), int(f64),
-                                                len(c), m['bps'], nv, int(sign), _n.ptr(out), st))
-    else:
-        _n.check(_n.lib().tdec_demap_dev(dev, _n.ptr(syms), int(sym_f64), n_sym, _n.ptr(c), int(f64),
-                                         len(c), m['bps'], nv, int(div_f32), int(sign), _n.ptr(out), st))
+    # tdec_demap[_rows][_logmap]_dev: (B, S) and the vector for rows, else n_sym and the
+    # scalar; no div_f32 for log-MAP
+    call = getattr(_n.lib(), f"tdec_demap{'_rows' if rows else ''}{'_logmap' if lm else ''}_dev")
+    _n.check(call(dev, _n.ptr(syms), int(sym_f64), *(syms.shape if rows else (n_sym,)), _n.ptr(c), int(f64), len(c),
+                  m['bps'], _n.ptr(nvt) if rows else nv, *(() if lm else (int(div_f32),)), int(sign), _n.ptr(out), st))
     return out

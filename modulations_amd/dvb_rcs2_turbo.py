@@ -433,20 +433,10 @@ class DVBRCS2_Turbo:
         B, S = syms.shape[0], syms.shape[1]
         if planes.numel() * 4 < self.planes_bytes(B):
             raise ValueError("planes buffer smaller than planes_bytes(B)")
-        if rows and lm:
-            self.handle.call("tdec_demap_planes_logmap_nv_dev", B, _n.ptr(syms), S, _n.ptr(cons), int(f64), len(cons),
-                             bps, _n.ptr(noise_var), _n.ptr(planes), self._stream(stream))
-            return planes
-        if rows:
-            self.handle.call("tdec_demap_planes_nv_dev", B, _n.ptr(syms), S, _n.ptr(cons), int(f64), len(cons), bps,
-                             _n.ptr(noise_var), int(div_f32), _n.ptr(planes), self._stream(stream))
-            return planes
-        if lm:
-            self.handle.call("tdec_demap_planes_logmap_dev", B, _n.ptr(syms), S, _n.ptr(cons), int(f64), len(cons),
-                             bps, float(noise_var), _n.ptr(planes), self._stream(stream))
-            return planes
-        self.handle.call("tdec_demap_planes_dev", B, _n.ptr(syms), S, _n.ptr(cons), int(f64), len(cons), bps,
-                         float(noise_var), int(div_f32), _n.ptr(planes), self._stream(stream))
+        # tdec_demap_planes[_logmap][_nv]_dev: the vector for rows, else the scalar; no div_f32 for log-MAP
+        self.handle.call(f"tdec_demap_planes{'_logmap' if lm else ''}{'_nv' if rows else ''}_dev", B, _n.ptr(syms), S,
+                         _n.ptr(cons), int(f64), len(cons), bps, _n.ptr(noise_var) if rows else float(noise_var),
+                         *(() if lm else (int(div_f32),)), _n.ptr(planes), self._stream(stream))
         return planes
 
     # -- fused demap + decode (one launch; tdec_demap_decode_dev) -------------------------
