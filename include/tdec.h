@@ -298,6 +298,51 @@ int tdec_demap_planes_nv_dev(tdec_t *h, int B, const float *d_syms, int S, const
 int tdec_demap_planes_logmap_nv_dev(tdec_t *h, int B, const float *d_syms, int S, const void *cons, int cons_f64,
                                     int M, int bps, const double *d_noise_var, float *d_planes, void *stream);
 
+/* Per-symbol noise variance (flat fading with known gains): a
+ * received sample y = h x + n equalised to z = y / h has the noise variance
+ * nv / |h|^2, so every symbol of a faded burst has its own.  These calls read one
+ * f64 per symbol from a device array d_noise_var[B][S], S the launch's symbols per
+ * row (tdec_equalize_dev below writes it).
+ *
+ * tdec_symnv_demap_dev / _logmap_dev: tdec_demap_rows_dev / _logmap_dev with
+ * symbol (r, s) demapped at noise_var = d_noise_var[r * S + s] (floored at 0.005
+ * on the device); d_llr is f64[B][S * bps].  tdec_symnv_demap_planes_dev /
+ * tdec_symnv_demap_planes_logmap_dev: the same for tdec_demap_planes_dev /
+ * tdec_demap_planes_logmap_dev (same ordering on the handle, table upload and
+ * decline list; after tdec_reserve they neither allocate nor synchronise); the
+ * value belongs to the symbol, so the label bits of a couple that come from two
+ * symbols each take their own symbol's.  The LLRs of symbol (r, s) are, bit for
+ * bit, what the scalar call gives that symbol with noise_var =
+ * d_noise_var[r * S + s]: a NaN value gives that symbol NaN LLRs, +inf what the
+ * scalar call gives at +inf (zero LLRs for a finite symbol: an erasure).
+ * Conventions as the per-row calls: B = 0 is a no-op, null or negative arguments
+ * are TDEC_EINVAL. */
+int tdec_symnv_demap_dev(int device, const void *d_syms, int sym_f64, int B, int S, const void *cons, int cons_f64,
+                        int M, int bps, const double *d_noise_var, int div_f32, int sign, double *d_llr,
+                        void *stream);
+int tdec_symnv_demap_logmap_dev(int device, const void *d_syms, int sym_f64, int B, int S, const void *cons,
+                               int cons_f64, int M, int bps, const double *d_noise_var, int sign, double *d_llr,
+                               void *stream);
+int tdec_symnv_demap_planes_dev(tdec_t *h, int B, const float *d_syms, int S, const void *cons, int cons_f64, int M,
+                              int bps, const double *d_noise_var, int div_f32, float *d_planes, void *stream);
+int tdec_symnv_demap_planes_logmap_dev(tdec_t *h, int B, const float *d_syms, int S, const void *cons, int cons_f64,
+                                     int M, int bps, const double *d_noise_var, float *d_planes, void *stream);
+
+/* The equaliser in front of them (build-defined).  d_y: received
+ * symbols, complex64 [B][S]; d_h: channel gains, complex64 [B][ceil(S / coh)],
+ * coh >= 1: symbol s of row r uses h[r][s / coh] (coh = 1: per-symbol gains,
+ * coh >= S: one gain per burst).  Noise variance of y: d_noise_var[r] (f64 [B] on
+ * the device, tdec_noise_var_dev's output or the caller's) when d_noise_var is not
+ * null, else the host value noise_var.  Outputs d_z complex64 [B][S] and d_nv_sym
+ * f64 [B][S].  All in f64 without contraction:
+ *   g = hr*hr + hi*hi,  z = ((float)((yr*hr + yi*hi) / g), (float)((yi*hr - yr*hi) / g)),
+ *   nv_sym = nv_r / g   (no floor: the demapper floors)
+ * and where g == 0 or g is not finite the symbol is an erasure: z = 0 + 0j,
+ * nv_sym = +inf.  B = 0 or S = 0 is a no-op; null pointers, negative sizes and
+ * coh < 1 are TDEC_EINVAL. */
+int tdec_equalize_dev(int device, const float *d_y, const float *d_h, int B, int S, int coh, double noise_var,
+                      const double *d_noise_var, float *d_z, double *d_nv_sym, void *stream);
+
 /* Fused soft demap + turbo decode (one launch): what tdec_demap_planes_dev +
  * tdec_decode_planes_dev compute, bit for bit, with each persistent decoder wave
  * demapping its own next tile into a per-wave plane buffer.  Instantiated for
@@ -342,6 +387,17 @@ long tdec_encode_host(int n_couples, int period, const uint8_t *punct, const int
  * complex64 [B][ceil(n_out / bps)]; d_info (nullable): uint8 [B][2N]. */
 int tdec_workload_dev(tdec_t *h, int B, int64_t cw0, uint64_t seed, const float *cons_iq, int M, int bps,
                       double sigma, float *d_syms, uint8_t *d_info, void *stream);
+/* The same over a flat-fading channel: each symbol is h x + n, with
+ * the info bits and the noise tdec_workload_dev draws for the same (seed, cw0 + c, s),
+ * and the gains are written to d_h, complex64 [B][ceil(S / coh)], S = ceil(n_out / bps):
+ * gain block j of a codeword covers its symbols [j * coh, (j + 1) * coh), coh >= 1.
+ *   h = sqrt(K / (K + 1)) + sqrt(1 / (K + 1)) * w,  w ~ CN(0, 1)
+ * for the Rician factor K = rician_k >= 0 (0: Rayleigh), w by Box-Muller on
+ * philox4x32_10({g_lo, g_hi, j/2, 0x3C5D}, seed) with the noise's uniform mapping,
+ * 1/2 variance per dimension.  A codeword's gains depend only on its global index. */
+int tdec_workload_fading_dev(tdec_t *h, int B, int64_t cw0, uint64_t seed, const float *cons_iq, int M, int bps,
+                             double sigma, double rician_k, int coh, float *d_syms, float *d_h, uint8_t *d_info,
+                             void *stream);
 /* The info bits alone: uint8 [B][2N] of 0/1. */
 int tdec_info_bits_dev(tdec_t *h, int B, int64_t cw0, uint64_t seed, uint8_t *d_info, void *stream);
 /* Bit errors per codeword of decoded rows (int32 [B][2N], tdec_decode_*) against

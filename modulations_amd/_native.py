@@ -39,6 +39,8 @@ EXPORTS = (
     "tdec_demap_logmap_dev", "tdec_demap_logmap", "tdec_demap_planes_logmap_dev",
     "tdec_noise_var_dev", "tdec_demap_rows_dev", "tdec_demap_rows_logmap_dev", "tdec_demap_planes_nv_dev",
     "tdec_demap_planes_logmap_nv_dev",
+    "tdec_symnv_demap_dev", "tdec_symnv_demap_logmap_dev", "tdec_symnv_demap_planes_dev",
+    "tdec_symnv_demap_planes_logmap_dev", "tdec_equalize_dev", "tdec_workload_fading_dev",
 )
 
 _lib = None
@@ -129,6 +131,17 @@ def _declare(L):
                                                       _vp, _vp, _vp]
         for f in (L.tdec_noise_var_dev, L.tdec_demap_rows_dev, L.tdec_demap_rows_logmap_dev,
                   L.tdec_demap_planes_nv_dev, L.tdec_demap_planes_logmap_nv_dev):
+            f.restype = C.c_int
+    if hasattr(L, "tdec_equalize_dev"):   # (A/B tools also load older builds without the per-symbol noise variance)
+        L.tdec_symnv_demap_dev.argtypes = L.tdec_demap_rows_dev.argtypes
+        L.tdec_symnv_demap_logmap_dev.argtypes = L.tdec_demap_rows_logmap_dev.argtypes
+        L.tdec_symnv_demap_planes_dev.argtypes = L.tdec_demap_planes_nv_dev.argtypes
+        L.tdec_symnv_demap_planes_logmap_dev.argtypes = L.tdec_demap_planes_logmap_nv_dev.argtypes
+        L.tdec_equalize_dev.argtypes = [C.c_int, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_double, _vp, _vp, _vp, _vp]
+        L.tdec_workload_fading_dev.argtypes = [_vp, C.c_int, C.c_int64, C.c_uint64, _vp, C.c_int, C.c_int, C.c_double,
+                                               C.c_double, C.c_int, _vp, _vp, _vp, _vp]
+        for f in (L.tdec_symnv_demap_dev, L.tdec_symnv_demap_logmap_dev, L.tdec_symnv_demap_planes_dev,
+                  L.tdec_symnv_demap_planes_logmap_dev, L.tdec_equalize_dev, L.tdec_workload_fading_dev):
             f.restype = C.c_int
     L.tdec_encode_dev.argtypes = [_vp, C.c_int, _vp, _vp, _vp]
     L.tdec_demap_batch.argtypes = [C.c_int, C.c_int, C.c_int, _vp, C.c_long, C.c_float, _vp]

@@ -15,9 +15,15 @@ only those int64 counters are all-reduced.  Finished points are written to
 §5).  The file records the sweep's configuration and the generator version;
 a rerun into it with any other configuration (modulation, block size, rate,
 algorithm, iterations, interleaver, codewords per point, base seed, early
-stop and its decoder, demapper) or generator is refused instead of mixing two data streams, and each point's
+stop and its decoder, demapper, channel) or generator is refused instead of mixing two data streams, and each point's
 generator key is derived from its Eb/N0 value (not its index in --ebn0), so a
 resumed sweep over a different grid regenerates exactly the same data.
+
+--channel rayleigh | rician (with --rician-k, --coherence) sweeps a flat-fading
+channel with known gains: the generator multiplies each symbol by
+its gain (E|h|^2 = 1, one gain per --coherence symbols of a codeword), and the
+pipeline equalises and demaps with the per-symbol noise variance N0 / |h|^2.  The
+bits and the noise are those of the AWGN sweep with the same seed.
 """
 from __future__ import annotations
 
@@ -53,9 +59,23 @@ def sweep_config(a, inv_perm=None):
             cfg["es_decoder"] = a.es_decoder
     if getattr(a, "demap", "max-log") != "max-log":   # (absent at the default, for the same reason)
         cfg["demap"] = a.demap
+    fading = channel_fading(a)
+    if fading is not None:   # (absent for awgn, for the same reason)
+        cfg["channel"] = a.channel
+        cfg["rician_k"] = fading["K"]
+        cfg["coherence"] = fading["coh"]
     if inv_perm is not None:
         cfg["inv_perm_digest"] = interleaver_digest(inv_perm)
     return cfg
+
+
+def channel_fading(a):
+    """workload.make_symbols' `fading` for the sweep's --channel (None: awgn).  rayleigh is
+    rician with K = 0, whatever --rician-k says."""
+    channel = getattr(a, "channel", "awgn")
+    if channel == "awgn":
+        return None
+    return {"K": float(a.rician_k) if channel == "rician" else 0.0, "coh": int(a.coherence)}
 
 
 def load_resume(path, cfg):
@@ -90,7 +110,7 @@ def parse_points(spec):
     return [float(x) for x in spec.split(",")]
 
 
-def run_point(pipe, codec, mod, ebn0, start, count, batch, seed, device, times=None, iter_hist=None):
+def run_point(pipe, codec, mod, ebn0, start, count, batch, seed, device, times=None, iter_hist=None, fading=None):
     """Bit errors, frame errors and codewords of global codewords
     [start, start + count) at one Eb/N0 point.  The data of codeword g is a
     counter-based stream of (seed, g) (workload.make_symbols), so the counters
@@ -98,17 +118,25 @@ def run_point(pipe, codec, mod, ebn0, start, count, batch, seed, device, times=N
     optional): per batch, (demap + decode ms, decode ms) from HIP events on the
     pipeline's stream -- the bench's timed step, without the generator and the
     error counting.  iter_hist (an int64 [iterations + 1] device tensor, optional;
-    early-stop pipelines): entry i gains the codewords that ran i iterations."""
+    early-stop pipelines): entry i gains the codewords that ran i iterations.
+    fading (make_symbols' dict, optional): the flat-fading channel; the pipeline (built
+    with csi=True) equalises with the generator's gains."""
     import torch
     from . import sharding as S
     from .workload import count_errors, make_symbols
     cnt = torch.zeros(3, dtype=torch.int64, device=device)
     ev = []
     for off, n in S.batches(count, batch):
-        _, syms, n0 = make_symbols(codec, n, mod, ebn0, seed, device, cw0=start + off, want_info=False)
+        csi = {}
+        if fading is None:
+            _, syms, n0 = make_symbols(codec, n, mod, ebn0, seed, device, cw0=start + off, want_info=False)
+        else:
+            _, syms, n0, gains = make_symbols(codec, n, mod, ebn0, seed, device, cw0=start + off, want_info=False,
+                                              fading=fading)
+            csi = {"csi": gains, "coh": fading["coh"]}
         e3 = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
         e3[0].record()
-        bits = pipe.run(syms, n0, events=e3[1:])[:n]
+        bits = pipe.run(syms, n0, events=e3[1:], **csi)[:n]
         ev.append(e3)
         e = count_errors(codec, bits, seed, cw0=start + off)
         if iter_hist is not None:
@@ -141,6 +169,13 @@ def arg_parser():
     ap.add_argument("--demap", choices=["max-log", "log-map"], default="max-log",
                     help="the soft demapper in front of the decoder: the reference's max-log, or the exact "
                          "log-sum it approximates")
+    ap.add_argument("--channel", choices=["awgn", "rayleigh", "rician"], default="awgn",
+                    help="awgn, or flat fading with known gains (E|h|^2 = 1): equalised, then demapped with "
+                         "the per-symbol noise variance N0 / |h|^2")
+    ap.add_argument("--rician-k", type=float, default=4.0, help="--channel rician: the K factor (linear, >= 0)")
+    ap.add_argument("--coherence", type=int, default=1,
+                    help="fading channels: symbols per gain (1: fast fading; >= the symbols of a codeword: "
+                         "one gain per burst)")
     ap.add_argument("--out", default=None)
     ap.add_argument("--dist-backend", default="nccl", help="nccl (= RCCL) on the node; gloo to rehearse")
     ap.add_argument("--all-on-device0", action="store_true", help="every rank on GPU 0 (rehearsal on a 1-GPU box)")
@@ -157,6 +192,9 @@ def main(argv=None):
 
     ap = arg_parser()
     a = ap.parse_args(argv)
+    if a.coherence < 1 or not (0.0 <= a.rician_k < float("inf")):
+        ap.error("--coherence must be >= 1 and --rician-k a finite value >= 0")
+    fading = channel_fading(a)
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -188,11 +226,11 @@ def main(argv=None):
                             device=device.index, early_stop=a.early_stop, es_decoder=a.es_decoder)
     if world > 1:   # every rank must decode with the same de-interleaver
         S.check_same_interleaver(codec.inv_perm, dist, device if a.dist_backend == "nccl" else "cpu")
-    pipe = DevicePipeline(codec, a.mod, a.batch, device, demap=a.demap)
+    pipe = DevicePipeline(codec, a.mod, a.batch, device, demap=a.demap, csi=fading is not None)
     results = list(done.values())
     # one untimed batch first: code-object loading and first-launch costs stay out of
     # the first point's figures
-    run_point(pipe, codec, a.mod, 2.0, 0, min(a.batch, 65536), a.batch, a.seed, device)
+    run_point(pipe, codec, a.mod, 2.0, 0, min(a.batch, 65536), a.batch, a.seed, device, fading=fading)
     for e in parse_points(a.ebn0):
         if e in done:
             continue
@@ -200,7 +238,8 @@ def main(argv=None):
         t0 = time.time()
         times = []
         hist = torch.zeros(a.iterations + 1, dtype=torch.int64, device=device) if a.early_stop else None
-        cnt = run_point(pipe, codec, a.mod, e, start, count, a.batch, ebn0_seed(a.seed, e), device, times, hist)
+        cnt = run_point(pipe, codec, a.mod, e, start, count, a.batch, ebn0_seed(a.seed, e), device, times, hist,
+                        fading=fading)
         if hist is not None:
             cnt = torch.cat([cnt, hist])   # one reduction for the error counters and the histogram
         if world > 1 and a.dist_backend != "nccl":
@@ -219,6 +258,8 @@ def main(argv=None):
                "decode_codewords_per_s": count / max(1e-9, sum(t[1] for t in times) * 1e-3)}
         if a.demap != "max-log":
             rec["demap"] = a.demap
+        if fading is not None:
+            rec.update(channel=a.channel, rician_k=fading["K"], coherence=fading["coh"])
         if a.early_stop:
             h = [int(x) for x in cnt[3:].tolist()]
             rec["early_stop"] = True

@@ -1888,9 +1888,10 @@ int tdec_siso_batch_f64(tdec_t *h, int B, const double *LcA, const double *LcB, 
 }  // extern "C"
 
 // ---- demapper entry points ------------------------------------------
-// Templates on ROWNV (noise_var per launch, or noise_var[row] read on the device).  Kernel
-// templates are emitted in the order this file first names them; the ROWNV = true
-// instantiations are first named at the end of this file.
+// Templates on ROWNV (0: noise_var per launch; 1: noise_var[row], 2: noise_var[row][symbol],
+// read on the device).  Kernel templates are emitted in the order this file first names
+// them; the ROWNV = 1 and then the ROWNV = 2 instantiations are first named at the end of
+// this file.
 namespace {
 
 // The handle-less calls' device table (the caller holds the device's Guard)
@@ -1923,7 +1924,7 @@ int cached_table(int device, const void *cons, int cons_f64, int M, int bps, boo
 
 // k_demap / k_demap_lm (lm) over n_sym symbols.  With ROWNV the kernels form each row's
 // configuration from rn, and the launch's log-MAP scale is not read: 0.0
-template <typename T, typename S, bool ROWNV>
+template <typename T, typename S, int ROWNV>
 int launch_demap(bool lm, int bps, const S *d_syms, long n_sym, const T *d_cons, DemapCfg c, RowNv<ROWNV> rn,
                  double *d_llr, hipStream_t st) {
     const dim3 grid((unsigned)((n_sym + BLOCK - 1) / BLOCK));
@@ -1945,9 +1946,9 @@ int launch_demap(bool lm, int bps, const S *d_syms, long n_sym, const T *d_cons,
 }
 
 // The flat demappers' entry over [B][S] symbols: B = 1 and noise_var for the scalar calls,
-// d_nv[row] with ROWNV (c.nv is then the kernels' to fill).  lm: the log-MAP kernels;
+// d_nv[row] or d_nv[row][symbol] with ROWNV (c.nv is then the kernels' to fill).  lm: the log-MAP kernels;
 // div_f32 is the max-log path's alone
-template <bool ROWNV>
+template <int ROWNV>
 int demap_dev(bool lm, int device, const void *d_syms, int sym_f64, long B, long S, const void *cons, int cons_f64,
               int M, int bps, double noise_var, const double *d_nv, int div_f32, int sign, double *d_llr,
               void *stream) {
@@ -1988,7 +1989,7 @@ int demap_host(bool lm, int device, const void *syms, int sym_f64, long n_sym, c
     HIPCHK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
     int rc = 0;
     if (hipMemcpyAsync(ds, syms, ns, hipMemcpyHostToDevice, st) != hipSuccess) rc = fail(TDEC_EHIP, "memcpy");
-    if (!rc) rc = demap_dev<false>(lm, device, ds, sym_f64, 1, n_sym, cons, cons_f64, M, bps, noise_var, nullptr,
+    if (!rc) rc = demap_dev<0>(lm, device, ds, sym_f64, 1, n_sym, cons, cons_f64, M, bps, noise_var, nullptr,
                                    div_f32, sign, (double *)dl, st);
     if (!rc && hipMemcpyAsync(llr, dl, nl, hipMemcpyDeviceToHost, st) != hipSuccess) rc = fail(TDEC_EHIP, "memcpy");
     if (!rc && hipStreamSynchronize(st) != hipSuccess) rc = fail(TDEC_EHIP, "demap failed");
@@ -2007,7 +2008,7 @@ int handle_table(tdec_t *h, const void *cons, int cons_f64, int M, int bps, hipS
 
 // One plane-demapper launch over (64-codeword tile, dm_kc-couple chunk) items, a block each:
 // k_demap_planes_lm (lm), k_demap_planes<SPLIT> + k_demap_fix (split tables) or k_demap_planes
-template <typename TT, int K, bool ROWNV>
+template <typename TT, int K, int ROWNV>
 void launch_planes(bool lm, bool split, tdec_t *h, int B, int S, const float *d_syms, DemapCfg c, float *P,
                    RowNv<ROWNV> rn, hipStream_t st) {
     const long n_avail = std::min<long>((long)S * K, h->llr_len);   // LLRs the symbols provide
@@ -2034,9 +2035,9 @@ void launch_planes(bool lm, bool split, tdec_t *h, int B, int S, const float *d_
                        off, n_avail, P, n_items, dd, rn);
 }
 
-// The plane demappers' entry: noise_var, or d_nv[row] with ROWNV (c.nv is then the kernels'
+// The plane demappers' entry: noise_var, or d_nv[row] / d_nv[row][symbol] with ROWNV (c.nv is then the kernels'
 // to fill).  lm: the log-MAP kernels, which have no div_f32 and no decline list
-template <bool ROWNV>
+template <int ROWNV>
 int demap_planes(bool lm, tdec_t *h, int B, const float *d_syms, int S, const void *cons, int cons_f64, int M, int bps,
                  double noise_var, const double *d_nv, int div_f32, float *d_planes, void *stream) {
     if (!h || B < 0 || !cons) return fail(TDEC_EINVAL, "bad demap arguments");
@@ -2096,13 +2097,13 @@ extern "C" {
 
 int tdec_demap_dev(int device, const void *d_syms, int sym_f64, long n_sym, const void *cons, int cons_f64, int M,
                    int bps, double noise_var, int div_f32, int sign, double *d_llr, void *stream) {
-    return demap_dev<false>(false, device, d_syms, sym_f64, 1, n_sym, cons, cons_f64, M, bps, noise_var, nullptr,
+    return demap_dev<0>(false, device, d_syms, sym_f64, 1, n_sym, cons, cons_f64, M, bps, noise_var, nullptr,
                             div_f32, sign, d_llr, stream);
 }
 
 int tdec_demap_logmap_dev(int device, const void *d_syms, int sym_f64, long n_sym, const void *cons, int cons_f64,
                           int M, int bps, double noise_var, int sign, double *d_llr, void *stream) {
-    return demap_dev<false>(true, device, d_syms, sym_f64, 1, n_sym, cons, cons_f64, M, bps, noise_var, nullptr, 0,
+    return demap_dev<0>(true, device, d_syms, sym_f64, 1, n_sym, cons, cons_f64, M, bps, noise_var, nullptr, 0,
                             sign, d_llr, stream);
 }
 
@@ -2157,13 +2158,13 @@ int tdec_selftest_trans(int device, int which, uint32_t lo_bits, long long n, fl
 
 int tdec_demap_planes_dev(tdec_t *h, int B, const float *d_syms, int S, const void *cons, int cons_f64, int M,
                           int bps, double noise_var, int div_f32, float *d_planes, void *stream) {
-    return demap_planes<false>(false, h, B, d_syms, S, cons, cons_f64, M, bps, noise_var, nullptr, div_f32, d_planes,
+    return demap_planes<0>(false, h, B, d_syms, S, cons, cons_f64, M, bps, noise_var, nullptr, div_f32, d_planes,
                                stream);
 }
 
 int tdec_demap_planes_logmap_dev(tdec_t *h, int B, const float *d_syms, int S, const void *cons, int cons_f64, int M,
                                  int bps, double noise_var, float *d_planes, void *stream) {
-    return demap_planes<false>(true, h, B, d_syms, S, cons, cons_f64, M, bps, noise_var, nullptr, 0, d_planes, stream);
+    return demap_planes<0>(true, h, B, d_syms, S, cons, cons_f64, M, bps, noise_var, nullptr, 0, d_planes, stream);
 }
 
 }  // extern "C"
@@ -2424,26 +2425,26 @@ extern "C" {
 int tdec_demap_rows_dev(int device, const void *d_syms, int sym_f64, int B, int S, const void *cons, int cons_f64,
                         int M, int bps, const double *d_noise_var, int div_f32, int sign, double *d_llr,
                         void *stream) {
-    return demap_dev<true>(false, device, d_syms, sym_f64, B, S, cons, cons_f64, M, bps, 0.0, d_noise_var, div_f32, sign,
+    return demap_dev<1>(false, device, d_syms, sym_f64, B, S, cons, cons_f64, M, bps, 0.0, d_noise_var, div_f32, sign,
                            d_llr, stream);
 }
 
 int tdec_demap_rows_logmap_dev(int device, const void *d_syms, int sym_f64, int B, int S, const void *cons,
                                int cons_f64, int M, int bps, const double *d_noise_var, int sign, double *d_llr,
                                void *stream) {
-    return demap_dev<true>(true, device, d_syms, sym_f64, B, S, cons, cons_f64, M, bps, 0.0, d_noise_var, 0, sign, d_llr,
+    return demap_dev<1>(true, device, d_syms, sym_f64, B, S, cons, cons_f64, M, bps, 0.0, d_noise_var, 0, sign, d_llr,
                            stream);
 }
 
 int tdec_demap_planes_nv_dev(tdec_t *h, int B, const float *d_syms, int S, const void *cons, int cons_f64, int M,
                              int bps, const double *d_noise_var, int div_f32, float *d_planes, void *stream) {
-    return demap_planes<true>(false, h, B, d_syms, S, cons, cons_f64, M, bps, 0.0, d_noise_var, div_f32, d_planes,
+    return demap_planes<1>(false, h, B, d_syms, S, cons, cons_f64, M, bps, 0.0, d_noise_var, div_f32, d_planes,
                               stream);
 }
 
 int tdec_demap_planes_logmap_nv_dev(tdec_t *h, int B, const float *d_syms, int S, const void *cons, int cons_f64,
                                     int M, int bps, const double *d_noise_var, float *d_planes, void *stream) {
-    return demap_planes<true>(true, h, B, d_syms, S, cons, cons_f64, M, bps, 0.0, d_noise_var, 0, d_planes, stream);
+    return demap_planes<1>(true, h, B, d_syms, S, cons, cons_f64, M, bps, 0.0, d_noise_var, 0, d_planes, stream);
 }
 
 int tdec_noise_var_dev(int device, const float *d_syms, int B, int S, const void *cons, int cons_f64, int M,
@@ -2464,6 +2465,101 @@ int tdec_noise_var_dev(int device, const float *d_syms, int B, int S, const void
     else
         hipLaunchKernelGGL(k_noise_var<float>, dim3((unsigned)B), dim3(BLOCK), 0, st, d_syms, S,
                            (const float *)cc->buf.p, M, floor, d_nv);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+}  // extern "C"
+
+// ---- flat fading: per-symbol noise variance, equaliser, generator --------
+// Behind the per-row entries for the same reason: the ROWNV = 2 instantiations of the
+// demapper entries and k_equalize are first named here, in this order.
+namespace {
+template <bool NVROWS>
+void launch_equalize(bool vec, const float2 *y, const float2 *hh, long n_sym, int S, int coh, int nh, double nv,
+                     const double *nvs, float2 *z, double *nv_sym, hipStream_t st) {
+    if (vec) {
+        const long n_thr = (n_sym + 1) / 2;
+        hipLaunchKernelGGL((k_equalize<NVROWS, true>), dim3((unsigned)((n_thr + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, st, y,
+                           hh, n_sym, S, coh, nh, nv, nvs, z, nv_sym);
+    } else {
+        hipLaunchKernelGGL((k_equalize<NVROWS, false>), dim3((unsigned)((n_sym + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, st,
+                           y, hh, n_sym, S, coh, nh, nv, nvs, z, nv_sym);
+    }
+}
+}  // namespace
+
+extern "C" {
+
+int tdec_symnv_demap_dev(int device, const void *d_syms, int sym_f64, int B, int S, const void *cons, int cons_f64,
+                        int M, int bps, const double *d_noise_var, int div_f32, int sign, double *d_llr,
+                        void *stream) {
+    return demap_dev<2>(false, device, d_syms, sym_f64, B, S, cons, cons_f64, M, bps, 0.0, d_noise_var, div_f32, sign,
+                        d_llr, stream);
+}
+
+int tdec_symnv_demap_logmap_dev(int device, const void *d_syms, int sym_f64, int B, int S, const void *cons,
+                               int cons_f64, int M, int bps, const double *d_noise_var, int sign, double *d_llr,
+                               void *stream) {
+    return demap_dev<2>(true, device, d_syms, sym_f64, B, S, cons, cons_f64, M, bps, 0.0, d_noise_var, 0, sign, d_llr,
+                        stream);
+}
+
+int tdec_symnv_demap_planes_dev(tdec_t *h, int B, const float *d_syms, int S, const void *cons, int cons_f64, int M,
+                              int bps, const double *d_noise_var, int div_f32, float *d_planes, void *stream) {
+    return demap_planes<2>(false, h, B, d_syms, S, cons, cons_f64, M, bps, 0.0, d_noise_var, div_f32, d_planes, stream);
+}
+
+int tdec_symnv_demap_planes_logmap_dev(tdec_t *h, int B, const float *d_syms, int S, const void *cons, int cons_f64,
+                                     int M, int bps, const double *d_noise_var, float *d_planes, void *stream) {
+    return demap_planes<2>(true, h, B, d_syms, S, cons, cons_f64, M, bps, 0.0, d_noise_var, 0, d_planes, stream);
+}
+
+int tdec_equalize_dev(int device, const float *d_y, const float *d_h, int B, int S, int coh, double noise_var,
+                      const double *d_noise_var, float *d_z, double *d_nv_sym, void *stream) {
+    if (B < 0 || S < 0 || coh < 1) return fail(TDEC_EINVAL, "bad equalize arguments");
+    if (B == 0 || S == 0) return 0;
+    if (!d_y || !d_h || !d_z || !d_nv_sym) return fail(TDEC_EINVAL, "bad equalize arguments");
+    Guard g(device);
+    const long n_sym = (long)B * S;
+    const int nh = (S + coh - 1) / coh;
+    // 16-byte accesses where y, z and nv_sym all allow them
+    const bool vec = (((uintptr_t)d_y | (uintptr_t)d_z | (uintptr_t)d_nv_sym) & 15) == 0;
+    const float2 *y = reinterpret_cast<const float2 *>(d_y), *hh = reinterpret_cast<const float2 *>(d_h);
+    float2 *z = reinterpret_cast<float2 *>(d_z);
+    if (d_noise_var) launch_equalize<true>(vec, y, hh, n_sym, S, coh, nh, 0.0, d_noise_var, z, d_nv_sym, (hipStream_t)stream);
+    else launch_equalize<false>(vec, y, hh, n_sym, S, coh, nh, noise_var, nullptr, z, d_nv_sym, (hipStream_t)stream);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+int tdec_workload_fading_dev(tdec_t *h, int B, int64_t cw0, uint64_t seed, const float *cons_iq, int M, int bps,
+                             double sigma, double rician_k, int coh, float *d_syms, float *d_h, uint8_t *d_info,
+                             void *stream) {
+    if (!h || B < 0 || cw0 < 0) return fail(TDEC_EINVAL, "bad workload arguments");
+    if (B == 0) return 0;
+    if (!cons_iq || !d_syms || !d_h || bps < 1 || bps > 8 || M != (1 << bps) || !(sigma >= 0.0) || coh < 1 ||
+        !(rician_k >= 0.0) || !(rician_k < INFINITY))
+        return fail(TDEC_EINVAL, "bad workload arguments (the constellation must have 2^bps points; K >= 0, coh >= 1)");
+    if (!staged_encoder_ok(h)) return fail(TDEC_EINVAL, "workload generation needs N % 4 == 0 and N <= 1024");
+    Guard g(h->device);
+    WorkloadArgs a = workload_args(h, B);
+    a.bps = bps;
+    a.M = M;
+    a.S = (int)((h->enc_len + bps - 1) / bps);
+    a.cw0 = (uint64_t)cw0;
+    a.seed = seed;
+    a.sigma = (float)sigma;
+    for (int m = 0; m < M; ++m) a.cons[m] = make_float2(cons_iq[2 * m], cons_iq[2 * m + 1]);
+    a.info_out = d_info;
+    a.syms = reinterpret_cast<float2 *>(d_syms);
+    FadeArgs f{};
+    f.h = reinterpret_cast<float2 *>(d_h);
+    f.coh = coh;
+    f.nh = (a.S + coh - 1) / coh;
+    f.los = (float)std::sqrt(rician_k / (rician_k + 1.0));
+    f.scat = (float)std::sqrt(1.0 / (rician_k + 1.0));
+    hipLaunchKernelGGL(k_workload_fading, dim3((unsigned)n_tiles_of(B)), dim3(64), 0, (hipStream_t)stream, a, f);
     HIPCHK(hipGetLastError());
     return 0;
 }

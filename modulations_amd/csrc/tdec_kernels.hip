@@ -2058,16 +2058,27 @@ struct DemapCfg {
     int nv_fast;               // nv in [2^-8, 2^16]: the unscaled f32 / f64 division (dm_fast)
 };
 __host__ __device__ inline int dm_nv_fast(double nv) { return nv >= 0x1p-8 && nv <= 0x1p16; }
-// Per-row noise variance (ROWNV): the demap kernels' last argument.
-// Empty for the scalar kernels, whose DemapCfg carries the launch's one value; with
-// ROWNV a device vector, one value per row of [B][S] symbols, from which each thread
-// forms its symbol's configuration with the host's own expressions (demap_cfg /
-// demap_lm_scale, tdec_api.hip), so row r is row r of the scalar launch with nvs[r].
-template <bool ROWNV> struct RowNv {};
-template <> struct RowNv<true> {
+// Per-row and per-symbol noise variance (ROWNV): the demap kernels'
+// last argument.  ROWNV 0: empty, the scalar kernels, whose DemapCfg carries the launch's
+// one value; 1: a device vector, one value per row of [B][S] symbols; 2: a device array,
+// one value per symbol.  Each thread forms its symbol's configuration from it with the
+// host's own expressions (demap_cfg / demap_lm_scale, tdec_api.hip), so row r (symbol
+// (r, s)) is what the scalar launch gives it with nvs[r] (nvs[r * S + s]).
+template <int ROWNV> struct RowNv {};
+template <> struct RowNv<1> {
     const double *nvs;         // device, [B]
     long S;                    // symbols per row (the flat kernels' row = symbol / S)
 };
+template <> struct RowNv<2> {
+    const double *nvs;         // device, [B][S]
+    long S;                    // symbols per row
+};
+// the value of flat symbol s (the flat kernels: row s / S, symbol s % S)
+__device__ __forceinline__ double flat_nv(const RowNv<1> &rn, long s) { return rn.nvs[s / rn.S]; }
+__device__ __forceinline__ double flat_nv(const RowNv<2> &rn, long s) { return rn.nvs[s]; }
+// the value of symbol s of codeword cw (k_demap_fix)
+__device__ __forceinline__ double sym_nv(const RowNv<1> &rn, long cw, long) { return rn.nvs[cw]; }
+__device__ __forceinline__ double sym_nv(const RowNv<2> &rn, long cw, long s) { return rn.nvs[cw * rn.S + s]; }
 __device__ __forceinline__ DemapCfg row_cfg(const DemapCfg &c, double x) {
     DemapCfg r = c;
     r.nv = (0.005 > x) ? 0.005 : x;   // a NaN x stays NaN, as on the host
@@ -2706,7 +2717,7 @@ template <typename T, int BPS> __device__ __forceinline__ void load_table(T *con
     for (int i = threadIdx.x; i < n; i += BLOCK) cons[i] = cons_g[i];
 }
 
-template <typename T, typename S, int BPS, bool ROWNV = false>
+template <typename T, typename S, int BPS, int ROWNV = 0>
 __global__ __launch_bounds__(BLOCK) void k_demap(const S *syms, long n_sym, const T *cons_g, DemapCfg c, double *llr,
                                                 RowNv<ROWNV> rn = {}) {
     __shared__ T cons[DM_TAB];
@@ -2716,7 +2727,7 @@ __global__ __launch_bounds__(BLOCK) void k_demap(const S *syms, long n_sym, cons
     if (s >= n_sym) return;
     double v[BPS];
     if constexpr (ROWNV) {
-        demap_sym<T, BPS>((T)syms[2 * s], (T)syms[2 * s + 1], cons, row_cfg(c, rn.nvs[s / rn.S]), v);
+        demap_sym<T, BPS>((T)syms[2 * s], (T)syms[2 * s + 1], cons, row_cfg(c, flat_nv(rn, s)), v);
     } else {
         demap_sym<T, BPS>((T)syms[2 * s], (T)syms[2 * s + 1], cons, c, v);
     }
@@ -2879,19 +2890,23 @@ __device__ __forceinline__ double *row_nv_tile() {
 }
 // stage the tile's values (before the item's first symbol; the item's closing barrier
 // orders the next item's staging after this item's reads)
-__device__ __forceinline__ void row_nv_stage(const RowNv<true> &rn, long tile, int B) {
+__device__ __forceinline__ void row_nv_stage(const RowNv<1> &rn, long tile, int B) {
     if constexpr (DM_ROWNV_LDS) {
         const long cw = tile * WAVE + threadIdx.x;
         if (threadIdx.x < WAVE) row_nv_tile()[threadIdx.x] = cw < B ? rn.nvs[cw] : 0.0;
         __syncthreads();
     }
 }
-__device__ __forceinline__ double row_nv(const RowNv<true> &rn, int ln, long cw) {   // cw < B
+__device__ __forceinline__ double row_nv(const RowNv<1> &rn, int ln, long cw, long) {   // cw < B
     if constexpr (DM_ROWNV_LDS) return row_nv_tile()[ln];
     else return rn.nvs[cw];
 }
+// Per symbol (ROWNV 2): the value belongs to symbol s of the row, so the symbols of one
+// couple that straddles two of them each take their own; one 8-byte load per symbol,
+// consecutive threads consecutive addresses within a row (cw < B, s < S).
+__device__ __forceinline__ double row_nv(const RowNv<2> &rn, int, long cw, long s) { return rn.nvs[cw * rn.S + s]; }
 
-template <typename T, int BPS, bool SPLIT = false, bool ROWNV = false>
+template <typename T, int BPS, bool SPLIT = false, int ROWNV = 0>
 __global__ __launch_bounds__(BLOCK) void k_demap_planes(int B, int N, int S, const float *syms, const T *cons_g,
                                                        DemapCfg c, const int *__restrict__ src,
                                                        const int *__restrict__ off, long n_avail, float *planes,
@@ -2930,7 +2945,7 @@ __global__ __launch_bounds__(BLOCK) void k_demap_planes(int B, int N, int S, con
         // measured faster; QPSK and 64 / 256QAM slower)
         constexpr bool PF = BPS == 3 || BPS == 4;
         float2 zn = PF ? sym_at(T0, lane, si) : make_float2(0.0f, 0.0f);
-        if constexpr (ROWNV) row_nv_stage(rn, tile, B);
+        if constexpr (ROWNV == 1) row_nv_stage(rn, tile, B);
         for (int t = T0; t < nt; t += BLOCK) {
             const int ln = lane, sx = si;
             lane += dq;
@@ -2948,7 +2963,7 @@ __global__ __launch_bounds__(BLOCK) void k_demap_planes(int B, int N, int S, con
             if constexpr (SPLIT) {
                 bool dec = false;
                 if constexpr (ROWNV) {
-                    if (live) dec = !demap_fast<T, BPS, DM_F32OUT>((T)zc.x, (T)zc.y, cons, row_cfg(c, row_nv(rn, ln, cw)), v);
+                    if (live) dec = !demap_fast<T, BPS, DM_F32OUT>((T)zc.x, (T)zc.y, cons, row_cfg(c, row_nv(rn, ln, cw, s)), v);
                 } else {
                     if (live) dec = !demap_fast<T, BPS, DM_F32OUT>((T)zc.x, (T)zc.y, cons, c, v);
                 }
@@ -2971,7 +2986,7 @@ __global__ __launch_bounds__(BLOCK) void k_demap_planes(int B, int N, int S, con
             } else {
                 if (!live) continue;
                 if constexpr (ROWNV) {
-                    demap_sym<T, BPS, DM_F32OUT>((T)zc.x, (T)zc.y, cons, row_cfg(c, row_nv(rn, ln, cw)), v);
+                    demap_sym<T, BPS, DM_F32OUT>((T)zc.x, (T)zc.y, cons, row_cfg(c, row_nv(rn, ln, cw, s)), v);
                 } else {
                     demap_sym<T, BPS, DM_F32OUT>((T)zc.x, (T)zc.y, cons, c, v);
                 }
@@ -3024,7 +3039,7 @@ __device__ __forceinline__ void dm_fix_symbol(long cw, long s, int N, int S, con
         else base[(long)N * WAVE * 4 + ((long)k * WAVE + lane) * 2 + (cc - 6)] = (float)v[b];
     }
 }
-template <typename T, int BPS, bool ROWNV = false>
+template <typename T, int BPS, int ROWNV = 0>
 __global__ __launch_bounds__(BLOCK) void k_demap_fix(int B, int N, int S, const float *syms, const T *cons_g,
                                                     DemapCfg c, const int *__restrict__ dst, long n_avail,
                                                     float *planes, DemapDecl dd, long n_tiles, RowNv<ROWNV> rn = {}) {
@@ -3036,7 +3051,7 @@ __global__ __launch_bounds__(BLOCK) void k_demap_fix(int B, int N, int S, const 
         const int2 e = dd.list[i];
         if (dd.ovf[e.x / WAVE]) continue;   // redone below
         if constexpr (ROWNV) {
-            dm_fix_symbol<T, BPS>(e.x, e.y, N, S, syms, cons, row_cfg(c, rn.nvs[e.x]), dst, n_avail, planes);
+            dm_fix_symbol<T, BPS>(e.x, e.y, N, S, syms, cons, row_cfg(c, sym_nv(rn, e.x, e.y)), dst, n_avail, planes);
         } else {
             dm_fix_symbol<T, BPS>(e.x, e.y, N, S, syms, cons, c, dst, n_avail, planes);
         }
@@ -3046,7 +3061,7 @@ __global__ __launch_bounds__(BLOCK) void k_demap_fix(int B, int N, int S, const 
         for (long i = threadIdx.x; i < (long)WAVE * S; i += BLOCK) {
             const long cw = t * WAVE + i / S;
             if constexpr (ROWNV) {
-                if (cw < B) dm_fix_symbol<T, BPS>(cw, i % S, N, S, syms, cons, row_cfg(c, rn.nvs[cw]), dst, n_avail, planes);
+                if (cw < B) dm_fix_symbol<T, BPS>(cw, i % S, N, S, syms, cons, row_cfg(c, sym_nv(rn, cw, i % S)), dst, n_avail, planes);
             } else {
                 if (cw < B) dm_fix_symbol<T, BPS>(cw, i % S, N, S, syms, cons, c, dst, n_avail, planes);
             }
@@ -3176,7 +3191,7 @@ __device__ __forceinline__ void demap_lm_sym(T sr, T si, const T *cons, const De
 }
 
 // k_demap's launch shape: one symbol per thread, f64 LLRs
-template <typename T, typename S, int BPS, bool ROWNV = false>
+template <typename T, typename S, int BPS, int ROWNV = 0>
 __global__ __launch_bounds__(BLOCK) void k_demap_lm(const S *syms, long n_sym, const T *cons_g, DemapCfg c, double scale,
                                                    double *llr, RowNv<ROWNV> rn = {}) {
     __shared__ T cons[DM_TAB];
@@ -3186,7 +3201,7 @@ __global__ __launch_bounds__(BLOCK) void k_demap_lm(const S *syms, long n_sym, c
     if (s >= n_sym) return;
     double v[BPS];
     if constexpr (ROWNV) {
-        const DemapCfg rc = row_cfg(c, rn.nvs[s / rn.S]);
+        const DemapCfg rc = row_cfg(c, flat_nv(rn, s));
         demap_lm_sym<T, BPS>((T)syms[2 * s], (T)syms[2 * s + 1], cons, rc, (T)row_lm_scale(rc), v);
     } else {
         demap_lm_sym<T, BPS>((T)syms[2 * s], (T)syms[2 * s + 1], cons, c, (T)scale, v);
@@ -3198,7 +3213,7 @@ __global__ __launch_bounds__(BLOCK) void k_demap_lm(const S *syms, long n_sym, c
 // k_demap_planes' items, LDS tile and plane layout (its phase 2 verbatim, so
 // tdec_decode_planes_dev consumes these planes unchanged) around demap_lm_sym;
 // no split and no prefetch: the symbol's work is the transcendentals.
-template <typename T, int BPS, bool ROWNV = false>
+template <typename T, int BPS, int ROWNV = 0>
 __global__ __launch_bounds__(BLOCK) void k_demap_planes_lm(int B, int N, int S, const float *syms, const T *cons_g,
                                                           DemapCfg c, double scale, const int *__restrict__ src,
                                                           const int *__restrict__ off, long n_avail, float *planes,
@@ -3217,7 +3232,7 @@ __global__ __launch_bounds__(BLOCK) void k_demap_planes_lm(int B, int N, int S, 
         const long j0 = off[k0], j1 = off[k1];
         const long s0 = j0 / BPS, s1 = (j1 + BPS - 1) / BPS;        // symbols covering [j0, j1)
         const int ns = (int)(s1 - s0);
-        if constexpr (ROWNV) row_nv_stage(rn, tile, B);
+        if constexpr (ROWNV == 1) row_nv_stage(rn, tile, B);
         for (int t = threadIdx.x; t < WAVE * ns; t += BLOCK) {      // consecutive threads: consecutive symbols
             const int ln = t / ns, sx = t - ln * ns;
             const long cw = tile * WAVE + ln, s = s0 + sx;
@@ -3225,7 +3240,7 @@ __global__ __launch_bounds__(BLOCK) void k_demap_planes_lm(int B, int N, int S, 
             const float2 z = *reinterpret_cast<const float2 *>(syms + 2 * (cw * S + s));
             double v[BPS];
             if constexpr (ROWNV) {
-                const DemapCfg rc = row_cfg(c, row_nv(rn, ln, cw));
+                const DemapCfg rc = row_cfg(c, row_nv(rn, ln, cw, s));
                 demap_lm_sym<T, BPS>((T)z.x, (T)z.y, cons, rc, (T)row_lm_scale(rc), v);
             } else {
                 demap_lm_sym<T, BPS>((T)z.x, (T)z.y, cons, c, sc, v);
@@ -3297,6 +3312,56 @@ __global__ __launch_bounds__(BLOCK) void k_noise_var(const float *syms, int S, c
         for (int w = 1; w < BLOCK / WAVE; ++w) sum += part[w];
         const double mean = sum / (double)S;
         nv[blockIdx.x] = (floor_nv > mean) ? floor_nv : mean;
+    }
+}
+
+// ---- flat-fading equaliser (build-defined) -------------------------------
+// y = h x + n with known h: z = y / h and the noise variance of z, nv / |h|^2, for each
+// symbol of [B][S] complex64 rows; symbol s of row r uses h[r][s / coh] of
+// [B][ceil(S / coh)] gains.  All in f64, no contraction:
+//   g = hr*hr + hi*hi   (the products of f32 values are exact in f64: one rounding)
+//   z = ((float)((yr*hr + yi*hi) / g), (float)((yi*hr - yr*hi) / g)),  nv_sym = nv_r / g
+// (no floor here: the demapper floors).  g == 0 or not finite: an erasure, z = 0 and
+// nv_sym = +inf, which the demappers turn into all-zero LLRs.  NVROWS: nv_r = nvs[r] (a
+// device vector), else the launch's nv.  One thread per symbol; with VEC one thread per
+// two consecutive symbols of the flat [B * S] array (which may lie in two rows), so y is
+// read and z and nv_sym are written 16 bytes at a time (the host checks the alignment).
+struct EqOut {
+    float zr, zi;
+    double nv;
+};
+__device__ __forceinline__ EqOut eq_symbol(float2 y, float2 h, double nv) {
+    const double hr = (double)h.x, hi = (double)h.y, yr = (double)y.x, yi = (double)y.y;
+    const double g = hr * hr + hi * hi;
+    if (g == 0.0 || !(fabs(g) < INFINITY)) return EqOut{0.0f, 0.0f, (double)INFINITY};
+    return EqOut{(float)((yr * hr + yi * hi) / g), (float)((yi * hr - yr * hi) / g), nv / g};
+}
+template <bool NVROWS, bool VEC>
+__global__ __launch_bounds__(BLOCK) void k_equalize(const float2 *y, const float2 *h, long n_sym, int S, int coh, int nh,
+                                                   double nv, const double *nvs, float2 *z, double *nv_sym) {
+    const long t = (long)blockIdx.x * BLOCK + threadIdx.x;
+    auto one = [&](long i, float2 yi) -> EqOut {   // i < n_sym
+        const long r = i / S;
+        const int s = (int)(i - r * S);
+        return eq_symbol(yi, h[r * nh + s / coh], NVROWS ? nvs[r] : nv);
+    };
+    if constexpr (VEC) {
+        const long i = 2 * t;
+        if (i + 1 < n_sym) {
+            const float4 yy = reinterpret_cast<const float4 *>(y)[t];
+            const EqOut a = one(i, make_float2(yy.x, yy.y)), b = one(i + 1, make_float2(yy.z, yy.w));
+            reinterpret_cast<float4 *>(z)[t] = make_float4(a.zr, a.zi, b.zr, b.zi);
+            reinterpret_cast<double2 *>(nv_sym)[t] = make_double2(a.nv, b.nv);
+        } else if (i < n_sym) {   // the last symbol of an odd count
+            const EqOut a = one(i, y[i]);
+            z[i] = make_float2(a.zr, a.zi);
+            nv_sym[i] = a.nv;
+        }
+    } else {
+        if (t >= n_sym) return;
+        const EqOut a = one(t, y[t]);
+        z[t] = make_float2(a.zr, a.zi);
+        nv_sym[t] = a.nv;
     }
 }
 

@@ -9,6 +9,7 @@
 // ranks a job is sharded over:
 //   info bits   ctr = {cw_lo, cw_hi, 128-bit block, 0x1AF0}, key = seed
 //   noise       ctr = {cw_lo, cw_hi, symbol pair,    0x2B0E}, key = seed
+//   gains       ctr = {cw_lo, cw_hi, gain-block pair, 0x3C5D}, key = seed   (k_workload_fading)
 // Info bit j of a codeword is bit j % 32 of word (j % 128) / 32 of block j / 128.
 // Noise: Box-Muller, u = (x >> 8 + 0.5) * 2^-24 in (0, 1): one complex sample
 // per symbol from two words, r = sigma * sqrt(-2 ln u1), theta = 2 pi u2.
@@ -46,7 +47,7 @@ __host__ __device__ __forceinline__ Philox4 philox4x32_10(Philox4 c, uint32_t k0
     return c;
 }
 
-constexpr uint32_t INFO_DOMAIN = 0x1AF0u, NOISE_DOMAIN = 0x2B0Eu;
+constexpr uint32_t INFO_DOMAIN = 0x1AF0u, NOISE_DOMAIN = 0x2B0Eu, FADE_DOMAIN = 0x3C5Du;
 
 __device__ __forceinline__ Philox4 info_block(uint64_t cw, uint32_t blk, uint64_t seed) {
     return philox4x32_10(Philox4{(uint32_t)cw, (uint32_t)(cw >> 32), blk, INFO_DOMAIN}, (uint32_t)seed,
@@ -170,24 +171,54 @@ __device__ __forceinline__ float2 awgn(uint64_t cw, long s, const WorkloadArgs &
     return make_float2(rad * cs, rad * sn);
 }
 
+// Flat fading (k_workload_fading): gain block j of a codeword covers its
+// symbols [j * coh, (j + 1) * coh).  h = los + scat * w, w ~ CN(0, 1) by awgn()'s uniform
+// mapping and sincospif form on the gain stream (unit total variance: 1/2 per dimension);
+// los = sqrt(K / (K + 1)), scat = sqrt(1 / (K + 1)) for the Rician factor K (0: Rayleigh).
+struct FadeArgs {
+    float2 *h;                                  // [B][nh] complex64
+    int coh, nh;                                // symbols per gain block; nh = ceil(S / coh)
+    float los, scat;
+};
+__device__ __forceinline__ float2 fade_gain(uint64_t cw, long j, uint64_t seed, const FadeArgs &f) {
+    const Philox4 r = philox4x32_10(Philox4{(uint32_t)cw, (uint32_t)(cw >> 32), (uint32_t)(j >> 1), FADE_DOMAIN},
+                                    (uint32_t)seed, (uint32_t)(seed >> 32));
+    const uint32_t a = (j & 1) ? r.z : r.x, b = (j & 1) ? r.w : r.y;
+    const float u1 = ((float)(a >> 8) + 0.5f) * 0x1p-24f, u2 = ((float)(b >> 8) + 0.5f) * 0x1p-24f;
+    const float rad = 0.70710678118654752f * sqrtf(-2.0f * logf(u1));
+    float sn, cs;
+    sincospif(2.0f * u2, &sn, &cs);
+    return make_float2(f.los + f.scat * (rad * cs), f.scat * (rad * sn));
+}
+
 // Row-order flush of a chunk of symbol labels lab[k][lane] (k < ns): symbols
-// [s0, s0 + ns) of every codeword, table point + AWGN, complex64.
-__device__ __forceinline__ void flush_syms(const WorkloadArgs &p, long base, uint8_t (*lab)[64], const float2 *cons,
-                                           int ns, long s0, int lane) {
+// [s0, s0 + ns) of every codeword, table point + AWGN, complex64.  FADE: h x + AWGN, and
+// the first symbol of each gain block writes its gain.
+template <bool FADE>
+__device__ __forceinline__ void flush_syms(const WorkloadArgs &p, const FadeArgs &f, long base, uint8_t (*lab)[64],
+                                           const float2 *cons, int ns, long s0, int lane) {
     __syncthreads();
     for (int t = lane; t < 64 * ns; t += 64) {
         const int l = t / ns, k = t - l * ns;
         if (base + l < p.B) {
             const uint64_t cw = p.cw0 + (uint64_t)(base + l);
             const float2 x = cons[lab[k][l]], n = awgn(cw, s0 + k, p);
-            p.syms[(base + l) * (long)p.S + s0 + k] = make_float2(x.x + n.x, x.y + n.y);
+            if constexpr (FADE) {
+                const long s = s0 + k, j = s / f.coh;
+                const float2 g = fade_gain(cw, j, p.seed, f);
+                if (s == j * f.coh) f.h[(base + l) * (long)f.nh + j] = g;
+                p.syms[(base + l) * (long)p.S + s] =
+                    make_float2((g.x * x.x - g.y * x.y) + n.x, (g.x * x.y + g.y * x.x) + n.y);
+            } else {
+                p.syms[(base + l) * (long)p.S + s0 + k] = make_float2(x.x + n.x, x.y + n.y);
+            }
         }
     }
     __syncthreads();
 }
 
 // One wave per 64-codeword tile (block = 1 wave: no cross-wave barriers).
-__global__ __launch_bounds__(64) void k_workload(WorkloadArgs p) {
+template <bool FADE> __device__ __forceinline__ void workload_tile(const WorkloadArgs &p, const FadeArgs &f) {
     __shared__ uint32_t inpw[ENC_NW][64];
     __shared__ uint32_t outw[OUT_CHUNK][64];
     __shared__ uint8_t lab[SYM_CHUNK][64];
@@ -232,7 +263,7 @@ __global__ __launch_bounds__(64) void k_workload(WorkloadArgs p) {
                 lbl = 0;
                 nl = 0;
                 if (++ns == SYM_CHUNK) {
-                    flush_syms(p, base, lab, cons, ns, s0, lane);
+                    flush_syms<FADE>(p, f, base, lab, cons, ns, s0, lane);
                     s0 += ns;
                     ns = 0;
                 }
@@ -259,9 +290,10 @@ __global__ __launch_bounds__(64) void k_workload(WorkloadArgs p) {
     }
     if (p.syms) {
         if (nl) lab[ns++][lane] = (uint8_t)(lbl << (p.bps - nl));   // zero pad of the last symbol
-        if (ns) flush_syms(p, base, lab, cons, ns, s0, lane);
+        if (ns) flush_syms<FADE>(p, f, base, lab, cons, ns, s0, lane);
     }
 }
+__global__ __launch_bounds__(64) void k_workload(WorkloadArgs p) { workload_tile<false>(p, FadeArgs{}); }
 
 // Bit errors of decoded rows against the counter-based info bits: one wave per
 // codeword, each lane 4 consecutive bits (one 16-B load) per sweep.
@@ -289,5 +321,10 @@ __global__ __launch_bounds__(64) void k_count_errors(int B, int N, uint64_t cw0,
     for (int o = 32; o > 0; o >>= 1) e += __shfl_xor(e, o);
     if (lane == 0) errs[cw] = e;
 }
+
+
+// k_workload with flat fading: the same bits and the same noise, each symbol h x + n, and
+// the gains written to f.h.
+__global__ __launch_bounds__(64) void k_workload_fading(WorkloadArgs p, FadeArgs f) { workload_tile<true>(p, f); }
 
 }  // namespace tdec

@@ -160,6 +160,71 @@ def _rows_check(syms, nv, name="noise_var"):
         raise ValueError(f"{name} must be on the symbols' HIP device")
 
 
+def _syms_check(syms, nv, name="noise_var"):
+    """A per-symbol noise variance: a contiguous float64 [B, S]
+    tensor on the device of the 2-D [B, S] complex symbols.  Refused here, before any
+    device call."""
+    import torch
+    if not isinstance(syms, torch.Tensor) or syms.dim() != 2 or not syms.is_complex():
+        raise ValueError(f"a per-symbol {name} needs 2-D [B, S] complex symbols")
+    if nv.dtype != torch.float64:
+        raise TypeError(f"{name} must be torch.float64, got {nv.dtype}")
+    if tuple(nv.shape) != tuple(syms.shape) or not nv.is_contiguous():
+        raise ValueError(f"{name} must be a contiguous tensor of shape {tuple(syms.shape)}, got {tuple(nv.shape)}")
+    if nv.device.type != "cuda" or nv.device != syms.device:
+        raise ValueError(f"{name} must be on the symbols' HIP device")
+
+
+def nv_tensor_form(syms, nv):
+    """Which per-launch form a noise_var tensor is: "rows" ([B]) or "syms" ([B, S]), checked
+    against the symbols."""
+    if nv.dim() == 2:
+        _syms_check(syms, nv)
+        return "syms"
+    _rows_check(syms, nv)
+    return "rows"
+
+
+def equalize_device(syms, h, noise_var, coh=1, out=None, nv_out=None, stream=None):
+    """Flat-fading equaliser: received complex64 [B, S] device
+    symbols y = h x + n with known gains h, complex64 [B, ceil(S / coh)] (symbol s uses
+    h[:, s // coh]), and the noise variance of y (a scalar, or a float64 [B] device
+    tensor) -> (z = y / h complex64 [B, S], nv_sym = noise_var / |h|^2 float64 [B, S]),
+    stream-ordered, for compute_llr_device / demap_planes_device to read in place.
+    |h|^2 zero or not finite marks an erasure: z = 0, nv_sym = +inf (zero LLRs)."""
+    import torch
+    if not isinstance(syms, torch.Tensor) or syms.dtype != torch.complex64:
+        raise TypeError(f"syms must be a torch.complex64 tensor, got {getattr(syms, 'dtype', type(syms))}")
+    if not isinstance(h, torch.Tensor) or h.dtype != torch.complex64:
+        raise TypeError(f"h must be a torch.complex64 tensor, got {getattr(h, 'dtype', type(h))}")
+    if syms.dim() != 2 or syms.device.type != "cuda" or not syms.is_contiguous():
+        raise ValueError("syms must be a contiguous 2-D [B, S] tensor on a HIP device")
+    B, S = syms.shape
+    coh = int(coh)
+    if coh < 1:
+        raise ValueError("coh must be >= 1")
+    nh = -(-S // coh)
+    if tuple(h.shape) != (B, nh) or not h.is_contiguous() or h.device != syms.device:
+        raise ValueError(f"h must be a contiguous tensor of shape ({B}, {nh}) on the symbols' device, "
+                         f"got {tuple(h.shape)}")
+    rows = isinstance(noise_var, torch.Tensor)
+    if rows:
+        _rows_check(syms, noise_var)
+    if out is None:
+        out = torch.empty_like(syms)
+    elif out.dtype != torch.complex64 or tuple(out.shape) != (B, S) or not out.is_contiguous() or out.device != syms.device:
+        raise ValueError(f"out must be a contiguous complex64 tensor of shape ({B}, {S}) on the symbols' device")
+    if nv_out is None:
+        nv_out = torch.empty((B, S), dtype=torch.float64, device=syms.device)
+    else:
+        _syms_check(syms, nv_out, "nv_out")
+    dev = syms.device.index or 0
+    st = _n.stream_ptr(stream) if stream is not None else torch.cuda.current_stream(dev).cuda_stream
+    _n.check(_n.lib().tdec_equalize_dev(dev, _n.ptr(syms), _n.ptr(h), B, S, coh, 0.0 if rows else float(noise_var),
+                                        _n.ptr(noise_var) if rows else None, _n.ptr(out), _n.ptr(nv_out), st))
+    return out, nv_out
+
+
 def estimate_noise_var_device(syms, mod_type, floor=0.02, out=None, stream=None):
     """The receiver's decision-directed noise variance (test_sdr_with_coding.py:459-467:
     hard decision, re-map, mean |rx - const|^2, max(nv, 0.02)) of each row of complex64
@@ -192,14 +257,15 @@ def compute_llr_device(syms, mod_type, noise_var, out=None, sign=+1, stream=None
     """compute_llr over a device tensor of complex symbols (complex64/complex128 or
     a float [..., 2] view); returns a float64 device tensor.  noise_var: a scalar, or
     a float64 [B] device tensor with 2-D [B, S] symbols (row r demapped with
-    noise_var[r], read on the device: no host round trip); the result is then [B, S*bps]."""
+    noise_var[r], read on the device: no host round trip), or a float64 [B, S] one
+    (symbol (r, s) with noise_var[r, s], equalize_device's nv_sym; DESIGN.md section 11);
+    the result is then [B, S*bps]."""
     import torch
     lm = check_algo(algo)
     m = MODULATIONS[mod_type]
     cons = _cons(mod_type)
     rows = isinstance(noise_var, torch.Tensor)
-    if rows:
-        _rows_check(syms, noise_var)
+    form = nv_tensor_form(syms, noise_var) if rows else ""
     sym_f64 = syms.dtype in (torch.complex128, torch.float64)
     n_sym = syms.numel() // (1 if syms.is_complex() else 2)
     if rows:   # the division's dtype: what a numpy float64 scalar gives (as DevicePipeline.run treats its scalar)
@@ -217,9 +283,10 @@ def compute_llr_device(syms, mod_type, noise_var, out=None, sign=+1, stream=None
     if out.dtype != torch.float64 or not out.is_contiguous() or out.numel() < n_sym * m['bps'] or out.device != syms.device:
         raise ValueError("out must be a contiguous float64 tensor of n_sym*bps elements on the symbols' device")
     st = _n.stream_ptr(stream) if stream is not None else torch.cuda.current_stream(dev).cuda_stream
-    # tdec_demap[_rows][_logmap]_dev: (B, S) and the vector for rows, else n_sym and the
-    # scalar; no div_f32 for log-MAP
-    call = getattr(_n.lib(), f"tdec_demap{'_rows' if rows else ''}{'_logmap' if lm else ''}_dev")
+    # tdec_demap[_rows][_logmap]_dev, or tdec_symnv_demap[_logmap]_dev for a per-symbol tensor:
+    # (B, S) and the tensor for rows / syms, else n_sym and the scalar; no div_f32 for log-MAP
+    stem = "tdec_symnv_demap" if form == "syms" else f"tdec_demap{'_rows' if rows else ''}"
+    call = getattr(_n.lib(), f"{stem}{'_logmap' if lm else ''}_dev")
     _n.check(call(dev, _n.ptr(syms), int(sym_f64), *(syms.shape if rows else (n_sym,)), _n.ptr(c), int(f64), len(c),
                   m['bps'], _n.ptr(nvt) if rows else nv, *(() if lm else (int(div_f32),)), int(sign), _n.ptr(out), st))
     return out

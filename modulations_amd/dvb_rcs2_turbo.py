@@ -418,7 +418,8 @@ class DVBRCS2_Turbo:
         """Fused soft demap (decoder sign) + de-puncture of complex64 symbols [B, S];
         algo="log-map": the exact log-sum demapper (div_f32 has no meaning there).
         noise_var: a scalar, or a float64 [B] tensor on this codec's device (row r
-        demapped with noise_var[r], read on the device)."""
+        demapped with noise_var[r], read on the device), or a
+        float64 [B, S] one (symbol (r, s) with noise_var[r, s]; section 11)."""
         from .demap import check_algo
         lm = check_algo(algo)
         cons = np.ascontiguousarray(np.asarray(constellation))
@@ -426,15 +427,19 @@ class DVBRCS2_Turbo:
         cons = cons.astype(np.complex128 if f64 else np.complex64)
         import torch
         rows = isinstance(noise_var, torch.Tensor)
+        per_sym = rows and noise_var.dim() == 2
         if rows:
-            self._dev_check(noise_var, "noise_var", torch.float64, (len(syms),))
+            self._dev_check(noise_var, "noise_var", torch.float64, tuple(syms.shape) if per_sym else (len(syms),))
         self._dev_check(syms, "syms", torch.complex64)
         self._dev_check(planes, "planes", torch.float32)
         B, S = syms.shape[0], syms.shape[1]
         if planes.numel() * 4 < self.planes_bytes(B):
             raise ValueError("planes buffer smaller than planes_bytes(B)")
-        # tdec_demap_planes[_logmap][_nv]_dev: the vector for rows, else the scalar; no div_f32 for log-MAP
-        self.handle.call(f"tdec_demap_planes{'_logmap' if lm else ''}{'_nv' if rows else ''}_dev", B, _n.ptr(syms), S,
+        # tdec_demap_planes[_logmap][_nv]_dev, or tdec_symnv_demap_planes[_logmap]_dev for a per-symbol
+        # tensor: the tensor for rows / symbols, else the scalar; no div_f32 for log-MAP
+        name = (f"tdec_symnv_demap_planes{'_logmap' if lm else ''}_dev" if per_sym else
+                f"tdec_demap_planes{'_logmap' if lm else ''}{'_nv' if rows else ''}_dev")
+        self.handle.call(name, B, _n.ptr(syms), S,
                          _n.ptr(cons), int(f64), len(cons), bps, _n.ptr(noise_var) if rows else float(noise_var),
                          *(() if lm else (int(div_f32),)), _n.ptr(planes), self._stream(stream))
         return planes

@@ -17,7 +17,7 @@ def noise_n0(constellation, rate, bps, ebn0_db):
     return es / (rate * bps * 10 ** (ebn0_db / 10.0))
 
 
-def make_symbols(codec, B, mod, ebn0_db, seed, device, cw0=0, want_info=True):
+def make_symbols(codec, B, mod, ebn0_db, seed, device, cw0=0, want_info=True, fading=None):
     """(info uint8 [B, 2N] or None, received symbols complex64 [B, S], N0) on `device`.
 
     One launch of the counter-based generator (tdec_workload_dev): Philox info
@@ -25,7 +25,12 @@ def make_symbols(codec, B, mod, ebn0_db, seed, device, cw0=0, want_info=True):
     labelled Gray constellation (bps coded bits per label, MSB first, the last
     symbol zero-padded as the reference mappers pad, test_sdr_with_coding.py:45-86)
     -> complex AWGN with per-dimension variance N0/2.  Codeword g's data is the
-    same whichever batch or rank generates it."""
+    same whichever batch or rank generates it.
+
+    fading={"K": Rician factor >= 0 (0: Rayleigh), "coh": symbols per gain block >= 1}:
+    a flat-fading channel (tdec_workload_fading_dev), each symbol h x + n
+    with the same bits and the same noise as without it, E|h|^2 = 1; the result is then
+    (info, symbols, N0, h) with h complex64 [B, ceil(S / coh)]."""
     import torch
     from . import _native as _n
     bps = D.MODULATIONS[mod]["bps"]
@@ -37,6 +42,17 @@ def make_symbols(codec, B, mod, ebn0_db, seed, device, cw0=0, want_info=True):
     table = np.ascontiguousarray(cons.astype(np.complex64)).view(np.float32)
     syms = torch.empty((B, S), dtype=torch.complex64, device=device)
     info = torch.empty((B, codec.k_info), dtype=torch.uint8, device=device) if want_info else None
+    if fading is not None:
+        unknown = set(fading) - {"K", "coh"}
+        if unknown:
+            raise ValueError(f"fading takes the keys 'K' and 'coh', not {sorted(unknown)}")
+        k, coh = float(fading.get("K", 0.0)), int(fading.get("coh", 1))
+        if not (0.0 <= k < float("inf")) or coh < 1:
+            raise ValueError("fading needs a finite K >= 0 and coh >= 1")
+        gains = torch.empty((B, -(-S // coh)), dtype=torch.complex64, device=device)
+        h.call("tdec_workload_fading_dev", int(B), int(cw0), int(seed) & 0xFFFFFFFFFFFFFFFF, _n.ptr(table), len(cons),
+               bps, float(np.sqrt(n0 / 2)), k, coh, _n.ptr(syms), _n.ptr(gains), _n.ptr(info), codec._stream(None))
+        return info, syms, n0, gains
     h.call("tdec_workload_dev", int(B), int(cw0), int(seed) & 0xFFFFFFFFFFFFFFFF, _n.ptr(table), len(cons), bps,
            float(np.sqrt(n0 / 2)), _n.ptr(syms), _n.ptr(info), codec._stream(None))
     return info, syms, n0
@@ -93,9 +109,14 @@ class DevicePipeline:
 
     run() also takes a per-row noise variance, a float64 [B] device tensor, on the
     two-launch and overlap paths; a pipeline built with fused=True
-    refuses it, the fused kernel having no per-row form."""
+    refuses it, the fused kernel having no per-row form.
 
-    def __init__(self, codec, mod, B, device, fused=False, overlap=False, gate=True, demap="max-log"):
+    csi=True sizes the equaliser's outputs (`z` complex64 [B, S], `nv_sym` float64 [B, S])
+    so that run(..., csi=h, coh=...) equalises received symbols of a flat-fading channel
+    with known gains and demaps them with a per-symbol noise variance:
+    three launches on one stream; fused=True refuses it likewise."""
+
+    def __init__(self, codec, mod, B, device, fused=False, overlap=False, gate=True, demap="max-log", csi=False):
         import torch
         self.codec, self.mod, self.B = codec, mod, B
         self.bps = D.MODULATIONS[mod]["bps"]
@@ -115,6 +136,11 @@ class DevicePipeline:
             self.planes = torch.empty(codec.planes_bytes(B) // 4, dtype=torch.float32, device=device)
         self.bits = torch.empty((B, codec.k_info), dtype=torch.int32, device=device)
         self.n_iter = torch.empty(B, dtype=torch.int32, device=device) if self.early_stop else None
+        self.z = self.nv_sym = None
+        if csi:
+            S = -(-codec.handle.enc_len // self.bps)
+            self.z = torch.empty((B, S), dtype=torch.complex64, device=device)
+            self.nv_sym = torch.empty((B, S), dtype=torch.float64, device=device)
         if self.overlap:
             # Batch i+1's demap runs on its own handle (handles order only their own
             # buffers), its own low-priority stream and the other plane buffer, so
@@ -133,7 +159,7 @@ class DevicePipeline:
             self.step = 0
             self.gate = bool(gate)
 
-    def run(self, syms, noise_var, stream=None, events=None, syms_ready=None):
+    def run(self, syms, noise_var, stream=None, events=None, syms_ready=None, csi=None, coh=1):
         """One batch: demap -> decode, stream-ordered on `stream` (its bits are ready
         for work queued on `stream` afterwards).  With overlap=True, `syms_ready`
         (an event after which `syms` is valid) lets the demap start before the
@@ -142,8 +168,21 @@ class DevicePipeline:
 
         noise_var: a scalar, or a float64 [B] tensor on the symbols' device with one
         value per row (demap.estimate_noise_var_device queued on the same stream
-        gives it), which the demapper reads on the device."""
+        gives it), which the demapper reads on the device.
+
+        csi: the channel gains of `syms`, complex64 [B, ceil(S / coh)] on their device
+        (symbol s of a row was received through csi[:, s // coh]); the symbols are
+        equalised into `z` and demapped with `nv_sym` = noise_var / |csi|^2 per symbol.
+        Needs a pipeline built with csi=True."""
         import torch
+        if csi is not None:
+            if self.fused_asked:
+                raise ValueError("csi needs the two-launch pipeline: the fused demap+decode kernel has no "
+                                 "per-symbol form (fused=True)")
+            if self.z is None:
+                raise ValueError("csi needs a pipeline built with csi=True")
+            if syms.shape[0] > self.B or syms.shape[1] != self.z.shape[1]:
+                raise ValueError(f"csi: symbols must be [<= {self.B}, {self.z.shape[1]}], got {tuple(syms.shape)}")
         if isinstance(noise_var, torch.Tensor):
             if self.fused_asked:
                 raise ValueError("a per-row noise_var tensor needs the two-launch pipeline: the fused "
@@ -166,6 +205,8 @@ class DevicePipeline:
                 sd.wait_stream(stream)
             if self.gate:
                 self.codec.tail_gate(sd)                # batch i-1's decode is in its tail
+            if csi is not None:
+                syms, nve, div32 = self._equalize(syms, csi, noise_var, coh, sd)
             self.demapper.demap_planes_device(syms, self.cons, self.bps, nve, self.planes_db[b], div_f32=div32,
                                               stream=sd, algo=self.demap)
             self.demap_done[b].record(sd)
@@ -185,6 +226,8 @@ class DevicePipeline:
                 events[0].record(stream)
             self.codec.demap_decode_device(syms, self.cons, self.bps, nve, bits, div_f32=div32, stream=stream)
         else:
+            if csi is not None:
+                syms, nve, div32 = self._equalize(syms, csi, noise_var, coh, stream)
             self.codec.demap_planes_device(syms, self.cons, self.bps, nve, self.planes, div_f32=div32,
                                            stream=stream, algo=self.demap)
             if events is not None:
@@ -193,3 +236,11 @@ class DevicePipeline:
         if events is not None:
             events[1].record(stream)
         return bits
+
+    def _equalize(self, syms, csi, nv, coh, stream):
+        """(z, nv_sym, div_f32) for the demapper: `syms` equalised by `csi` into this
+        pipeline's buffers on `stream` (nv unfloored: the demapper floors nv / |h|^2); the
+        division's dtype is the tensor forms'."""
+        n = syms.shape[0]
+        z, nvs = D.equalize_device(syms, csi, nv, coh=coh, out=self.z[:n], nv_out=self.nv_sym[:n], stream=stream)
+        return z, nvs, D.demap_mode(np.complex64, self.cons.dtype, np.float64(1.0))[1]

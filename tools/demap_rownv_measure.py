@@ -1,9 +1,10 @@
 #!/usr/bin/env python3
-"""Cost of the per-row noise variance path, in one process with HIP
-events: tdec_demap_planes_dev against tdec_demap_planes_nv_dev with every row
-carrying the same value (so both write the same planes, which is checked), max-log
-and log-MAP, interleaved round by round in both orders, plus the estimator
-(tdec_noise_var_dev) on the same symbols.
+"""Cost of the per-row and per-symbol noise variance paths, in one
+process with HIP events: tdec_demap_planes_dev against tdec_demap_planes_nv_dev and
+tdec_symnv_demap_planes_dev with every row / symbol carrying the same value (so all
+write the same planes, which is checked), max-log and log-MAP, interleaved round by
+round in both orders, plus the estimator (tdec_noise_var_dev) and the equaliser
+(tdec_equalize_dev, per-symbol gains) on the same symbols.
 
   python tools/demap_rownv_measure.py [--mods 16QAM 256QAM --batch 1048576 --rounds 5] [--out f.json]
 
@@ -38,12 +39,16 @@ def measure(mod, a, dev):
     bps = D.MODULATIONS[mod]["bps"]
     _, div32, nve = D.demap_mode(np.complex64, cons.dtype, np.float64(n0))
     nvt = torch.full((B,), nve, dtype=torch.float64, device=dev)
+    nvs = torch.full(tuple(syms.shape), nve, dtype=torch.float64, device=dev)
+    gains = torch.ones_like(syms)
+    eq_z, eq_nv = torch.empty_like(syms), torch.empty_like(nvs)
     codec.reserve(B)
     planes = torch.empty(codec.planes_bytes(B) // 4, dtype=torch.float32, device=dev)
     st = torch.cuda.current_stream()
-    variants = [(algo, kind) for algo in ("max-log", "log-map") for kind in ("scalar", "per-row")]
+    variants = [(algo, kind) for algo in ("max-log", "log-map") for kind in ("scalar", "per-row", "per-symbol")]
     times = {f"{algo} {kind}": [] for algo, kind in variants}
     times["estimator"] = []
+    times["equaliser"] = []
     sums = {}
 
     def timed(fn):
@@ -56,7 +61,7 @@ def measure(mod, a, dev):
 
     for r in range(2 * a.rounds + 1):                  # round 0 untimed; odd rounds forward, even rounds reversed
         for algo, kind in (variants if r % 2 else variants[::-1]):
-            nv = nvt if kind == "per-row" else nve
+            nv = {"scalar": nve, "per-row": nvt, "per-symbol": nvs}[kind]
             t = timed(lambda: codec.demap_planes_device(syms, cons, bps, nv, planes, div_f32=div32, algo=algo))
             if r:
                 times[f"{algo} {kind}"].append(t)
@@ -65,14 +70,22 @@ def measure(mod, a, dev):
         t = timed(lambda: D.estimate_noise_var_device(syms, mod, out=est))
         if r:
             times["estimator"].append(t)
+        t = timed(lambda: D.equalize_device(syms, gains, nve, out=eq_z, nv_out=eq_nv))
+        if r:
+            times["equaliser"].append(t)
     for algo in ("max-log", "log-map"):
-        assert sums[(algo, "scalar")] == sums[(algo, "per-row")], f"{mod} {algo}: planes differ"
+        assert sums[(algo, "scalar")] == sums[(algo, "per-row")] == sums[(algo, "per-symbol")], \
+            f"{mod} {algo}: planes differ"
     ms = {k: stats(t) for k, t in times.items()}
     rec = {"mod": mod, "n_couples": a.n, "rate": a.rate, "codewords": B, "symbols": int(syms.numel()),
            "ebn0_db": a.ebn0, "noise_var": nve, "rounds_each_order": a.rounds,
            "lib": os.environ.get("TDEC_LIB_VARIANT", "libtdec"), "ms": ms,
            "ratio_per_row_over_scalar": {algo: ms[f"{algo} per-row"]["median"] / ms[f"{algo} scalar"]["median"]
                                          for algo in ("max-log", "log-map")},
+           "ratio_per_symbol_over_scalar": {algo: ms[f"{algo} per-symbol"]["median"] / ms[f"{algo} scalar"]["median"]
+                                            for algo in ("max-log", "log-map")},
+           # the equaliser reads y and h (8 B each) and writes z (8 B) and nv_sym (8 B) per symbol
+           "equaliser_bytes_per_s": 32.0 * syms.numel() / (ms["equaliser"]["median"] * 1e-3),
            "scalar_spread": {algo: (ms[f"{algo} scalar"]["max"] - ms[f"{algo} scalar"]["min"]) /
                              ms[f"{algo} scalar"]["median"] for algo in ("max-log", "log-map")}}
     print(json.dumps(rec), flush=True)
