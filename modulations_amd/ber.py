@@ -55,12 +55,12 @@ def sweep_config(a, inv_perm=None):
            "seed": int(a.seed)}
     if getattr(a, "early_stop", False):   # (absent without the flag: files of earlier sweeps keep resuming)
         cfg["early_stop"] = True
-        if getattr(a, "es_decoder", "frame") != "frame":   # (absent at the default, for the same reason)
+        if getattr(a, "es_decoder", "frame") != "frame":   # (absent at the default, likewise)
             cfg["es_decoder"] = a.es_decoder
-    if getattr(a, "demap", "max-log") != "max-log":   # (absent at the default, for the same reason)
+    if getattr(a, "demap", "max-log") != "max-log":   # (absent at the default, likewise)
         cfg["demap"] = a.demap
     fading = channel_fading(a)
-    if fading is not None:   # (absent for awgn, for the same reason)
+    if fading is not None:   # (absent for awgn, likewise)
         cfg["channel"] = a.channel
         cfg["rician_k"] = fading["K"]
         cfg["coherence"] = fading["coh"]

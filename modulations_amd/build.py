@@ -7,6 +7,7 @@ hipcc cross-compiles for gfx950 without a GPU.  Flags that the numerics need:
   -ffp-contract=off                  no FMA contraction (the reference has none)
   -fno-gpu-flush-denormals-to-zero   IEEE f32 denormals, as numpy/numba
 """
+import glob
 import hashlib
 import json
 import os
@@ -16,8 +17,8 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 SRC = os.path.join(HERE, "csrc", "tdec_api.hip")
-DEPS = [SRC, os.path.join(HERE, "csrc", "tdec_kernels.hip"), os.path.join(HERE, "csrc", "tdec_workload.hip"), os.path.join(HERE, "csrc", "npmath.hip"),
-        os.path.join(HERE, "csrc", "tdec_spl.hip"), os.path.join(HERE, "csrc", "tdec_lowlat.hip"), os.path.join(HERE, "csrc", "tdec_frame.hip"),
+# every csrc/tdec_*.hip is part of the one translation unit that tdec_api.hip includes
+DEPS = [*sorted(glob.glob(os.path.join(HERE, "csrc", "tdec_*.hip"))), os.path.join(HERE, "csrc", "npmath.hip"),
         os.path.join(ROOT, "include", "tdec.h")]
 OUT = os.path.join(HERE, "lib", "libtdec.so")
 MODEM_SRC = os.path.join(HERE, "csrc", "modem_api.hip")

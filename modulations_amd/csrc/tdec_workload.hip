@@ -293,6 +293,53 @@ template <bool FADE> __device__ __forceinline__ void workload_tile(const Workloa
         if (ns) flush_syms<FADE>(p, f, base, lab, cons, ns, s0, lane);
     }
 }
+
+// ---- row encoder (encode, :404-462): one codeword per thread, for the N the staged encoder does not hold ----
+struct EncodeArgs {
+    int B, N, period;
+    long n_out;
+    unsigned char punct[16];
+    int circ[16];
+    const int *perm;
+    const uint8_t *bits;
+    uint8_t *coded;
+};
+
+__device__ __forceinline__ int next_rt(int s, int inp) {
+    const int dk = ((inp >> 1) & 1) ^ (inp & 1) ^ ((s >> 2) & 1) ^ ((s >> 3) & 1);
+    return (((s >> 2) & 1) << 3) | (((s >> 1) & 1) << 2) | ((s & 1) << 1) | dk;
+}
+
+__global__ __launch_bounds__(BLOCK) void k_encode(EncodeArgs p) {
+    const long cw = (long)blockIdx.x * BLOCK + threadIdx.x;
+    if (cw >= p.B) return;
+    const uint8_t *u = p.bits + cw * 2 * p.N;
+    uint8_t *o = p.coded + cw * p.n_out;
+    int s1 = 0, s2 = 0;
+    for (int i = 0; i < p.N; ++i) {
+        const int j = p.perm[i];
+        s1 = next_rt(s1, (u[2 * i] << 1) | u[2 * i + 1]);
+        s2 = next_rt(s2, (u[2 * j] << 1) | u[2 * j + 1]);
+    }
+    s1 = p.circ[s1];
+    s2 = p.circ[s2];
+    long q = 0;
+    for (int i = 0; i < p.N; ++i) {
+        const int j = p.perm[i], ph = i % p.period;
+        const int i1 = (u[2 * i] << 1) | u[2 * i + 1], i2 = (u[2 * j] << 1) | u[2 * j + 1];
+        const int dk1 = ((i1 >> 1) & 1) ^ (i1 & 1) ^ ((s1 >> 2) & 1) ^ ((s1 >> 3) & 1);
+        const int dk2 = ((i2 >> 1) & 1) ^ (i2 & 1) ^ ((s2 >> 2) & 1) ^ ((s2 >> 3) & 1);
+        o[q++] = u[2 * i];
+        o[q++] = u[2 * i + 1];
+        if (p.punct[0 * 4 + ph]) o[q++] = dk1 ^ (s1 & 1) ^ ((s1 >> 1) & 1) ^ ((s1 >> 3) & 1);
+        if (p.punct[1 * 4 + ph]) o[q++] = dk1 ^ ((s1 >> 1) & 1) ^ ((s1 >> 2) & 1) ^ ((s1 >> 3) & 1);
+        if (p.punct[2 * 4 + ph]) o[q++] = dk2 ^ (s2 & 1) ^ ((s2 >> 1) & 1) ^ ((s2 >> 3) & 1);
+        if (p.punct[3 * 4 + ph]) o[q++] = dk2 ^ ((s2 >> 1) & 1) ^ ((s2 >> 2) & 1) ^ ((s2 >> 3) & 1);
+        s1 = next_rt(s1, i1);
+        s2 = next_rt(s2, i2);
+    }
+}
+
 __global__ __launch_bounds__(64) void k_workload(WorkloadArgs p) { workload_tile<false>(p, FadeArgs{}); }
 
 // Bit errors of decoded rows against the counter-based info bits: one wave per

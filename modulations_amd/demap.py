@@ -146,31 +146,18 @@ def compute_llr(syms, mod_type, noise_var, sign=+1, device=0, algo="max-log"):
     return out
 
 
-def _rows_check(syms, nv, name="noise_var"):
-    """A per-row noise variance: a contiguous float64 [B] tensor on the device of the
-    2-D [B, S] complex symbols.  Refused here, before any device call."""
+def _nv_check(syms, nv, per, name="noise_var"):
+    """A per-row (per = "row") or per-symbol ("symbol") noise
+    variance: a contiguous float64 [B] or [B, S] tensor on the device of the 2-D [B, S]
+    complex symbols.  Refused here, before any device call."""
     import torch
     if not isinstance(syms, torch.Tensor) or syms.dim() != 2 or not syms.is_complex():
-        raise ValueError(f"a per-row {name} needs 2-D [B, S] complex symbols")
+        raise ValueError(f"a per-{per} {name} needs 2-D [B, S] complex symbols")
     if nv.dtype != torch.float64:
         raise TypeError(f"{name} must be torch.float64, got {nv.dtype}")
-    if tuple(nv.shape) != (syms.shape[0],) or not nv.is_contiguous():
-        raise ValueError(f"{name} must be a contiguous tensor of shape ({syms.shape[0]},), got {tuple(nv.shape)}")
-    if nv.device.type != "cuda" or nv.device != syms.device:
-        raise ValueError(f"{name} must be on the symbols' HIP device")
-
-
-def _syms_check(syms, nv, name="noise_var"):
-    """A per-symbol noise variance: a contiguous float64 [B, S]
-    tensor on the device of the 2-D [B, S] complex symbols.  Refused here, before any
-    device call."""
-    import torch
-    if not isinstance(syms, torch.Tensor) or syms.dim() != 2 or not syms.is_complex():
-        raise ValueError(f"a per-symbol {name} needs 2-D [B, S] complex symbols")
-    if nv.dtype != torch.float64:
-        raise TypeError(f"{name} must be torch.float64, got {nv.dtype}")
-    if tuple(nv.shape) != tuple(syms.shape) or not nv.is_contiguous():
-        raise ValueError(f"{name} must be a contiguous tensor of shape {tuple(syms.shape)}, got {tuple(nv.shape)}")
+    want = tuple(syms.shape) if per == "symbol" else (syms.shape[0],)
+    if tuple(nv.shape) != want or not nv.is_contiguous():
+        raise ValueError(f"{name} must be a contiguous tensor of shape {want}, got {tuple(nv.shape)}")
     if nv.device.type != "cuda" or nv.device != syms.device:
         raise ValueError(f"{name} must be on the symbols' HIP device")
 
@@ -179,9 +166,9 @@ def nv_tensor_form(syms, nv):
     """Which per-launch form a noise_var tensor is: "rows" ([B]) or "syms" ([B, S]), checked
     against the symbols."""
     if nv.dim() == 2:
-        _syms_check(syms, nv)
+        _nv_check(syms, nv, "symbol")
         return "syms"
-    _rows_check(syms, nv)
+    _nv_check(syms, nv, "row")
     return "rows"
 
 
@@ -209,7 +196,7 @@ def equalize_device(syms, h, noise_var, coh=1, out=None, nv_out=None, stream=Non
                          f"got {tuple(h.shape)}")
     rows = isinstance(noise_var, torch.Tensor)
     if rows:
-        _rows_check(syms, noise_var)
+        _nv_check(syms, noise_var, "row")
     if out is None:
         out = torch.empty_like(syms)
     elif out.dtype != torch.complex64 or tuple(out.shape) != (B, S) or not out.is_contiguous() or out.device != syms.device:
@@ -217,7 +204,7 @@ def equalize_device(syms, h, noise_var, coh=1, out=None, nv_out=None, stream=Non
     if nv_out is None:
         nv_out = torch.empty((B, S), dtype=torch.float64, device=syms.device)
     else:
-        _syms_check(syms, nv_out, "nv_out")
+        _nv_check(syms, nv_out, "symbol", "nv_out")
     dev = syms.device.index or 0
     st = _n.stream_ptr(stream) if stream is not None else torch.cuda.current_stream(dev).cuda_stream
     _n.check(_n.lib().tdec_equalize_dev(dev, _n.ptr(syms), _n.ptr(h), B, S, coh, 0.0 if rows else float(noise_var),
@@ -243,7 +230,7 @@ def estimate_noise_var_device(syms, mod_type, floor=0.02, out=None, stream=None)
     if out is None:
         out = torch.empty(B, dtype=torch.float64, device=syms.device)
     else:
-        _rows_check(syms, out, "out")
+        _nv_check(syms, out, "row", "out")
     f64 = cons.dtype == np.complex128
     c = np.ascontiguousarray(cons.astype(np.complex128 if f64 else np.complex64))
     dev = syms.device.index or 0

@@ -110,16 +110,16 @@ def decode_llr(codec, family, seed, stretch=STRETCH):
 
 
 # ---- the shortcuts' constants, restated, and the depth classes they define -------------
-RING = 16        # modulations_amd/csrc/tdec_kernels.hip:873  beta1 kept at RING window starts
+RING = 16        # modulations_amd/csrc/tdec_kernels.hip RING  beta1 kept at RING window starts
 
 
-def rstep_of(w):  # tdec_kernels.hip:874  siso<0, W>: every rstep-th window start is kept
+def rstep_of(w):  # tdec_kernels.hip rstep_of  siso<0, W>: every rstep-th window start is kept
     return 1 if w >= 16 else 16 // w
 
 
-CK8 = 8          # tdec_kernels.hip:1168  siso8's window step / checkpoint interval (WS, CK)
-RSTEP8 = 2       # tdec_kernels.hip:1133  siso8 keeps every 2nd window start
-WIN = 4          # tdec_kernels.hip:1281  the row SISO runs siso<0, 4>; tdec_spl.hip:17 SPL_W = 4, :173 rw % 4
+CK8 = 8          # tdec_kernels.hip siso8 (WS, CK)  siso8's window step / checkpoint interval (WS, CK)
+RSTEP8 = 2       # tdec_kernels.hip RSTEP8  siso8 keeps every 2nd window start
+WIN = 4          # tdec_kernels.hip WIN  the row SISO runs siso<0, 4>; tdec_spl.hip SPL_W = 4, k_siso_spl rw % 4
 FR_LMIN = 32     # modulations_amd/csrc/tdec_frame.hip:66
 
 
@@ -130,8 +130,8 @@ def fr_seg_len(n, p):   # tdec_frame.hip:67-71
 
 def b2_checks(n, w, rstep):
     """The depths d (steps from the top) at which a backward second pass with
-    w-step windows compares beta2 with the kept beta1 (tdec_kernels.hip:977-987,
-    :1244-1257, tdec_spl.hip:171-177): the entry of window r = 0, rstep, 2 rstep, ...
+    w-step windows compares beta2 with the kept beta1 (tdec_kernels.hip siso and siso8,
+    their `keep` loops; tdec_spl.hip k_siso_spl): the entry of window r = 0, rstep, 2 rstep, ...
     below RING * rstep; the top window may be short."""
     top = (n - 1) // w * w
     n_win = top // w + 1

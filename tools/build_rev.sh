@@ -1,12 +1,13 @@
 #!/bin/bash
 # Build libtdec.so from the sources of a git revision (for in-process A/B with tools/ab.py):
 #   tools/build_rev.sh <rev> <name> [-DDEFINE ...]  ->  modulations_amd/lib/libtdec_<name>.so
+# The file list is the revision's own csrc listing, so older and newer layouts both build.
 set -euo pipefail
 rev=$1; name=$2; shift 2
 d=$(mktemp -d)
-mkdir -p $d/csrc $d/include
-for f in tdec_api.hip tdec_kernels.hip tdec_workload.hip tdec_spl.hip tdec_lowlat.hip tdec_frame.hip npmath.hip; do
-  git show $rev:modulations_amd/csrc/$f > $d/csrc/$f 2>/dev/null || rm -f $d/csrc/$f
+mkdir -p $d/csrc $d/include modulations_amd/lib
+for f in $(git ls-tree --name-only $rev modulations_amd/csrc/ | grep -E '/(tdec_[^/]*|npmath)\.hip$'); do
+  git show $rev:$f > $d/csrc/$(basename $f)
 done
 git show $rev:include/tdec.h > $d/include/tdec.h
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -shared -ffp-contract=off \

@@ -8,8 +8,7 @@ round in both orders, plus the estimator (tdec_noise_var_dev) and the equaliser
 
   python tools/demap_rownv_measure.py [--mods 16QAM 256QAM --batch 1048576 --rounds 5] [--out f.json]
 
-TDEC_LIB_VARIANT=<name> measures a side-by-side build (build.py --variant), e.g. the
-LDS staging of a tile's 64 values (-DDM_ROWNV_LDS=1)."""
+TDEC_LIB_VARIANT=<name> measures a side-by-side build (build.py --variant)."""
 import argparse
 import json
 import os
