@@ -343,6 +343,41 @@ int tdec_symnv_demap_planes_logmap_dev(tdec_t *h, int B, const float *d_syms, in
 int tdec_equalize_dev(int device, const float *d_y, const float *d_h, int B, int S, int coh, double noise_var,
                       const double *d_noise_var, float *d_z, double *d_nv_sym, void *stream);
 
+/* ---- pilot-aided channel estimation (build-defined) ----
+ * A framed burst of S data symbols carries J + 1 pilot blocks of plen symbols around
+ * J = ceil(S / dlen) data segments, P0 D0 P1 D1 ... D(J-1) PJ, T = S + (J + 1) plen
+ * positions; segment j holds data symbols [j dlen, min((j + 1) dlen, S)), L_j of them (only
+ * the last may be short).  d_frames: complex64 [B][T]; d_pilots: the known sequence,
+ * complex64 [(J + 1) plen] on the device, shared by all rows, every block of non-zero energy
+ * (the caller's to check: a zero-energy block gives a non-finite gain, and so erasures).
+ * One launch, one block per row, every sum in f64 without contraction in this order:
+ *   hp[j] = (nr / e, ni / e),  over i = 0 .. plen-1 in turn from 0.0:
+ *           nr += yr*pr + yi*pi,  ni += yi*pr - yr*pi,  e += pr*pr + pi*pi
+ *   q_j   = sum_i (dr*dr + di*di),  d = y_i - (hr*pr - hi*pi, hr*pi + hi*pr)
+ *   nv[r] = max_py((q_0 + q_1 + ...) / ((J + 1)(plen - 1)), floor)        (plen >= 2 only)
+ *   data u of segment j, a = hp[j], b = hp[j + 1]:
+ *           w = (double)(2u + plen + 1) / (double)(2 (plen + L_j)),  TDEC_CSI_MEAN: w = 0.5
+ *           h = (float)(ar + w (br - ar)), (float)(ai + w (bi - ai));  0 + 0j when a or b is
+ *           exactly zero (a block that received nothing vouches for neither neighbour)
+ * then z and nv_sym are tdec_equalize_dev's for (y, h, nv_r): complex64 [B][S] and f64
+ * [B][S], erasures (z = 0, nv_sym = +inf) where |h|^2 is zero or not finite, so a
+ * non-finite pilot erases the segments it borders.  nv_r is d_nv_rows_in[r] (f64 [B]) when
+ * that is not null, else noise_var when it is not negative (NaN counts as given), else the
+ * estimate nv[r].  d_h (nullable): the interpolated gains, complex64 [B][S]; d_nv_out
+ * (nullable, plen >= 2): nv[r], f64 [B], formed whichever source equalises.  A row's
+ * values depend on neither B nor the grid.  TDEC_EINVAL: a null required pointer; B, S,
+ * plen or dlen < 1; an unknown mode; d_nv_out with plen == 1; no noise source (plen == 1,
+ * no d_nv_rows_in, noise_var < 0).  TDEC_EUNSUPPORTED: more than 2048 pilot blocks. */
+enum { TDEC_CSI_LINEAR = 0, TDEC_CSI_MEAN = 1 };
+int tdec_csi_pilots_dev(int device, const float *d_frames, int B, int S, int plen, int dlen, const float *d_pilots,
+                        int mode, double noise_var, const double *d_nv_rows_in, double floor, float *d_z,
+                        double *d_nv_sym, float *d_h, double *d_nv_out, void *stream);
+/* The unfused form: the stripped data d_y complex64 [B][S] and the gains d_h [B][S] (both
+ * required), and nv[r] into d_nv_out when asked; tdec_equalize_dev with coh = 1 behind it
+ * writes what the fused call writes, bit for bit. */
+int tdec_csi_strip_dev(int device, const float *d_frames, int B, int S, int plen, int dlen, const float *d_pilots,
+                       int mode, double floor, float *d_y, float *d_h, double *d_nv_out, void *stream);
+
 /* Fused soft demap + turbo decode (one launch): what tdec_demap_planes_dev +
  * tdec_decode_planes_dev compute, bit for bit, with each persistent decoder wave
  * demapping its own next tile into a per-wave plane buffer.  Instantiated for
@@ -398,6 +433,21 @@ int tdec_workload_dev(tdec_t *h, int B, int64_t cw0, uint64_t seed, const float 
 int tdec_workload_fading_dev(tdec_t *h, int B, int64_t cw0, uint64_t seed, const float *cons_iq, int M, int bps,
                              double sigma, double rician_k, int coh, float *d_syms, float *d_h, uint8_t *d_info,
                              void *stream);
+/* Frames of that call's output with pilot blocks (the layout of tdec_csi_pilots_dev, DESIGN.md
+ * §13).  d_y complex64 [B][S] and d_gains complex64 [B][ceil(S / coh)] as written by
+ * tdec_workload_fading_dev with the same cw0, seed and sigma; d_pilots complex64
+ * [(J + 1) plen] on the device; d_frames complex64 [B][T]; d_h_true (nullable) complex64
+ * [B][T], the gain each position went through.  Data positions copy their symbol.  Pilot i
+ * of block j is h p + n: h the gain of data symbol min(j dlen, S - 1), h p formed in f64
+ * and rounded to f32, n Box-Muller noise of sigma per dimension on
+ * philox4x32_10({g_lo, g_hi, (j plen + i) / 2, 0x4D6C}, seed), the data noise's mapping.
+ * cfo_max > 0: position t of global codeword g is then multiplied by exp(j 2 pi f_g t),
+ * f_g = cfo_max (2u - 1) cycles per symbol, u = ((x >> 8) + 0.5) 2^-24 of word x of
+ * philox4x32_10({g_lo, g_hi, 0, 0x5E7B}, seed); angle and sincospi in f64, the product
+ * rounded to f32; d_h_true carries the rotation.  cfo_max == 0: no multiply. */
+int tdec_workload_frame_dev(int device, const float *d_y, const float *d_gains, int B, int S, int coh, int plen,
+                            int dlen, const float *d_pilots, double sigma, int64_t cw0, uint64_t seed, double cfo_max,
+                            float *d_frames, float *d_h_true, void *stream);
 /* The info bits alone: uint8 [B][2N] of 0/1. */
 int tdec_info_bits_dev(tdec_t *h, int B, int64_t cw0, uint64_t seed, uint8_t *d_info, void *stream);
 /* Bit errors per codeword of decoded rows (int32 [B][2N], tdec_decode_*) against

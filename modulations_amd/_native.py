@@ -41,6 +41,7 @@ EXPORTS = (
     "tdec_demap_planes_logmap_nv_dev",
     "tdec_symnv_demap_dev", "tdec_symnv_demap_logmap_dev", "tdec_symnv_demap_planes_dev",
     "tdec_symnv_demap_planes_logmap_dev", "tdec_equalize_dev", "tdec_workload_fading_dev",
+    "tdec_csi_pilots_dev", "tdec_csi_strip_dev", "tdec_workload_frame_dev",
 )
 
 _lib = None
@@ -142,6 +143,15 @@ def _declare(L):
                                                C.c_double, C.c_int, _vp, _vp, _vp, _vp]
         for f in (L.tdec_symnv_demap_dev, L.tdec_symnv_demap_logmap_dev, L.tdec_symnv_demap_planes_dev,
                   L.tdec_symnv_demap_planes_logmap_dev, L.tdec_equalize_dev, L.tdec_workload_fading_dev):
+            f.restype = C.c_int
+    if hasattr(L, "tdec_csi_pilots_dev"):   # (A/B tools also load older builds without the pilot estimator)
+        L.tdec_csi_pilots_dev.argtypes = [C.c_int, _vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, C.c_int, C.c_double,
+                                          _vp, C.c_double, _vp, _vp, _vp, _vp, _vp]
+        L.tdec_csi_strip_dev.argtypes = [C.c_int, _vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, C.c_int, C.c_double,
+                                         _vp, _vp, _vp, _vp]
+        L.tdec_workload_frame_dev.argtypes = [C.c_int, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp,
+                                              C.c_double, C.c_int64, C.c_uint64, C.c_double, _vp, _vp, _vp]
+        for f in (L.tdec_csi_pilots_dev, L.tdec_csi_strip_dev, L.tdec_workload_frame_dev):
             f.restype = C.c_int
     L.tdec_encode_dev.argtypes = [_vp, C.c_int, _vp, _vp, _vp]
     L.tdec_demap_batch.argtypes = [C.c_int, C.c_int, C.c_int, _vp, C.c_long, C.c_float, _vp]

@@ -24,6 +24,12 @@ channel with known gains: the generator multiplies each symbol 
 its gain (E|h|^2 = 1, one gain per --coherence symbols of a codeword), and the
 pipeline equalises and demaps with the per-symbol noise variance N0 / |h|^2.  The
 bits and the noise are those of the AWGN sweep with the same seed.
+
+--csi pilots (fading channels) frames each burst with pilot blocks
+(--pilot-len symbols every --pilot-spacing data symbols, --cfo cycles per symbol of residual
+carrier rotation at most) and lets the pipeline estimate the gains from them, with the
+noise variance known (--csi-noise known) or estimated from the pilots as well (pilots).
+The pilots' energy is not charged to Eb/N0.
 """
 from __future__ import annotations
 
@@ -64,6 +70,9 @@ def sweep_config(a, inv_perm=None):
         cfg["channel"] = a.channel
         cfg["rician_k"] = fading["K"]
         cfg["coherence"] = fading["coh"]
+        if getattr(a, "csi", "known") == "pilots":   # (absent at the default, likewise)
+            cfg.update(csi="pilots", pilot_len=int(a.pilot_len), pilot_spacing=int(a.pilot_spacing),
+                       cfo=float(a.cfo), csi_noise=a.csi_noise)
     if inv_perm is not None:
         cfg["inv_perm_digest"] = interleaver_digest(inv_perm)
     return cfg
@@ -110,7 +119,8 @@ def parse_points(spec):
     return [float(x) for x in spec.split(",")]
 
 
-def run_point(pipe, codec, mod, ebn0, start, count, batch, seed, device, times=None, iter_hist=None, fading=None):
+def run_point(pipe, codec, mod, ebn0, start, count, batch, seed, device, times=None, iter_hist=None, fading=None,
+              pilots=None):
     """Bit errors, frame errors and codewords of global codewords
     [start, start + count) at one Eb/N0 point.  The data of codeword g is a
     counter-based stream of (seed, g) (workload.make_symbols), so the counters
@@ -120,7 +130,9 @@ def run_point(pipe, codec, mod, ebn0, start, count, batch, seed, device, times=N
     error counting.  iter_hist (an int64 [iterations + 1] device tensor, optional;
     early-stop pipelines): entry i gains the codewords that ran i iterations.
     fading (make_symbols' dict, optional): the flat-fading channel; the pipeline (built
-    with csi=True) equalises with the generator's gains."""
+    with csi=True) equalises with the generator's gains.  pilots (optional, with fading):
+    {"layout": demap.PilotLayout, "cfo": cycles per symbol, "noise": "known" | "pilots"}: the
+    bursts are framed and the pipeline estimates the gains (and the noise) from the pilots."""
     import torch
     from . import sharding as S
     from .workload import count_errors, make_symbols
@@ -130,13 +142,20 @@ def run_point(pipe, codec, mod, ebn0, start, count, batch, seed, device, times=N
         csi = {}
         if fading is None:
             _, syms, n0 = make_symbols(codec, n, mod, ebn0, seed, device, cw0=start + off, want_info=False)
+        elif pilots is not None:
+            _, syms, n0, _ = make_symbols(codec, n, mod, ebn0, seed, device, cw0=start + off, want_info=False,
+                                          fading=fading, pilots=pilots["layout"], cfo=pilots["cfo"])
         else:
             _, syms, n0, gains = make_symbols(codec, n, mod, ebn0, seed, device, cw0=start + off, want_info=False,
                                               fading=fading)
             csi = {"csi": gains, "coh": fading["coh"]}
         e3 = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
         e3[0].record()
-        bits = pipe.run(syms, n0, events=e3[1:], **csi)[:n]
+        if pilots is not None:
+            bits = pipe.run_frames(syms, pilots["layout"], n0 if pilots["noise"] == "known" else None,
+                                   events=e3[1:])[:n]
+        else:
+            bits = pipe.run(syms, n0, events=e3[1:], **csi)[:n]
         ev.append(e3)
         e = count_errors(codec, bits, seed, cw0=start + off)
         if iter_hist is not None:
@@ -176,6 +195,15 @@ def arg_parser():
     ap.add_argument("--coherence", type=int, default=1,
                     help="fading channels: symbols per gain (1: fast fading; >= the symbols of a codeword: "
                          "one gain per burst)")
+    ap.add_argument("--csi", choices=["known", "pilots"], default="known",
+                    help="fading channels: equalise with the generator's gains, or frame the bursts with pilot "
+                         "blocks and estimate the gains from them")
+    ap.add_argument("--pilot-len", type=int, default=4, help="--csi pilots: symbols per pilot block")
+    ap.add_argument("--pilot-spacing", type=int, default=47, help="--csi pilots: data symbols between pilot blocks")
+    ap.add_argument("--cfo", type=float, default=0.0,
+                    help="--csi pilots: residual carrier rotation, uniform in (-cfo, cfo) cycles per symbol per burst")
+    ap.add_argument("--csi-noise", choices=["known", "pilots"], default="known",
+                    help="--csi pilots: the noise variance is N0, or each burst's estimate from its pilots")
     ap.add_argument("--out", default=None)
     ap.add_argument("--dist-backend", default="nccl", help="nccl (= RCCL) on the node; gloo to rehearse")
     ap.add_argument("--all-on-device0", action="store_true", help="every rank on GPU 0 (rehearsal on a 1-GPU box)")
@@ -195,6 +223,16 @@ def main(argv=None):
     if a.coherence < 1 or not (0.0 <= a.rician_k < float("inf")):
         ap.error("--coherence must be >= 1 and --rician-k a finite value >= 0")
     fading = channel_fading(a)
+    pilots = None
+    if a.csi == "pilots":
+        from .demap import PilotLayout
+        if fading is None:
+            ap.error("--csi pilots needs a fading --channel")
+        if a.pilot_len < 1 or a.pilot_spacing < 1 or not (0.0 <= a.cfo < float("inf")):
+            ap.error("--pilot-len and --pilot-spacing must be >= 1 and --cfo a finite value >= 0")
+        if a.csi_noise == "pilots" and a.pilot_len < 2:
+            ap.error("--csi-noise pilots needs --pilot-len >= 2")
+        pilots = {"layout": PilotLayout(a.pilot_len, a.pilot_spacing), "cfo": a.cfo, "noise": a.csi_noise}
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -230,7 +268,7 @@ def main(argv=None):
     results = list(done.values())
     # one untimed batch first: code-object loading and first-launch costs stay out of
     # the first point's figures
-    run_point(pipe, codec, a.mod, 2.0, 0, min(a.batch, 65536), a.batch, a.seed, device, fading=fading)
+    run_point(pipe, codec, a.mod, 2.0, 0, min(a.batch, 65536), a.batch, a.seed, device, fading=fading, pilots=pilots)
     for e in parse_points(a.ebn0):
         if e in done:
             continue
@@ -239,7 +277,7 @@ def main(argv=None):
         times = []
         hist = torch.zeros(a.iterations + 1, dtype=torch.int64, device=device) if a.early_stop else None
         cnt = run_point(pipe, codec, a.mod, e, start, count, a.batch, ebn0_seed(a.seed, e), device, times, hist,
-                        fading=fading)
+                        fading=fading, pilots=pilots)
         if hist is not None:
             cnt = torch.cat([cnt, hist])   # one reduction for the error counters and the histogram
         if world > 1 and a.dist_backend != "nccl":
@@ -260,6 +298,9 @@ def main(argv=None):
             rec["demap"] = a.demap
         if fading is not None:
             rec.update(channel=a.channel, rician_k=fading["K"], coherence=fading["coh"])
+        if pilots is not None:
+            rec.update(csi="pilots", pilot_len=a.pilot_len, pilot_spacing=a.pilot_spacing, cfo=a.cfo,
+                       csi_noise=a.csi_noise)
         if a.early_stop:
             h = [int(x) for x in cnt[3:].tolist()]
             rec["early_stop"] = True

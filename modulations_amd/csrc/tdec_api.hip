@@ -68,6 +68,7 @@ namespace {
     FLATS(1) PLANES(LM_ML, LM_ML_SPLIT, 1) (void)k_noise_var<double>, (void)k_noise_var<float>;   // per row
     FLATS(2) PLANES(LM_ML, LM_ML_SPLIT, 2)                                                         // per symbol
     (void)k_equalize<true, true>, (void)k_equalize<true, false>, (void)k_equalize<false, true>, (void)k_equalize<false, false>;
+    (void)k_csi_pilots<true>, (void)k_csi_pilots<false>, (void)k_workload_frame<false>, (void)k_workload_frame<true>;   // pilots (§13)
 }
 #undef EACH_BPS
 #undef BOTH
@@ -2060,6 +2061,32 @@ int tdec_workload_fading_dev(tdec_t *h, int B, int64_t cw0, uint64_t seed, const
     f.los = (float)std::sqrt(rician_k / (rician_k + 1.0));
     f.scat = (float)std::sqrt(1.0 / (rician_k + 1.0));
     hipLaunchKernelGGL(k_workload_fading, dim3((unsigned)n_tiles_of(B)), dim3(64), 0, (hipStream_t)stream, a, f);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+int tdec_workload_frame_dev(int device, const float *d_y, const float *d_gains, int B, int S, int coh, int plen,
+                            int dlen, const float *d_pilots, double sigma, int64_t cw0, uint64_t seed, double cfo_max,
+                            float *d_frames, float *d_h_true, void *stream) {
+    if (B < 0 || cw0 < 0) return fail(TDEC_EINVAL, "bad frame arguments");
+    if (B == 0) return 0;
+    if (!d_y || !d_gains || !d_pilots || !d_frames || S < 1 || coh < 1 || plen < 1 || dlen < 1 || !(sigma >= 0.0) ||
+        !(cfo_max >= 0.0) || !(cfo_max < INFINITY))
+        return fail(TDEC_EINVAL, "bad frame arguments (S, coh, plen, dlen >= 1; sigma >= 0; finite cfo_max >= 0)");
+    const int J = (S + dlen - 1) / dlen;
+    const long T = (long)S + (long)(J + 1) * plen;
+    if (T > INT32_MAX) return fail(TDEC_EINVAL, "bad frame arguments (frame too long)");
+    Guard g(device);
+    FrameArgs f{};
+    f.y = reinterpret_cast<const float2 *>(d_y);
+    f.gains = reinterpret_cast<const float2 *>(d_gains);
+    f.pilots = reinterpret_cast<const float2 *>(d_pilots);
+    f.B = B, f.S = S, f.coh = coh, f.nh = (S + coh - 1) / coh, f.plen = plen, f.dlen = dlen, f.J = J, f.T = (int)T;
+    f.cw0 = (uint64_t)cw0, f.seed = seed, f.sigma = (float)sigma, f.cfo_max = cfo_max;
+    f.frames = reinterpret_cast<float2 *>(d_frames), f.h_true = reinterpret_cast<float2 *>(d_h_true);
+    const dim3 grid((unsigned)(((long)B * T + BLOCK - 1) / BLOCK));
+    if (cfo_max > 0.0) hipLaunchKernelGGL(k_workload_frame<true>, grid, dim3(BLOCK), 0, (hipStream_t)stream, f);
+    else hipLaunchKernelGGL(k_workload_frame<false>, grid, dim3(BLOCK), 0, (hipStream_t)stream, f);
     HIPCHK(hipGetLastError());
     return 0;
 }

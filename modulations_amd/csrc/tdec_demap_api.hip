@@ -223,6 +223,44 @@ void launch_equalize(bool vec, const float2 *y, const float2 *hh, long n_sym, in
     }
 }
 
+// k_csi_pilots, one block per framed row.  EQ: estimate + equalise into z and
+// nv_sym with the row's noise variance from d_nv_rows (when not null), else noise_var (when not
+// negative), else the pilots' own estimate; !EQ: the stripped data and the interpolated gains.
+// The residual estimate is formed when it is the noise source or d_nv_out asks for it.
+constexpr int CSI_MAX_BLOCKS = 2048;   // pilot blocks per row whose gains and residuals LDS holds (48 KiB)
+template <bool EQ>
+int csi_pilots(int device, const float *d_frames, int B, int S, int plen, int dlen, const float *d_pilots, int mode,
+               double noise_var, const double *d_nv_rows, double floor, float *d_z, double *d_nv_sym, float *d_h,
+               double *d_nv_out, void *stream) {
+    if (B < 1 || S < 1 || plen < 1 || dlen < 1) return fail(TDEC_EINVAL, "csi_pilots: B, S, plen and dlen must be >= 1");
+    if (mode != TDEC_CSI_LINEAR && mode != TDEC_CSI_MEAN) return fail(TDEC_EINVAL, "csi_pilots: unknown interpolation mode");
+    if (d_nv_out && plen < 2) return fail(TDEC_EINVAL, "csi_pilots: a noise estimate needs plen >= 2");
+    const int nv_src = !EQ ? 0 : (d_nv_rows ? 1 : (!(noise_var < 0.0) ? 0 : 2));
+    if (nv_src == 2 && plen < 2) return fail(TDEC_EINVAL, "csi_pilots: no noise source (plen == 1 and no noise_var)");
+    const int J = (S + dlen - 1) / dlen;
+    if (J + 1 > CSI_MAX_BLOCKS) return fail(TDEC_EUNSUPPORTED, "csi_pilots: more than 2048 pilot blocks per burst");
+    const long T = (long)S + (long)(J + 1) * plen;
+    if (T > INT32_MAX) return fail(TDEC_EINVAL, "csi_pilots: frame too long");
+    Guard g(device);
+    CsiArgs a{};
+    a.frames = reinterpret_cast<const float2 *>(d_frames);
+    a.pilots = reinterpret_cast<const float2 *>(d_pilots);
+    a.S = S, a.plen = plen, a.dlen = dlen, a.J = J, a.T = (int)T;
+    a.mean = mode == TDEC_CSI_MEAN;
+    a.estimate = nv_src == 2 || d_nv_out != nullptr;
+    a.nv_src = nv_src;
+    a.nv = noise_var, a.floor_nv = floor, a.nvs = d_nv_rows;
+    a.z = reinterpret_cast<float2 *>(d_z), a.nv_sym = d_nv_sym, a.h = reinterpret_cast<float2 *>(d_h), a.nv_out = d_nv_out;
+    // 16-byte stores where every output has the same address modulo 16 (their elements are 8 bytes)
+    const uintptr_t z0 = (uintptr_t)d_z & 15;
+    a.vec = (z0 & 7) == 0 && (!d_nv_sym || ((uintptr_t)d_nv_sym & 15) == z0) && (!d_h || ((uintptr_t)d_h & 15) == z0);
+    a.odd0 = z0 == 8;
+    const size_t lds = (3 * (size_t)(J + 1) + 1) * sizeof(double);
+    hipLaunchKernelGGL((k_csi_pilots<EQ>), dim3((unsigned)B), dim3(BLOCK), lds, (hipStream_t)stream, a);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
 }  // namespace
 
 // ---- exported calls ---------------------------------------------------------------------
@@ -350,6 +388,22 @@ int tdec_equalize_dev(int device, const float *d_y, const float *d_h, int B, int
     else launch_equalize<false>(vec, y, hh, n_sym, S, coh, nh, noise_var, nullptr, z, d_nv_sym, (hipStream_t)stream);
     HIPCHK(hipGetLastError());
     return 0;
+}
+
+// pilot-aided channel estimation
+int tdec_csi_pilots_dev(int device, const float *d_frames, int B, int S, int plen, int dlen, const float *d_pilots,
+                        int mode, double noise_var, const double *d_nv_rows_in, double floor, float *d_z,
+                        double *d_nv_sym, float *d_h, double *d_nv_out, void *stream) {
+    if (!d_frames || !d_pilots || !d_z || !d_nv_sym) return fail(TDEC_EINVAL, "csi_pilots: null pointer");
+    return csi_pilots<true>(device, d_frames, B, S, plen, dlen, d_pilots, mode, noise_var, d_nv_rows_in, floor, d_z,
+                            d_nv_sym, d_h, d_nv_out, stream);
+}
+
+int tdec_csi_strip_dev(int device, const float *d_frames, int B, int S, int plen, int dlen, const float *d_pilots,
+                       int mode, double floor, float *d_y, float *d_h, double *d_nv_out, void *stream) {
+    if (!d_frames || !d_pilots || !d_y || !d_h) return fail(TDEC_EINVAL, "csi_strip: null pointer");
+    return csi_pilots<false>(device, d_frames, B, S, plen, dlen, d_pilots, mode, -1.0, nullptr, floor, d_y, nullptr,
+                             d_h, d_nv_out, stream);
 }
 
 #if TDEC_DM_STATS

@@ -1382,4 +1382,145 @@ __global__ __launch_bounds__(BLOCK) void k_trans_table(int which, unsigned lo, l
     out[i] = which == 0 ? hw_exp2(-x) : hw_log2(x);
 }
 
+// ---- pilot-aided channel estimation (build-defined) ----------------------
+// A framed burst of S data symbols: J = ceil(S / dlen) data segments between J + 1 pilot
+// blocks of plen symbols, P0 D0 P1 D1 ... D(J-1) PJ, T = S + (J + 1) plen positions; segment
+// j holds data symbols [j dlen, min((j + 1) dlen, S)), L_j of them.  One block per row of
+// [B][T] complex64 frames, all arithmetic f64 without contraction, every order fixed:
+//   block gain  hp[j] = (nr / e, ni / e) over i = 0 .. plen-1 in turn, sums from 0.0:
+//               nr += yr*pr + yi*pi,  ni += yi*pr - yr*pi,  e += pr*pr + pi*pi
+//   residual    q_j = sum_i (dr*dr + di*di), d = y_i - (hr*pr - hi*pi, hr*pi + hi*pr)
+//   row noise   nv = max_py((q_0 + q_1 + ...) / ((J + 1)(plen - 1)), floor)   (plen >= 2)
+//   data u of segment j, a = hp[j], b = hp[j + 1]:
+//               w = (double)(2u + plen + 1) / (double)(2 (plen + L_j))   (mean: w = 0.5)
+//               h = (float2)(ar + w (br - ar), ai + w (bi - ai)); (0, 0) if a or b is exactly 0
+//   EQ:         eq_symbol(y, h, nv_r) -> z, nv_sym;   else y and h are written as they are.
+// Thread t forms the gains (and residuals) of pilot blocks t, t + BLOCK, ... into LDS and
+// thread 0 adds the residuals in block order, so a row's values depend on neither B nor the
+// grid.  The frame is read 8 bytes at a time (T is odd in general: no row alignment to
+// speak of); with `vec` (the host checks that every output has the same address modulo 16)
+// a thread owns the two symbols of one aligned 16-byte slot of each output row and stores
+// them at once, the row's first or last symbol alone where the slot straddles the row's end.
+struct CsiArgs {
+    const float2 *frames;                      // [B][T]
+    const float2 *pilots;                      // [(J + 1) plen]
+    int S, plen, dlen, J, T;
+    int mean;                                  // 1: w = 0.5
+    int estimate;                              // 1: form q_j and the row's nv
+    int nv_src;                                // the equaliser's nv_r: 0 nv, 1 nvs[r], 2 the estimate
+    int vec, odd0;                             // 16-byte stores; the outputs' base is 8 modulo 16
+    double nv, floor_nv;
+    const double *nvs;                         // [B]
+    float2 *z;                                 // [B][S]: z (EQ) or the stripped y
+    double *nv_sym;                            // [B][S] (EQ)
+    float2 *h;                                 // [B][S] (nullable with EQ)
+    double *nv_out;                            // [B] (nullable)
+};
+
+template <bool EQ>
+__global__ __launch_bounds__(BLOCK) void k_csi_pilots(CsiArgs a) {
+    extern __shared__ __attribute__((aligned(16))) double csi_lds[];
+    const int nb = a.J + 1;
+    double2 *hp = reinterpret_cast<double2 *>(csi_lds);   // [nb]
+    double *q = csi_lds + 2 * nb;                         // [nb], then the row's nv
+    const long r = blockIdx.x;
+    const float2 *row = a.frames + r * (long)a.T;
+    for (int j = threadIdx.x; j < nb; j += BLOCK) {
+        // block j starts behind j segments, all full but perhaps the last: at S + J plen for j = J
+        const long t0 = j < a.J ? (long)j * (a.plen + a.dlen) : (long)a.S + (long)a.J * a.plen;
+        const float2 *y = row + t0, *p = a.pilots + (long)j * a.plen;
+        double nr = 0.0, ni = 0.0, e = 0.0;
+        for (int i = 0; i < a.plen; ++i) {
+            const double yr = (double)y[i].x, yi = (double)y[i].y, pr = (double)p[i].x, pi = (double)p[i].y;
+            nr += yr * pr + yi * pi;
+            ni += yi * pr - yr * pi;
+            e += pr * pr + pi * pi;
+        }
+        const double hr = nr / e, hi = ni / e;
+        hp[j] = make_double2(hr, hi);
+        if (a.estimate) {
+            double qq = 0.0;
+            for (int i = 0; i < a.plen; ++i) {
+                const double pr = (double)p[i].x, pi = (double)p[i].y;
+                const double dr = (double)y[i].x - (hr * pr - hi * pi), di = (double)y[i].y - (hr * pi + hi * pr);
+                qq += dr * dr + di * di;
+            }
+            q[j] = qq;
+        }
+    }
+    __syncthreads();
+    if (a.estimate) {   // uniform
+        if (threadIdx.x == 0) {
+            double sum = q[0];
+            for (int j = 1; j < nb; ++j) sum += q[j];
+            const double mean = sum / (double)((long)nb * (a.plen - 1));
+            const double v = (a.floor_nv > mean) ? a.floor_nv : mean;
+            q[nb] = v;
+            if (a.nv_out) a.nv_out[r] = v;
+        }
+        __syncthreads();
+    }
+    const double nv_r = a.nv_src == 2 ? q[nb] : (a.nv_src == 1 ? a.nvs[r] : a.nv);
+    struct Sym {
+        float2 y, h;
+    };
+    auto at = [&](int s) -> Sym {   // 0 <= s < S
+        const int j = s / a.dlen, u = s - j * a.dlen;
+        const int L = min(a.dlen, a.S - j * a.dlen);
+        const float2 y = row[(long)s + (long)(j + 1) * a.plen];
+        const double2 A = hp[j], Bq = hp[j + 1];
+        const double w = a.mean ? 0.5 : (double)(2 * u + a.plen + 1) / (double)(2 * (a.plen + L));
+        float2 h = make_float2((float)(A.x + w * (Bq.x - A.x)), (float)(A.y + w * (Bq.y - A.y)));
+        if ((A.x == 0.0 && A.y == 0.0) || (Bq.x == 0.0 && Bq.y == 0.0)) h = make_float2(0.0f, 0.0f);
+        return Sym{y, h};
+    };
+    const long o = r * (long)a.S;
+    if (a.vec) {
+        // slot k of the row: symbols 2k - a0 and 2k - a0 + 1, a0 = 1 when the row starts in the
+        // upper half of a 16-byte slot
+        const int a0 = (int)((o + a.odd0) & 1);
+        const int n_slots = (a.S + a0 + 1) / 2;
+        for (int k = threadIdx.x; k < n_slots; k += BLOCK) {
+            const int s0 = 2 * k - a0;
+            if (s0 >= 0 && s0 + 1 < a.S) {
+                const Sym u0 = at(s0), u1 = at(s0 + 1);
+                if constexpr (EQ) {
+                    const EqOut e0 = eq_symbol(u0.y, u0.h, nv_r), e1 = eq_symbol(u1.y, u1.h, nv_r);
+                    *reinterpret_cast<float4 *>(a.z + o + s0) = make_float4(e0.zr, e0.zi, e1.zr, e1.zi);
+                    *reinterpret_cast<double2 *>(a.nv_sym + o + s0) = make_double2(e0.nv, e1.nv);
+                    if (a.h) *reinterpret_cast<float4 *>(a.h + o + s0) = make_float4(u0.h.x, u0.h.y, u1.h.x, u1.h.y);
+                } else {
+                    *reinterpret_cast<float4 *>(a.z + o + s0) = make_float4(u0.y.x, u0.y.y, u1.y.x, u1.y.y);
+                    *reinterpret_cast<float4 *>(a.h + o + s0) = make_float4(u0.h.x, u0.h.y, u1.h.x, u1.h.y);
+                }
+            } else {
+                const int s = s0 >= 0 ? s0 : s0 + 1;   // the row's last symbol, or its first
+                const Sym u0 = at(s);
+                if constexpr (EQ) {
+                    const EqOut e0 = eq_symbol(u0.y, u0.h, nv_r);
+                    a.z[o + s] = make_float2(e0.zr, e0.zi);
+                    a.nv_sym[o + s] = e0.nv;
+                    if (a.h) a.h[o + s] = u0.h;
+                } else {
+                    a.z[o + s] = u0.y;
+                    a.h[o + s] = u0.h;
+                }
+            }
+        }
+    } else {
+        for (int s = threadIdx.x; s < a.S; s += BLOCK) {
+            const Sym u0 = at(s);
+            if constexpr (EQ) {
+                const EqOut e0 = eq_symbol(u0.y, u0.h, nv_r);
+                a.z[o + s] = make_float2(e0.zr, e0.zi);
+                a.nv_sym[o + s] = e0.nv;
+                if (a.h) a.h[o + s] = u0.h;
+            } else {
+                a.z[o + s] = u0.y;
+                a.h[o + s] = u0.h;
+            }
+        }
+    }
+}
+
 }  // namespace tdec

@@ -10,6 +10,8 @@
 //   info bits   ctr = {cw_lo, cw_hi, 128-bit block, 0x1AF0}, key = seed
 //   noise       ctr = {cw_lo, cw_hi, symbol pair,    0x2B0E}, key = seed
 //   gains       ctr = {cw_lo, cw_hi, gain-block pair, 0x3C5D}, key = seed   (k_workload_fading)
+//   pilot noise ctr = {cw_lo, cw_hi, pilot pair,      0x4D6C}, key = seed   (k_workload_frame)
+//   rotation    ctr = {cw_lo, cw_hi, 0,               0x5E7B}, key = seed   (k_workload_frame)
 // Info bit j of a codeword is bit j % 32 of word (j % 128) / 32 of block j / 128.
 // Noise: Box-Muller, u = (x >> 8 + 0.5) * 2^-24 in (0, 1): one complex sample
 // per symbol from two words, r = sigma * sqrt(-2 ln u1), theta = 2 pi u2.
@@ -373,5 +375,80 @@ __global__ __launch_bounds__(64) void k_count_errors(int B, int N, uint64_t cw0,
 // k_workload with flat fading: the same bits and the same noise, each symbol h x + n, and
 // the gains written to f.h.
 __global__ __launch_bounds__(64) void k_workload_fading(WorkloadArgs p, FadeArgs f) { workload_tile<true>(p, f); }
+
+// ---- framing with pilot blocks (k_workload_frame) --------------------------
+// k_workload_fading's symbols y [B][S] and gains [B][nh] framed as P0 D0 P1 D1 ... D(J-1) PJ
+// (k_csi_pilots' layout), one thread per frame position.  Data positions copy their symbol.
+// Pilot i of block j is h p + n: h the gain of data symbol min(j dlen, S - 1), p =
+// pilots[j plen + i], h p formed in f64 and rounded to f32 once per component, n Box-Muller
+// noise of sigma per dimension in awgn()'s form on a stream of its own,
+//   pilot noise ctr = {cw_lo, cw_hi, (j plen + i) / 2, 0x4D6C}, key = seed
+// CFO: position t is then multiplied by exp(j 2 pi f t), f = cfo_max (2u - 1) cycles per
+// symbol with u = (x >> 8 + 0.5) 2^-24 of
+//   rotation    ctr = {cw_lo, cw_hi, 0, 0x5E7B}, key = seed
+// the angle 2 (f t) and sincospi in f64, each product component rounded to f32 once.
+// h_true (nullable) is the gain each position went through, the rotation included.
+constexpr uint32_t PILOT_DOMAIN = 0x4D6Cu, CFO_DOMAIN = 0x5E7Bu;
+
+struct FrameArgs {
+    const float2 *y;                            // [B][S]
+    const float2 *gains;                        // [B][nh]
+    const float2 *pilots;                       // [(J + 1) plen]
+    int B, S, coh, nh, plen, dlen, J, T;
+    uint64_t cw0, seed;
+    float sigma;
+    double cfo_max;
+    float2 *frames, *h_true;                    // [B][T]; h_true nullable
+};
+
+template <bool CFO>
+__global__ __launch_bounds__(BLOCK) void k_workload_frame(FrameArgs f) {
+    const long i = (long)blockIdx.x * BLOCK + threadIdx.x;
+    if (i >= (long)f.B * f.T) return;
+    const long r = i / f.T;
+    const int t = (int)(i - r * f.T);
+    const uint64_t cw = f.cw0 + (uint64_t)r;
+    const int t_last = f.S + f.J * f.plen;      // where pilot block J starts
+    int j, off;
+    if (t >= t_last) {
+        j = f.J;
+        off = t - t_last;
+    } else {
+        j = t / (f.plen + f.dlen);
+        off = t - j * (f.plen + f.dlen);
+    }
+    float2 v, g;
+    if (off < f.plen) {
+        const int s = min(j * f.dlen, f.S - 1), k = j * f.plen + off;
+        g = f.gains[r * f.nh + s / f.coh];
+        const float2 p = f.pilots[k];
+        const double hr = (double)g.x, hi = (double)g.y, pr = (double)p.x, pi = (double)p.y;
+        const Philox4 q = philox4x32_10(Philox4{(uint32_t)cw, (uint32_t)(cw >> 32), (uint32_t)(k >> 1), PILOT_DOMAIN},
+                                        (uint32_t)f.seed, (uint32_t)(f.seed >> 32));
+        const uint32_t a = (k & 1) ? q.z : q.x, b = (k & 1) ? q.w : q.y;
+        const float u1 = ((float)(a >> 8) + 0.5f) * 0x1p-24f, u2 = ((float)(b >> 8) + 0.5f) * 0x1p-24f;
+        const float rad = f.sigma * sqrtf(-2.0f * logf(u1));
+        float sn, cs;
+        sincospif(2.0f * u2, &sn, &cs);
+        v = make_float2((float)(hr * pr - hi * pi) + rad * cs, (float)(hr * pi + hi * pr) + rad * sn);
+    } else {
+        const int s = j * f.dlen + (off - f.plen);
+        g = f.gains[r * f.nh + s / f.coh];
+        v = f.y[r * f.S + s];
+    }
+    if constexpr (CFO) {
+        const Philox4 q = philox4x32_10(Philox4{(uint32_t)cw, (uint32_t)(cw >> 32), 0u, CFO_DOMAIN}, (uint32_t)f.seed,
+                                        (uint32_t)(f.seed >> 32));
+        const double u = ((double)(q.x >> 8) + 0.5) * 0x1p-24;
+        const double fg = f.cfo_max * (2.0 * u - 1.0);
+        double sn, cs;
+        sincospi(2.0 * (fg * (double)t), &sn, &cs);
+        const double vr = (double)v.x, vi = (double)v.y, gr = (double)g.x, gi = (double)g.y;
+        v = make_float2((float)(vr * cs - vi * sn), (float)(vr * sn + vi * cs));
+        g = make_float2((float)(gr * cs - gi * sn), (float)(gr * sn + gi * cs));
+    }
+    f.frames[i] = v;
+    if (f.h_true) f.h_true[i] = g;
+}
 
 }  // namespace tdec

@@ -277,3 +277,194 @@ def compute_llr_device(syms, mod_type, noise_var, out=None, sign=+1, stream=None
     _n.check(call(dev, _n.ptr(syms), int(sym_f64), *(syms.shape if rows else (n_sym,)), _n.ptr(c), int(f64), len(c),
                   m['bps'], _n.ptr(nvt) if rows else nv, *(() if lm else (int(div_f32),)), int(sign), _n.ptr(out), st))
     return out
+
+
+# ---- pilot-aided channel estimation ------------------------------
+CSI_MODES = {"linear": 0, "mean": 1}
+CSI_MAX_BLOCKS = 2048                                 # pilot blocks per burst the estimator's LDS holds
+
+
+class PilotLayout:
+    """A framed burst: J + 1 pilot blocks of `plen` symbols around J = ceil(S / dlen) data
+    segments of `dlen` symbols (the last may be short), P0 D0 P1 D1 ... D(J-1) PJ.
+
+    The pilot sequence is shared by all rows.  By default pilot k of the frame (counted
+    over the pilots alone) is 1j ** ((k * (k + 1) // 2) % 4): unit modulus, QPSK phases, an
+    integer formula and no RNG.  `sequence`, a complex array, replaces it; a burst of S data
+    symbols takes its first (J + 1) * plen values.  A pilot block of zero energy is refused."""
+
+    def __init__(self, plen, dlen, sequence=None):
+        plen, dlen = int(plen), int(dlen)
+        if plen < 1 or dlen < 1:
+            raise ValueError("PilotLayout needs plen >= 1 and dlen >= 1")
+        self.plen, self.dlen = plen, dlen
+        self.sequence = None if sequence is None else np.asarray(sequence).astype(np.complex64).reshape(-1)
+        self._dev = {}
+
+    def n_segments(self, S):
+        """J = ceil(S / dlen)."""
+        if int(S) < 1:
+            raise ValueError("a burst needs S >= 1 data symbols")
+        return -(-int(S) // self.dlen)
+
+    def n_blocks(self, S):
+        return self.n_segments(S) + 1
+
+    def frame_len(self, S):
+        """T = S + (J + 1) * plen."""
+        return int(S) + self.n_blocks(S) * self.plen
+
+    def segment_len(self, S, j):
+        """L_j: data symbols [j * dlen, min((j + 1) * dlen, S))."""
+        if not 0 <= j < self.n_segments(S):
+            raise IndexError(f"segment {j} of {self.n_segments(S)}")
+        return min(self.dlen, int(S) - j * self.dlen)
+
+    def block_start(self, S, j):
+        """Frame position of the first pilot of block j."""
+        J = self.n_segments(S)
+        if not 0 <= j <= J:
+            raise IndexError(f"pilot block {j} of {J + 1}")
+        return j * (self.plen + self.dlen) if j < J else int(S) + J * self.plen
+
+    def data_positions(self, S):
+        """Frame position of each data symbol, int64 [S]."""
+        s = np.arange(int(S), dtype=np.int64)
+        return s + (s // self.dlen + 1) * self.plen
+
+    def pilot_positions(self, S):
+        """Frame position of each pilot, int64 [(J + 1) * plen], block by block."""
+        return np.concatenate([self.block_start(S, j) + np.arange(self.plen, dtype=np.int64)
+                               for j in range(self.n_blocks(S))])
+
+    def pilots(self, S):
+        """The burst's pilot sequence, complex64 [(J + 1) * plen]."""
+        n = self.n_blocks(S) * self.plen
+        if self.sequence is None:
+            k = np.arange(n, dtype=np.int64)
+            q = (k * (k + 1) // 2) % 4
+            p = np.empty(n, np.complex64)
+            p.real = np.array([1, 0, -1, 0], np.float32)[q]
+            p.imag = np.array([0, 1, 0, -1], np.float32)[q]
+        else:
+            if len(self.sequence) < n:
+                raise ValueError(f"the pilot sequence has {len(self.sequence)} values; S = {S} needs {n}")
+            p = self.sequence[:n]
+        e = (np.abs(p.astype(np.complex128)) ** 2).reshape(-1, self.plen).sum(axis=1)
+        if not np.all(e > 0):                         # (also refuses a NaN block)
+            raise ValueError(f"pilot block {int(np.flatnonzero(~(e > 0))[0])} has no energy")
+        return np.ascontiguousarray(p)
+
+    def pilots_device(self, S, device):
+        """pilots(S) on `device`, uploaded once per (S, device)."""
+        import torch
+        key = (int(S), str(device))
+        t = self._dev.get(key)
+        if t is None:
+            t = self._dev[key] = torch.from_numpy(self.pilots(S)).to(device)
+        return t
+
+
+def _csi_frames_check(frames, layout, mode, need_residual=False):
+    """(B, S) of a framed batch.  Every refusal comes before any device call, and in an order
+    that lets each be met with host tensors: layout, mode and noise source, dtype, shape, the
+    pilot blocks' energy, then device and contiguity."""
+    import torch
+    if not isinstance(layout, PilotLayout):
+        raise TypeError(f"layout must be a PilotLayout, got {type(layout)}")
+    if mode not in CSI_MODES:
+        raise ValueError(f"mode must be one of {tuple(CSI_MODES)}, not {mode!r}")
+    if need_residual and layout.plen < 2:
+        raise ValueError("plen == 1 leaves no residual to estimate the noise from: pass noise_var "
+                         "(and no nv_rows_out)")
+    if not isinstance(frames, torch.Tensor) or frames.dtype != torch.complex64:
+        raise TypeError(f"frames must be a torch.complex64 tensor, got {getattr(frames, 'dtype', type(frames))}")
+    if frames.dim() != 2:
+        raise ValueError("frames must be a 2-D [B, T] tensor")
+    B, T = frames.shape
+    # T = S + (ceil(S / dlen) + 1) * plen is increasing in S: the one S that gives T, if any
+    full, rest = divmod(T - layout.plen, layout.plen + layout.dlen)
+    S = full * layout.dlen + (rest - layout.plen if rest else 0)
+    if B < 1 or S < 1 or (rest and rest <= layout.plen) or layout.frame_len(S) != T:
+        raise ValueError(f"frames must be [B >= 1, T] with T the frame length of some S >= 1 for plen = "
+                         f"{layout.plen}, dlen = {layout.dlen}; got {tuple(frames.shape)}")
+    if layout.n_blocks(S) > CSI_MAX_BLOCKS:
+        raise ValueError(f"more than {CSI_MAX_BLOCKS} pilot blocks per burst")
+    layout.pilots(S)                                  # refuses a zero-energy block
+    return B, S
+
+
+def _csi_device_check(frames):
+    if frames.device.type != "cuda" or not frames.is_contiguous():
+        raise ValueError("frames must be a contiguous tensor on a HIP device")
+
+
+def _csi_out(t, frames, shape, dtype, name):
+    import torch
+    if t is None:
+        return torch.empty(shape, dtype=dtype, device=frames.device)
+    if (not isinstance(t, torch.Tensor) or t.dtype != dtype or tuple(t.shape) != tuple(shape) or not t.is_contiguous()
+            or t.device != frames.device):
+        raise ValueError(f"{name} must be a contiguous {dtype} tensor of shape {tuple(shape)} on the frames' device")
+    return t
+
+
+def estimate_csi_device(frames, layout, noise_var=None, mode="linear", floor=0.02, out=None, nv_out=None, h_out=None,
+                        nv_rows_out=None, stream=None):
+    """Pilot-aided channel estimation and equalisation in one launch:
+    framed complex64 [B, T] device bursts (layout: PilotLayout) -> (z complex64 [B, S],
+    nv_sym float64 [B, S]), what equalize_device gives for the stripped data, the gains
+    interpolated between the pilot blocks' estimates (mode "linear", or "mean": the midpoint
+    of the two bordering blocks for the whole segment) and the burst's noise variance.
+
+    noise_var: a scalar, a float64 [B] device tensor, or None: estimated from the pilots'
+    residuals, max(mean, floor) per row, which needs plen >= 2.  h_out (complex64 [B, S]) and
+    nv_rows_out (float64 [B], plen >= 2) receive the gains and the estimate when given.
+    A non-finite or all-zero received pilot block erases the segments it borders."""
+    import torch
+    B, S = _csi_frames_check(frames, layout, mode, need_residual=noise_var is None or nv_rows_out is not None)
+    rows = isinstance(noise_var, torch.Tensor)
+    if rows:
+        if noise_var.dtype != torch.float64:
+            raise TypeError(f"noise_var must be torch.float64, got {noise_var.dtype}")
+        if tuple(noise_var.shape) != (B,) or not noise_var.is_contiguous():
+            raise ValueError(f"noise_var must be a contiguous tensor of shape ({B},), got {tuple(noise_var.shape)}")
+    elif noise_var is not None and float(noise_var) < 0:
+        raise ValueError("noise_var must not be negative")
+    _csi_device_check(frames)
+    if rows and noise_var.device != frames.device:
+        raise ValueError("noise_var must be on the frames' HIP device")
+    pil = layout.pilots_device(S, frames.device)
+    out = _csi_out(out, frames, (B, S), torch.complex64, "out")
+    nv_out = _csi_out(nv_out, frames, (B, S), torch.float64, "nv_out")
+    if h_out is not None:
+        h_out = _csi_out(h_out, frames, (B, S), torch.complex64, "h_out")
+    if nv_rows_out is not None:
+        nv_rows_out = _csi_out(nv_rows_out, frames, (B,), torch.float64, "nv_rows_out")
+    dev = frames.device.index or 0
+    st = _n.stream_ptr(stream) if stream is not None else torch.cuda.current_stream(dev).cuda_stream
+    _n.check(_n.lib().tdec_csi_pilots_dev(dev, _n.ptr(frames), B, S, layout.plen, layout.dlen, _n.ptr(pil),
+                                          CSI_MODES[mode], -1.0 if rows or noise_var is None else float(noise_var),
+                                          _n.ptr(noise_var) if rows else None, float(floor), _n.ptr(out),
+                                          _n.ptr(nv_out), _n.ptr(h_out), _n.ptr(nv_rows_out), st))
+    return out, nv_out
+
+
+def strip_pilots_device(frames, layout, mode="linear", floor=0.02, out=None, h_out=None, nv_rows_out=None, stream=None):
+    """The unfused form of estimate_csi_device: (y complex64 [B, S], the stripped data, and
+    h complex64 [B, S], the interpolated gains), for equalize_device(y, h, nv, coh=1) to
+    follow; nv_rows_out (float64 [B], plen >= 2) receives the pilots' noise estimate."""
+    import torch
+    B, S = _csi_frames_check(frames, layout, mode, need_residual=nv_rows_out is not None)
+    _csi_device_check(frames)
+    pil = layout.pilots_device(S, frames.device)
+    out = _csi_out(out, frames, (B, S), torch.complex64, "out")
+    h_out = _csi_out(h_out, frames, (B, S), torch.complex64, "h_out")
+    if nv_rows_out is not None:
+        nv_rows_out = _csi_out(nv_rows_out, frames, (B,), torch.float64, "nv_rows_out")
+    dev = frames.device.index or 0
+    st = _n.stream_ptr(stream) if stream is not None else torch.cuda.current_stream(dev).cuda_stream
+    _n.check(_n.lib().tdec_csi_strip_dev(dev, _n.ptr(frames), B, S, layout.plen, layout.dlen, _n.ptr(pil),
+                                         CSI_MODES[mode], float(floor), _n.ptr(out), _n.ptr(h_out),
+                                         _n.ptr(nv_rows_out), st))
+    return out, h_out

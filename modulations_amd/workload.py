@@ -17,7 +17,7 @@ def noise_n0(constellation, rate, bps, ebn0_db):
     return es / (rate * bps * 10 ** (ebn0_db / 10.0))
 
 
-def make_symbols(codec, B, mod, ebn0_db, seed, device, cw0=0, want_info=True, fading=None):
+def make_symbols(codec, B, mod, ebn0_db, seed, device, cw0=0, want_info=True, fading=None, pilots=None, cfo=0.0):
     """(info uint8 [B, 2N] or None, received symbols complex64 [B, S], N0) on `device`.
 
     One launch of the counter-based generator (tdec_workload_dev): Philox info
@@ -30,7 +30,15 @@ def make_symbols(codec, B, mod, ebn0_db, seed, device, cw0=0, want_info=True, fa
     fading={"K": Rician factor >= 0 (0: Rayleigh), "coh": symbols per gain block >= 1}:
     a flat-fading channel (tdec_workload_fading_dev), each symbol h x + n
     with the same bits and the same noise as without it, E|h|^2 = 1; the result is then
-    (info, symbols, N0, h) with h complex64 [B, ceil(S / coh)]."""
+    (info, symbols, N0, h) with h complex64 [B, ceil(S / coh)].
+
+    pilots=demap.PilotLayout(...) (with `fading`) frames those symbols with the layout's pilot blocks
+    (tdec_workload_frame_dev): each pilot is h p + n with the gain of the data
+    symbol it stands in front of and noise of the same variance from a stream of its own;
+    cfo > 0 rotates frame position t of codeword g by exp(j 2 pi f_g t), f_g uniform in
+    (-cfo, cfo) cycles per symbol per global codeword.  The result is then (info, frames, N0,
+    h_true), frames and h_true complex64 [B, T], h_true the gain each position went through
+    (rotation included); the data positions of a cfo = 0 frame are the unframed symbols."""
     import torch
     from . import _native as _n
     bps = D.MODULATIONS[mod]["bps"]
@@ -42,6 +50,10 @@ def make_symbols(codec, B, mod, ebn0_db, seed, device, cw0=0, want_info=True, fa
     table = np.ascontiguousarray(cons.astype(np.complex64)).view(np.float32)
     syms = torch.empty((B, S), dtype=torch.complex64, device=device)
     info = torch.empty((B, codec.k_info), dtype=torch.uint8, device=device) if want_info else None
+    if pilots is not None and fading is None:
+        raise ValueError("pilots frames a fading channel's symbols: pass fading={...} as well")
+    if pilots is None and cfo:
+        raise ValueError("cfo needs pilots=PilotLayout(...)")
     if fading is not None:
         unknown = set(fading) - {"K", "coh"}
         if unknown:
@@ -52,6 +64,20 @@ def make_symbols(codec, B, mod, ebn0_db, seed, device, cw0=0, want_info=True, fa
         gains = torch.empty((B, -(-S // coh)), dtype=torch.complex64, device=device)
         h.call("tdec_workload_fading_dev", int(B), int(cw0), int(seed) & 0xFFFFFFFFFFFFFFFF, _n.ptr(table), len(cons),
                bps, float(np.sqrt(n0 / 2)), k, coh, _n.ptr(syms), _n.ptr(gains), _n.ptr(info), codec._stream(None))
+        if pilots is not None:
+            if not isinstance(pilots, D.PilotLayout):
+                raise TypeError(f"pilots must be a demap.PilotLayout, got {type(pilots)}")
+            if not (0.0 <= float(cfo) < float("inf")):
+                raise ValueError("cfo must be a finite value >= 0")
+            T = pilots.frame_len(S)
+            frames = torch.empty((B, T), dtype=torch.complex64, device=device)
+            h_true = torch.empty((B, T), dtype=torch.complex64, device=device)
+            if B:
+                _n.check(_n.lib().tdec_workload_frame_dev(
+                    h.device, _n.ptr(syms), _n.ptr(gains), int(B), S, coh, pilots.plen, pilots.dlen,
+                    _n.ptr(pilots.pilots_device(S, frames.device)), float(np.sqrt(n0 / 2)), int(cw0),
+                    int(seed) & 0xFFFFFFFFFFFFFFFF, float(cfo), _n.ptr(frames), _n.ptr(h_true), codec._stream(None)))
+            return info, frames, n0, h_true
         return info, syms, n0, gains
     h.call("tdec_workload_dev", int(B), int(cw0), int(seed) & 0xFFFFFFFFFFFFFFFF, _n.ptr(table), len(cons), bps,
            float(np.sqrt(n0 / 2)), _n.ptr(syms), _n.ptr(info), codec._stream(None))
@@ -114,7 +140,9 @@ class DevicePipeline:
     csi=True sizes the equaliser's outputs (`z` complex64 [B, S], `nv_sym` float64 [B, S])
     so that run(..., csi=h, coh=...) equalises received symbols of a flat-fading channel
     with known gains and demaps them with a per-symbol noise variance:
-    three launches on one stream; fused=True refuses it likewise."""
+    three launches on one stream; fused=True refuses it likewise.  run_frames() takes framed
+    bursts with pilot blocks instead and estimates the gains (and, if asked, the noise
+    variance) from them in the launch that equalises."""
 
     def __init__(self, codec, mod, B, device, fused=False, overlap=False, gate=True, demap="max-log", csi=False):
         import torch
@@ -174,7 +202,6 @@ class DevicePipeline:
         (symbol s of a row was received through csi[:, s // coh]); the symbols are
         equalised into `z` and demapped with `nv_sym` = noise_var / |csi|^2 per symbol.
         Needs a pipeline built with csi=True."""
-        import torch
         if csi is not None:
             if self.fused_asked:
                 raise ValueError("csi needs the two-launch pipeline: the fused demap+decode kernel has no "
@@ -183,6 +210,37 @@ class DevicePipeline:
                 raise ValueError("csi needs a pipeline built with csi=True")
             if syms.shape[0] > self.B or syms.shape[1] != self.z.shape[1]:
                 raise ValueError(f"csi: symbols must be [<= {self.B}, {self.z.shape[1]}], got {tuple(syms.shape)}")
+        front = None
+        if csi is not None:
+            front = lambda st: self._equalize(syms, csi, noise_var, coh, st)  # noqa: E731
+        return self._run(syms, noise_var, stream, events, syms_ready, front)
+
+    def run_frames(self, frames, layout, noise_var=None, mode="linear", stream=None, events=None):
+        """One batch of framed bursts (demap.PilotLayout): the pilots' channel
+        estimate and the equalisation in one launch into `z` / `nv_sym`, the per-symbol
+        demap, the decode, all on `stream`.  noise_var: a scalar, a float64 [B] device
+        tensor, or None: each burst's own estimate from its pilots (plen >= 2).  Needs a
+        pipeline built with csi=True; fused=True refuses it as it refuses csi."""
+        if self.fused_asked:
+            raise ValueError("framed bursts need the two-launch pipeline: the fused demap+decode kernel has no "
+                             "per-symbol form (fused=True)")
+        if self.z is None:
+            raise ValueError("run_frames needs a pipeline built with csi=True")
+        S = self.z.shape[1]
+        if frames.dim() != 2 or frames.shape[0] > self.B or frames.shape[1] != layout.frame_len(S):
+            raise ValueError(f"frames must be [<= {self.B}, {layout.frame_len(S)}], got {tuple(frames.shape)}")
+        n = frames.shape[0]
+
+        def front(st):
+            z, nvs = D.estimate_csi_device(frames, layout, noise_var, mode=mode, out=self.z[:n],
+                                           nv_out=self.nv_sym[:n], stream=st)
+            return z, nvs, D.demap_mode(np.complex64, self.cons.dtype, np.float64(1.0))[1]
+        return self._run(frames, 1.0, stream, events, None, front)
+
+    def _run(self, syms, noise_var, stream, events, syms_ready, front):
+        """run()'s launches.  front (optional): queues what stands in front of the demapper on
+        the stream it is given and returns (symbols, noise variance, div_f32) for it."""
+        import torch
         if isinstance(noise_var, torch.Tensor):
             if self.fused_asked:
                 raise ValueError("a per-row noise_var tensor needs the two-launch pipeline: the fused "
@@ -205,8 +263,8 @@ class DevicePipeline:
                 sd.wait_stream(stream)
             if self.gate:
                 self.codec.tail_gate(sd)                # batch i-1's decode is in its tail
-            if csi is not None:
-                syms, nve, div32 = self._equalize(syms, csi, noise_var, coh, sd)
+            if front is not None:
+                syms, nve, div32 = front(sd)
             self.demapper.demap_planes_device(syms, self.cons, self.bps, nve, self.planes_db[b], div_f32=div32,
                                               stream=sd, algo=self.demap)
             self.demap_done[b].record(sd)
@@ -226,8 +284,8 @@ class DevicePipeline:
                 events[0].record(stream)
             self.codec.demap_decode_device(syms, self.cons, self.bps, nve, bits, div_f32=div32, stream=stream)
         else:
-            if csi is not None:
-                syms, nve, div32 = self._equalize(syms, csi, noise_var, coh, stream)
+            if front is not None:
+                syms, nve, div32 = front(stream)
             self.codec.demap_planes_device(syms, self.cons, self.bps, nve, self.planes, div_f32=div32,
                                            stream=stream, algo=self.demap)
             if events is not None:
