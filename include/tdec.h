@@ -378,6 +378,31 @@ int tdec_csi_pilots_dev(int device, const float *d_frames, int B, int S, int ple
 int tdec_csi_strip_dev(int device, const float *d_frames, int B, int S, int plen, int dlen, const float *d_pilots,
                        int mode, double floor, float *d_y, float *d_h, double *d_nv_out, void *stream);
 
+/* ---- receive diversity: maximal-ratio combining (build-defined) ----
+ * R copies of every burst (antennas, or retransmissions of one burst), each through a gain
+ * of its own, combined into what tdec_equalize_dev writes for one, so every demapper and
+ * decoder behind it is unchanged.  d_y: complex64 [B][R][S]; d_h: complex64
+ * [B][R][ceil(S / coh)], coh >= 1 as for tdec_equalize_dev; 1 <= R <= 8; outputs d_z
+ * complex64 [B][S] and d_nv_sym f64 [B][S].  All in f64 without contraction, the branches in
+ * the order r = 0 .. R-1.  Per branch
+ *   g_r = hr*hr + hi*hi,  a_r = yr*hr + yi*hi,  b_r = yi*hr - yr*hi
+ * and a branch whose g_r is zero or not finite is skipped (it vouches for nothing).
+ * Common noise (d_nv_branches null): nv_b = d_nv_rows[b] (f64 [B]) when that is not null,
+ * else noise_var; G, A, Bm are the sums of g_r, a_r, b_r over the live branches,
+ *   z = ((float)(A / G), (float)(Bm / G)),  nv_sym = nv_b / G.
+ * Per-branch noise (d_nv_branches, f64 [B][R], each branch's pilot estimate for example):
+ * the summed terms are g_r / nv_br, a_r / nv_br, b_r / nv_br,
+ *   z = ((float)(A / G), (float)(Bm / G)),  nv_sym = 1.0 / G.
+ * Each sum starts from the first live branch's term, not from 0.0 (a -0.0 numerator keeps
+ * its sign): R = 1 with common noise is tdec_equalize_dev bit for bit.  No live branch, or
+ * a G that came out zero or infinite (an overflow; a zero or infinite nv_br): an erasure,
+ * z = 0 + 0j, nv_sym = +inf.  A NaN nv_br is no skip: G is NaN and that row's symbols are
+ * NaN (§10's convention); a NaN y stays in its own symbol.  No floor: the demapper floors.
+ * B = 0 or S = 0 is a no-op.  TDEC_EINVAL, nothing written: null required pointers, negative
+ * sizes, coh < 1, R < 1 or R > 8, both noise arrays given. */
+int tdec_combine_dev(int device, const float *d_y, const float *d_h, int B, int R, int S, int coh, double noise_var,
+                     const double *d_nv_rows, const double *d_nv_branches, float *d_z, double *d_nv_sym, void *stream);
+
 /* Fused soft demap + turbo decode (one launch): what tdec_demap_planes_dev +
  * tdec_decode_planes_dev compute, bit for bit, with each persistent decoder wave
  * demapping its own next tile into a per-wave plane buffer.  Instantiated for
@@ -448,6 +473,23 @@ int tdec_workload_fading_dev(tdec_t *h, int B, int64_t cw0, uint64_t seed, const
 int tdec_workload_frame_dev(int device, const float *d_y, const float *d_gains, int B, int S, int coh, int plen,
                             int dlen, const float *d_pilots, double sigma, int64_t cw0, uint64_t seed, double cfo_max,
                             float *d_frames, float *d_h_true, void *stream);
+/* R receive branches of every codeword: tdec_workload_fading_dev with d_syms
+ * complex64 [B][R][S] and d_h complex64 [B][R][ceil(S / coh)], 1 <= R <= 8.  A codeword's info
+ * bits (d_info, uint8 [B][2N]) are shared by its branches; branch b draws its noise and its
+ * gains with b in the upper 16 bits of the counter's domain word, 0x2B0E | b << 16 and
+ * 0x3C5D | b << 16, so the branches are independent, branch 0 is tdec_workload_fading_dev's
+ * output bit for bit, and a codeword still depends only on its global index. */
+int tdec_workload_branches_dev(tdec_t *h, int B, int R, int64_t cw0, uint64_t seed, const float *cons_iq, int M, int bps,
+                               double sigma, double rician_k, int coh, float *d_syms, float *d_h, uint8_t *d_info,
+                               void *stream);
+/* tdec_workload_frame_dev over those branches: d_y [B][R][S] and d_gains [B][R][ceil(S / coh)]
+ * framed into d_frames (and d_h_true, nullable) complex64 [B][R][T].  Branch b's pilot noise is
+ * drawn with 0x4D6C | b << 16; the rotation f_g belongs to the codeword (one oscillator: the
+ * domain word 0x5E7B as it is) and is shared by its branches.  Branch 0 is
+ * tdec_workload_frame_dev's output bit for bit. */
+int tdec_workload_frame_branches_dev(int device, const float *d_y, const float *d_gains, int B, int R, int S, int coh,
+                                     int plen, int dlen, const float *d_pilots, double sigma, int64_t cw0, uint64_t seed,
+                                     double cfo_max, float *d_frames, float *d_h_true, void *stream);
 /* The info bits alone: uint8 [B][2N] of 0/1. */
 int tdec_info_bits_dev(tdec_t *h, int B, int64_t cw0, uint64_t seed, uint8_t *d_info, void *stream);
 /* Bit errors per codeword of decoded rows (int32 [B][2N], tdec_decode_*) against

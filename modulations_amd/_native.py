@@ -42,6 +42,7 @@ EXPORTS = (
     "tdec_symnv_demap_dev", "tdec_symnv_demap_logmap_dev", "tdec_symnv_demap_planes_dev",
     "tdec_symnv_demap_planes_logmap_dev", "tdec_equalize_dev", "tdec_workload_fading_dev",
     "tdec_csi_pilots_dev", "tdec_csi_strip_dev", "tdec_workload_frame_dev",
+    "tdec_combine_dev", "tdec_workload_branches_dev", "tdec_workload_frame_branches_dev",
 )
 
 _lib = None
@@ -152,6 +153,16 @@ def _declare(L):
         L.tdec_workload_frame_dev.argtypes = [C.c_int, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp,
                                               C.c_double, C.c_int64, C.c_uint64, C.c_double, _vp, _vp, _vp]
         for f in (L.tdec_csi_pilots_dev, L.tdec_csi_strip_dev, L.tdec_workload_frame_dev):
+            f.restype = C.c_int
+    if hasattr(L, "tdec_combine_dev"):   # (A/B tools also load older builds without receive diversity)
+        L.tdec_combine_dev.argtypes = [C.c_int, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, _vp, _vp, _vp,
+                                       _vp, _vp]
+        L.tdec_workload_branches_dev.argtypes = [_vp, C.c_int, C.c_int, C.c_int64, C.c_uint64, _vp, C.c_int, C.c_int,
+                                                 C.c_double, C.c_double, C.c_int, _vp, _vp, _vp, _vp]
+        L.tdec_workload_frame_branches_dev.argtypes = [C.c_int, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                                       C.c_int, _vp, C.c_double, C.c_int64, C.c_uint64, C.c_double, _vp,
+                                                       _vp, _vp]
+        for f in (L.tdec_combine_dev, L.tdec_workload_branches_dev, L.tdec_workload_frame_branches_dev):
             f.restype = C.c_int
     L.tdec_encode_dev.argtypes = [_vp, C.c_int, _vp, _vp, _vp]
     L.tdec_demap_batch.argtypes = [C.c_int, C.c_int, C.c_int, _vp, C.c_long, C.c_float, _vp]

@@ -15,7 +15,7 @@ only those int64 counters are all-reduced.  Finished points are written to
 §5).  The file records the sweep's configuration and the generator version;
 a rerun into it with any other configuration (modulation, block size, rate,
 algorithm, iterations, interleaver, codewords per point, base seed, early
-stop and its decoder, demapper, channel) or generator is refused instead of mixing two data streams, and each point's
+stop and its decoder, demapper, channel, receive branches) or generator is refused instead of mixing two data streams, and each point's
 generator key is derived from its Eb/N0 value (not its index in --ebn0), so a
 resumed sweep over a different grid regenerates exactly the same data.
 
@@ -30,6 +30,11 @@ bits and the noise are those of the AWGN sweep with the same seed.
 carrier rotation at most) and lets the pipeline estimate the gains from them, with the
 noise variance known (--csi-noise known) or estimated from the pilots as well (pilots).
 The pilots' energy is not charged to Eb/N0.
+
+--rx-branches R (fading channels) receives every burst on R independently
+faded, independently noisy branches and combines them (maximal ratio) in front of the
+demapper, with --csi known or pilots.  Eb/N0 is per branch: the array gain (10 log10 R dB
+of collected energy) is not charged, so the curves show it together with the diversity gain.
 """
 from __future__ import annotations
 
@@ -73,6 +78,8 @@ def sweep_config(a, inv_perm=None):
         if getattr(a, "csi", "known") == "pilots":   # (absent at the default, likewise)
             cfg.update(csi="pilots", pilot_len=int(a.pilot_len), pilot_spacing=int(a.pilot_spacing),
                        cfo=float(a.cfo), csi_noise=a.csi_noise)
+        if "branches" in fading:   # (absent for one branch, likewise)
+            cfg["rx_branches"] = fading["branches"]
     if inv_perm is not None:
         cfg["inv_perm_digest"] = interleaver_digest(inv_perm)
     return cfg
@@ -84,7 +91,10 @@ def channel_fading(a):
     channel = getattr(a, "channel", "awgn")
     if channel == "awgn":
         return None
-    return {"K": float(a.rician_k) if channel == "rician" else 0.0, "coh": int(a.coherence)}
+    fading = {"K": float(a.rician_k) if channel == "rician" else 0.0, "coh": int(a.coherence)}
+    if int(getattr(a, "rx_branches", 1)) > 1:   # (one branch is the call without the key: the same data)
+        fading["branches"] = int(a.rx_branches)
+    return fading
 
 
 def load_resume(path, cfg):
@@ -132,7 +142,8 @@ def run_point(pipe, codec, mod, ebn0, start, count, batch, seed, device, times=N
     fading (make_symbols' dict, optional): the flat-fading channel; the pipeline (built
     with csi=True) equalises with the generator's gains.  pilots (optional, with fading):
     {"layout": demap.PilotLayout, "cfo": cycles per symbol, "noise": "known" | "pilots"}: the
-    bursts are framed and the pipeline estimates the gains (and the noise) from the pilots."""
+    bursts are framed and the pipeline estimates the gains (and the noise) from the pilots.
+    fading["branches"] = R: symbols, gains and frames are [n, R, ...] and the pipeline combines."""
     import torch
     from . import sharding as S
     from .workload import count_errors, make_symbols
@@ -204,6 +215,10 @@ def arg_parser():
                     help="--csi pilots: residual carrier rotation, uniform in (-cfo, cfo) cycles per symbol per burst")
     ap.add_argument("--csi-noise", choices=["known", "pilots"], default="known",
                     help="--csi pilots: the noise variance is N0, or each burst's estimate from its pilots")
+    ap.add_argument("--rx-branches", type=int, default=1,
+                    help="fading channels: receive branches per burst (1 .. 8), independently faded and noisy, "
+                         "maximal-ratio combined in front of the demapper; Eb/N0 is per branch (the array gain "
+                         "is not charged)")
     ap.add_argument("--out", default=None)
     ap.add_argument("--dist-backend", default="nccl", help="nccl (= RCCL) on the node; gloo to rehearse")
     ap.add_argument("--all-on-device0", action="store_true", help="every rank on GPU 0 (rehearsal on a 1-GPU box)")
@@ -222,6 +237,10 @@ def main(argv=None):
     a = ap.parse_args(argv)
     if a.coherence < 1 or not (0.0 <= a.rician_k < float("inf")):
         ap.error("--coherence must be >= 1 and --rician-k a finite value >= 0")
+    if not 1 <= a.rx_branches <= 8:
+        ap.error("--rx-branches must be 1 .. 8")
+    if a.rx_branches > 1 and a.channel == "awgn":
+        ap.error("--rx-branches needs --channel rayleigh or rician")
     fading = channel_fading(a)
     pilots = None
     if a.csi == "pilots":
@@ -298,6 +317,8 @@ def main(argv=None):
             rec["demap"] = a.demap
         if fading is not None:
             rec.update(channel=a.channel, rician_k=fading["K"], coherence=fading["coh"])
+            if "branches" in fading:
+                rec["rx_branches"] = fading["branches"]
         if pilots is not None:
             rec.update(csi="pilots", pilot_len=a.pilot_len, pilot_spacing=a.pilot_spacing, cfo=a.cfo,
                        csi_noise=a.csi_noise)

@@ -69,6 +69,9 @@ namespace {
     FLATS(2) PLANES(LM_ML, LM_ML_SPLIT, 2)                                                         // per symbol
     (void)k_equalize<true, true>, (void)k_equalize<true, false>, (void)k_equalize<false, true>, (void)k_equalize<false, false>;
     (void)k_csi_pilots<true>, (void)k_csi_pilots<false>, (void)k_workload_frame<false>, (void)k_workload_frame<true>;   // pilots (§13)
+    (void)k_combine<0, true>, (void)k_combine<0, false>, (void)k_combine<1, true>, (void)k_combine<1, false>,
+        (void)k_combine<2, true>, (void)k_combine<2, false>;                                       // diversity (§14)
+    (void)k_workload_faded<BranchArgs>, (void)k_workload_frame_branches<false>, (void)k_workload_frame_branches<true>;
 }
 #undef EACH_BPS
 #undef BOTH
@@ -2087,6 +2090,65 @@ int tdec_workload_frame_dev(int device, const float *d_y, const float *d_gains, 
     const dim3 grid((unsigned)(((long)B * T + BLOCK - 1) / BLOCK));
     if (cfo_max > 0.0) hipLaunchKernelGGL(k_workload_frame<true>, grid, dim3(BLOCK), 0, (hipStream_t)stream, f);
     else hipLaunchKernelGGL(k_workload_frame<false>, grid, dim3(BLOCK), 0, (hipStream_t)stream, f);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+// receive diversity
+int tdec_workload_branches_dev(tdec_t *h, int B, int R, int64_t cw0, uint64_t seed, const float *cons_iq, int M, int bps,
+                               double sigma, double rician_k, int coh, float *d_syms, float *d_h, uint8_t *d_info,
+                               void *stream) {
+    if (!h || B < 0 || cw0 < 0 || R < 1 || R > 8) return fail(TDEC_EINVAL, "bad workload arguments (1 <= R <= 8)");
+    if (B == 0) return 0;
+    if (!cons_iq || !d_syms || !d_h || bps < 1 || bps > 8 || M != (1 << bps) || !(sigma >= 0.0) || coh < 1 ||
+        !(rician_k >= 0.0) || !(rician_k < INFINITY))
+        return fail(TDEC_EINVAL, "bad workload arguments (the constellation must have 2^bps points; K >= 0, coh >= 1)");
+    if (!staged_encoder_ok(h)) return fail(TDEC_EINVAL, "workload generation needs N % 4 == 0 and N <= 1024");
+    Guard g(h->device);
+    WorkloadArgs a = workload_args(h, B);
+    a.bps = bps;
+    a.M = M;
+    a.S = (int)((h->enc_len + bps - 1) / bps);
+    a.cw0 = (uint64_t)cw0;
+    a.seed = seed;
+    a.sigma = (float)sigma;
+    for (int m = 0; m < M; ++m) a.cons[m] = make_float2(cons_iq[2 * m], cons_iq[2 * m + 1]);
+    a.info_out = d_info;
+    a.syms = reinterpret_cast<float2 *>(d_syms);
+    BranchArgs f{};
+    f.h = reinterpret_cast<float2 *>(d_h);
+    f.coh = coh;
+    f.nh = (a.S + coh - 1) / coh;
+    f.los = (float)std::sqrt(rician_k / (rician_k + 1.0));
+    f.scat = (float)std::sqrt(1.0 / (rician_k + 1.0));
+    f.R = R;
+    hipLaunchKernelGGL(k_workload_faded<BranchArgs>, dim3((unsigned)n_tiles_of(B)), dim3(64), 0, (hipStream_t)stream, a, f);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+int tdec_workload_frame_branches_dev(int device, const float *d_y, const float *d_gains, int B, int R, int S, int coh,
+                                     int plen, int dlen, const float *d_pilots, double sigma, int64_t cw0, uint64_t seed,
+                                     double cfo_max, float *d_frames, float *d_h_true, void *stream) {
+    if (B < 0 || cw0 < 0 || R < 1 || R > 8) return fail(TDEC_EINVAL, "bad frame arguments (1 <= R <= 8)");
+    if (B == 0) return 0;
+    if (!d_y || !d_gains || !d_pilots || !d_frames || S < 1 || coh < 1 || plen < 1 || dlen < 1 || !(sigma >= 0.0) ||
+        !(cfo_max >= 0.0) || !(cfo_max < INFINITY))
+        return fail(TDEC_EINVAL, "bad frame arguments (S, coh, plen, dlen >= 1; sigma >= 0; finite cfo_max >= 0)");
+    const int J = (S + dlen - 1) / dlen;
+    const long T = (long)S + (long)(J + 1) * plen;
+    if (T > INT32_MAX || (long)B * R > INT32_MAX) return fail(TDEC_EINVAL, "bad frame arguments (frame or batch too long)");
+    Guard g(device);
+    FrameArgs f{};
+    f.y = reinterpret_cast<const float2 *>(d_y);
+    f.gains = reinterpret_cast<const float2 *>(d_gains);
+    f.pilots = reinterpret_cast<const float2 *>(d_pilots);
+    f.B = B * R, f.S = S, f.coh = coh, f.nh = (S + coh - 1) / coh, f.plen = plen, f.dlen = dlen, f.J = J, f.T = (int)T;
+    f.cw0 = (uint64_t)cw0, f.seed = seed, f.sigma = (float)sigma, f.cfo_max = cfo_max;
+    f.frames = reinterpret_cast<float2 *>(d_frames), f.h_true = reinterpret_cast<float2 *>(d_h_true);
+    const dim3 grid((unsigned)(((long)f.B * T + BLOCK - 1) / BLOCK));
+    if (cfo_max > 0.0) hipLaunchKernelGGL(k_workload_frame_branches<true>, grid, dim3(BLOCK), 0, (hipStream_t)stream, f, R);
+    else hipLaunchKernelGGL(k_workload_frame_branches<false>, grid, dim3(BLOCK), 0, (hipStream_t)stream, f, R);
     HIPCHK(hipGetLastError());
     return 0;
 }

@@ -1,7 +1,7 @@
 // tdec_demap_api.hip -- the soft demapper's host code, included by
 // tdec_api.hip behind the decoder's launch helpers: configuration and argument checks, the
 // table caches, the flat and plane launchers with their entries, every exported demap
-// call, the noise-variance estimator, the equaliser, the fused demap + decode call and the
+// call, the noise-variance estimator, the equaliser, the combiner, the fused demap + decode call and the
 // built-in constellations.  (ConsCache, the device table itself, is a member of the handle
 // and stands with the handle's other buffer types in tdec_api.hip.)
 
@@ -223,6 +223,21 @@ void launch_equalize(bool vec, const float2 *y, const float2 *hh, long n_sym, in
     }
 }
 
+// k_combine over n_sym = B * S combined symbols; NV: the noise source (0 nv,
+// 1 nvs[row], 2 nvs[row][branch]); vec: two symbols per thread, 16-byte accesses
+template <int NV>
+void launch_combine(bool vec, const float2 *y, const float2 *hh, long n_sym, int R, int S, int coh, int nh, double nv,
+                    const double *nvs, float2 *z, double *nv_sym, hipStream_t st) {
+    if (vec) {
+        const long n_thr = n_sym / 2;
+        hipLaunchKernelGGL((k_combine<NV, true>), dim3((unsigned)((n_thr + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, st, y, hh,
+                           n_sym, R, S, coh, nh, nv, nvs, z, nv_sym);
+    } else {
+        hipLaunchKernelGGL((k_combine<NV, false>), dim3((unsigned)((n_sym + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, st, y, hh,
+                           n_sym, R, S, coh, nh, nv, nvs, z, nv_sym);
+    }
+}
+
 // k_csi_pilots, one block per framed row.  EQ: estimate + equalise into z and
 // nv_sym with the row's noise variance from d_nv_rows (when not null), else noise_var (when not
 // negative), else the pilots' own estimate; !EQ: the stripped data and the interpolated gains.
@@ -404,6 +419,28 @@ int tdec_csi_strip_dev(int device, const float *d_frames, int B, int S, int plen
     if (!d_frames || !d_pilots || !d_y || !d_h) return fail(TDEC_EINVAL, "csi_strip: null pointer");
     return csi_pilots<false>(device, d_frames, B, S, plen, dlen, d_pilots, mode, -1.0, nullptr, floor, d_y, nullptr,
                              d_h, d_nv_out, stream);
+}
+
+// receive diversity
+int tdec_combine_dev(int device, const float *d_y, const float *d_h, int B, int R, int S, int coh, double noise_var,
+                     const double *d_nv_rows, const double *d_nv_branches, float *d_z, double *d_nv_sym, void *stream) {
+    if (B < 0 || S < 0 || coh < 1 || R < 1 || R > 8) return fail(TDEC_EINVAL, "bad combine arguments (1 <= R <= 8, coh >= 1)");
+    if (d_nv_rows && d_nv_branches) return fail(TDEC_EINVAL, "combine: one noise array at most");
+    if (B == 0 || S == 0) return 0;
+    if (!d_y || !d_h || !d_z || !d_nv_sym) return fail(TDEC_EINVAL, "bad combine arguments");
+    Guard g(device);
+    const long n_sym = (long)B * S;
+    const int nh = (S + coh - 1) / coh;
+    // 16-byte accesses where a pair of symbols stays in its row and y, z and nv_sym all allow them
+    const bool vec = S % 2 == 0 && (((uintptr_t)d_y | (uintptr_t)d_z | (uintptr_t)d_nv_sym) & 15) == 0;
+    const float2 *y = reinterpret_cast<const float2 *>(d_y), *hh = reinterpret_cast<const float2 *>(d_h);
+    float2 *z = reinterpret_cast<float2 *>(d_z);
+    hipStream_t st = (hipStream_t)stream;
+    if (d_nv_branches) launch_combine<2>(vec, y, hh, n_sym, R, S, coh, nh, 0.0, d_nv_branches, z, d_nv_sym, st);
+    else if (d_nv_rows) launch_combine<1>(vec, y, hh, n_sym, R, S, coh, nh, 0.0, d_nv_rows, z, d_nv_sym, st);
+    else launch_combine<0>(vec, y, hh, n_sym, R, S, coh, nh, noise_var, nullptr, z, d_nv_sym, st);
+    HIPCHK(hipGetLastError());
+    return 0;
 }
 
 #if TDEC_DM_STATS

@@ -1199,6 +1199,86 @@ __global__ __launch_bounds__(BLOCK) void k_equalize(const float2 *y, const float
     }
 }
 
+// ---- receive diversity: maximal-ratio combiner (build-defined) ------------
+// R copies of a burst, y [B][R][S] complex64 through the gains h [B][R][ceil(S / coh)], into
+// what k_equalize writes for one: z [B][S] and nv_sym [B][S].  All in f64, no contraction,
+// the branches in the order r = 0 .. R-1.  Per branch
+//   g = hr*hr + hi*hi,  a = yr*hr + yi*hi,  b = yi*hr - yr*hi
+// and a branch whose g is zero or not finite is skipped.  NV 0 / 1, a common noise variance
+// (the launch's nv / nvs[row]): G, A, Bm are the sums of g, a, b over the live branches,
+//   z = ((float)(A / G), (float)(Bm / G)),  nv_sym = nv_b / G.
+// NV 2, nvs[row][r] per branch: the summed terms are g / nv_br, a / nv_br, b / nv_br,
+//   z likewise,  nv_sym = 1.0 / G.
+// Each sum starts from the first live branch's term, not from 0.0 (a -0.0 numerator keeps
+// its sign), so R = 1 with a common noise is eq_symbol bit for bit.  No live branch, or a
+// G that came out zero or infinite: an erasure, z = 0 and nv_sym = +inf.  A NaN G (a NaN
+// nv_br, §10's convention) stays NaN in z and nv_sym.
+// One thread per symbol; with VEC one thread per two consecutive symbols of a row (S is
+// even, so a pair never straddles rows, and every base is 16-byte aligned: the host checks
+// both), each branch's y read and z and nv_sym written 16 bytes at a time.  Consecutive
+// lanes take consecutive s, so every branch's loads are coalesced; a symbol's R branches
+// lie S apart.
+struct MrcSum {
+    double G, A, Bm;
+    bool live;
+};
+template <int NV>
+__device__ __forceinline__ void mrc_add(MrcSum &m, float2 y, float2 h, double nv_br) {
+    const double hr = (double)h.x, hi = (double)h.y, yr = (double)y.x, yi = (double)y.y;
+    const double g = hr * hr + hi * hi;
+    if (g == 0.0 || !(fabs(g) < INFINITY)) return;   // a dead branch vouches for nothing
+    double gg = g, a = yr * hr + yi * hi, b = yi * hr - yr * hi;
+    if constexpr (NV == 2) {
+        gg = g / nv_br;
+        a = a / nv_br;
+        b = b / nv_br;
+    }
+    if (m.live) {
+        m.G += gg;
+        m.A += a;
+        m.Bm += b;
+    } else {
+        m = MrcSum{gg, a, b, true};
+    }
+}
+template <int NV>
+__device__ __forceinline__ EqOut mrc_out(const MrcSum &m, double nv) {
+    if (!m.live || m.G == 0.0 || fabs(m.G) == (double)INFINITY) return EqOut{0.0f, 0.0f, (double)INFINITY};
+    return EqOut{(float)(m.A / m.G), (float)(m.Bm / m.G), (NV == 2 ? 1.0 : nv) / m.G};
+}
+template <int NV, bool VEC>
+__global__ __launch_bounds__(BLOCK) void k_combine(const float2 *y, const float2 *h, long n_sym, int R, int S, int coh,
+                                                  int nh, double nv, const double *nvs, float2 *z, double *nv_sym) {
+    const long t = (long)blockIdx.x * BLOCK + threadIdx.x;
+    const long i = VEC ? 2 * t : t;                  // VEC: n_sym is even
+    if (i >= n_sym) return;
+    const long row = i / S;
+    const int s = (int)(i - row * S);
+    const float2 *yb = y + row * R * S + s, *hb = h + row * R * nh;
+    const double nv_c = NV == 1 ? nvs[row] : nv;
+    const int j0 = s / coh, j1 = VEC ? (s + 1) / coh : 0;
+    MrcSum m0{}, m1{};
+    for (int r = 0; r < R; ++r) {
+        const double nv_br = NV == 2 ? nvs[row * R + r] : 0.0;
+        if constexpr (VEC) {
+            const float4 yy = *reinterpret_cast<const float4 *>(yb + (long)r * S);
+            mrc_add<NV>(m0, make_float2(yy.x, yy.y), hb[r * nh + j0], nv_br);
+            mrc_add<NV>(m1, make_float2(yy.z, yy.w), hb[r * nh + j1], nv_br);
+        } else {
+            mrc_add<NV>(m0, yb[(long)r * S], hb[r * nh + j0], nv_br);
+        }
+    }
+    const EqOut a = mrc_out<NV>(m0, nv_c);
+    if constexpr (VEC) {
+        const EqOut b = mrc_out<NV>(m1, nv_c);
+        reinterpret_cast<float4 *>(z)[t] = make_float4(a.zr, a.zi, b.zr, b.zi);
+        reinterpret_cast<double2 *>(nv_sym)[t] = make_double2(a.nv, b.nv);
+    } else {
+        z[i] = make_float2(a.zr, a.zi);
+        nv_sym[i] = a.nv;
+    }
+}
+
 // ---- fused demap + decode ------------------------------------------------------------
 // Each persistent decoder wave demaps its next 64-codeword tile itself (the same
 // operations as k_demap_planes, so the planes are bit-identical) into a plane

@@ -12,6 +12,9 @@
 //   gains       ctr = {cw_lo, cw_hi, gain-block pair, 0x3C5D}, key = seed   (k_workload_fading)
 //   pilot noise ctr = {cw_lo, cw_hi, pilot pair,      0x4D6C}, key = seed   (k_workload_frame)
 //   rotation    ctr = {cw_lo, cw_hi, 0,               0x5E7B}, key = seed   (k_workload_frame)
+// Receive branch b of a codeword draws its noise, gains and pilot noise with
+// b in the upper 16 bits of the domain word (0x2B0E | b << 16, ...): branch 0 is the
+// streams above; the info bits and the rotation are the codeword's, shared by its branches.
 // Info bit j of a codeword is bit j % 32 of word (j % 128) / 32 of block j / 128.
 // Noise: Box-Muller, u = (x >> 8 + 0.5) * 2^-24 in (0, 1): one complex sample
 // per symbol from two words, r = sigma * sqrt(-2 ln u1), theta = 2 pi u2.
@@ -28,6 +31,8 @@
 //   symbols    8-B complex64 stores, noise generated in the coalesced phase
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+
+#include <type_traits>
 
 namespace tdec {
 
@@ -162,8 +167,8 @@ __device__ __forceinline__ void flush_coded(const WorkloadArgs &p, long base, ui
     __syncthreads();
 }
 
-__device__ __forceinline__ float2 awgn(uint64_t cw, long s, const WorkloadArgs &p) {
-    const Philox4 r = philox4x32_10(Philox4{(uint32_t)cw, (uint32_t)(cw >> 32), (uint32_t)(s >> 1), NOISE_DOMAIN},
+__device__ __forceinline__ float2 awgn(uint64_t cw, long s, const WorkloadArgs &p, uint32_t domain = NOISE_DOMAIN) {
+    const Philox4 r = philox4x32_10(Philox4{(uint32_t)cw, (uint32_t)(cw >> 32), (uint32_t)(s >> 1), domain},
                                     (uint32_t)p.seed, (uint32_t)(p.seed >> 32));
     const uint32_t a = (s & 1) ? r.z : r.x, b = (s & 1) ? r.w : r.y;
     const float u1 = ((float)(a >> 8) + 0.5f) * 0x1p-24f, u2 = ((float)(b >> 8) + 0.5f) * 0x1p-24f;
@@ -182,8 +187,13 @@ struct FadeArgs {
     int coh, nh;                                // symbols per gain block; nh = ceil(S / coh)
     float los, scat;
 };
-__device__ __forceinline__ float2 fade_gain(uint64_t cw, long j, uint64_t seed, const FadeArgs &f) {
-    const Philox4 r = philox4x32_10(Philox4{(uint32_t)cw, (uint32_t)(cw >> 32), (uint32_t)(j >> 1), FADE_DOMAIN},
+// BranchArgs: R branches of every codeword, rows [B][R] of syms and h
+struct BranchArgs : FadeArgs {
+    int R;
+};
+__device__ __forceinline__ float2 fade_gain(uint64_t cw, long j, uint64_t seed, const FadeArgs &f,
+                                            uint32_t domain = FADE_DOMAIN) {
+    const Philox4 r = philox4x32_10(Philox4{(uint32_t)cw, (uint32_t)(cw >> 32), (uint32_t)(j >> 1), domain},
                                     (uint32_t)seed, (uint32_t)(seed >> 32));
     const uint32_t a = (j & 1) ? r.z : r.x, b = (j & 1) ? r.w : r.y;
     const float u1 = ((float)(a >> 8) + 0.5f) * 0x1p-24f, u2 = ((float)(b >> 8) + 0.5f) * 0x1p-24f;
@@ -195,9 +205,10 @@ __device__ __forceinline__ float2 fade_gain(uint64_t cw, long j, uint64_t seed, 
 
 // Row-order flush of a chunk of symbol labels lab[k][lane] (k < ns): symbols
 // [s0, s0 + ns) of every codeword, table point + AWGN, complex64.  FADE: h x + AWGN, and
-// the first symbol of each gain block writes its gain.
-template <bool FADE>
-__device__ __forceinline__ void flush_syms(const WorkloadArgs &p, const FadeArgs &f, long base, uint8_t (*lab)[64],
+// the first symbol of each gain block writes its gain.  F = BranchArgs: f.R independently faded
+// and independently noisy copies of each symbol, branch b at row (codeword) * R + b.
+template <bool FADE, typename F>
+__device__ __forceinline__ void flush_syms(const WorkloadArgs &p, const F &f, long base, uint8_t (*lab)[64],
                                            const float2 *cons, int ns, long s0, int lane) {
     __syncthreads();
     for (int t = lane; t < 64 * ns; t += 64) {
@@ -205,7 +216,17 @@ __device__ __forceinline__ void flush_syms(const WorkloadArgs &p, const FadeArgs
         if (base + l < p.B) {
             const uint64_t cw = p.cw0 + (uint64_t)(base + l);
             const float2 x = cons[lab[k][l]], n = awgn(cw, s0 + k, p);
-            if constexpr (FADE) {
+            if constexpr (std::is_same<F, BranchArgs>::value) {
+                const long s = s0 + k, j = s / f.coh;
+                for (int b = 0; b < f.R; ++b) {
+                    const uint32_t tag = (uint32_t)b << 16;
+                    const float2 g = fade_gain(cw, j, p.seed, f, FADE_DOMAIN | tag);
+                    const float2 nb = b ? awgn(cw, s, p, NOISE_DOMAIN | tag) : n;
+                    const long row = (base + l) * f.R + b;
+                    if (s == j * f.coh) f.h[row * f.nh + j] = g;
+                    p.syms[row * p.S + s] = make_float2((g.x * x.x - g.y * x.y) + nb.x, (g.x * x.y + g.y * x.x) + nb.y);
+                }
+            } else if constexpr (FADE) {
                 const long s = s0 + k, j = s / f.coh;
                 const float2 g = fade_gain(cw, j, p.seed, f);
                 if (s == j * f.coh) f.h[(base + l) * (long)f.nh + j] = g;
@@ -220,7 +241,8 @@ __device__ __forceinline__ void flush_syms(const WorkloadArgs &p, const FadeArgs
 }
 
 // One wave per 64-codeword tile (block = 1 wave: no cross-wave barriers).
-template <bool FADE> __device__ __forceinline__ void workload_tile(const WorkloadArgs &p, const FadeArgs &f) {
+template <bool FADE, typename F = FadeArgs>
+__device__ __forceinline__ void workload_tile(const WorkloadArgs &p, const F &f) {
     __shared__ uint32_t inpw[ENC_NW][64];
     __shared__ uint32_t outw[OUT_CHUNK][64];
     __shared__ uint8_t lab[SYM_CHUNK][64];
@@ -265,7 +287,7 @@ template <bool FADE> __device__ __forceinline__ void workload_tile(const Workloa
                 lbl = 0;
                 nl = 0;
                 if (++ns == SYM_CHUNK) {
-                    flush_syms<FADE>(p, f, base, lab, cons, ns, s0, lane);
+                    flush_syms<FADE, F>(p, f, base, lab, cons, ns, s0, lane);
                     s0 += ns;
                     ns = 0;
                 }
@@ -292,7 +314,7 @@ template <bool FADE> __device__ __forceinline__ void workload_tile(const Workloa
     }
     if (p.syms) {
         if (nl) lab[ns++][lane] = (uint8_t)(lbl << (p.bps - nl));   // zero pad of the last symbol
-        if (ns) flush_syms<FADE>(p, f, base, lab, cons, ns, s0, lane);
+        if (ns) flush_syms<FADE, F>(p, f, base, lab, cons, ns, s0, lane);
     }
 }
 
@@ -376,6 +398,13 @@ __global__ __launch_bounds__(64) void k_count_errors(int B, int N, uint64_t cw0,
 // the gains written to f.h.
 __global__ __launch_bounds__(64) void k_workload_fading(WorkloadArgs p, FadeArgs f) { workload_tile<true>(p, f); }
 
+// k_workload_fading over R receive branches (f: BranchArgs).  A template, so
+// that the kernel-order manifest places it: a plain kernel would stand among the
+// non-template ones and move those behind it.
+template <typename F> __global__ __launch_bounds__(64) void k_workload_faded(WorkloadArgs p, F f) {
+    workload_tile<true, F>(p, f);
+}
+
 // ---- framing with pilot blocks (k_workload_frame) --------------------------
 // k_workload_fading's symbols y [B][S] and gains [B][nh] framed as P0 D0 P1 D1 ... D(J-1) PJ
 // (k_csi_pilots' layout), one thread per frame position.  Data positions copy their symbol.
@@ -401,13 +430,11 @@ struct FrameArgs {
     float2 *frames, *h_true;                    // [B][T]; h_true nullable
 };
 
+// Position i of the flat [f.B][f.T] frames: row r = i / T holds codeword cw, its pilot noise drawn from
+// pilot_domain
 template <bool CFO>
-__global__ __launch_bounds__(BLOCK) void k_workload_frame(FrameArgs f) {
-    const long i = (long)blockIdx.x * BLOCK + threadIdx.x;
-    if (i >= (long)f.B * f.T) return;
-    const long r = i / f.T;
+__device__ __forceinline__ void frame_position(const FrameArgs &f, long i, long r, uint64_t cw, uint32_t pilot_domain) {
     const int t = (int)(i - r * f.T);
-    const uint64_t cw = f.cw0 + (uint64_t)r;
     const int t_last = f.S + f.J * f.plen;      // where pilot block J starts
     int j, off;
     if (t >= t_last) {
@@ -423,7 +450,7 @@ __global__ __launch_bounds__(BLOCK) void k_workload_frame(FrameArgs f) {
         g = f.gains[r * f.nh + s / f.coh];
         const float2 p = f.pilots[k];
         const double hr = (double)g.x, hi = (double)g.y, pr = (double)p.x, pi = (double)p.y;
-        const Philox4 q = philox4x32_10(Philox4{(uint32_t)cw, (uint32_t)(cw >> 32), (uint32_t)(k >> 1), PILOT_DOMAIN},
+        const Philox4 q = philox4x32_10(Philox4{(uint32_t)cw, (uint32_t)(cw >> 32), (uint32_t)(k >> 1), pilot_domain},
                                         (uint32_t)f.seed, (uint32_t)(f.seed >> 32));
         const uint32_t a = (k & 1) ? q.z : q.x, b = (k & 1) ? q.w : q.y;
         const float u1 = ((float)(a >> 8) + 0.5f) * 0x1p-24f, u2 = ((float)(b >> 8) + 0.5f) * 0x1p-24f;
@@ -449,6 +476,24 @@ __global__ __launch_bounds__(BLOCK) void k_workload_frame(FrameArgs f) {
     }
     f.frames[i] = v;
     if (f.h_true) f.h_true[i] = g;
+}
+
+template <bool CFO>
+__global__ __launch_bounds__(BLOCK) void k_workload_frame(FrameArgs f) {
+    const long i = (long)blockIdx.x * BLOCK + threadIdx.x;
+    if (i >= (long)f.B * f.T) return;
+    const long r = i / f.T;
+    frame_position<CFO>(f, i, r, f.cw0 + (uint64_t)r, PILOT_DOMAIN);
+}
+
+// The same over R receive branches: f.B = codewords * R rows, row r branch r % R of
+// codeword r / R, whose rotation all its branches share
+template <bool CFO>
+__global__ __launch_bounds__(BLOCK) void k_workload_frame_branches(FrameArgs f, int R) {
+    const long i = (long)blockIdx.x * BLOCK + threadIdx.x;
+    if (i >= (long)f.B * f.T) return;
+    const long r = i / f.T;
+    frame_position<CFO>(f, i, r, f.cw0 + (uint64_t)(r / R), PILOT_DOMAIN | (uint32_t)(r % R) << 16);
 }
 
 }  // namespace tdec

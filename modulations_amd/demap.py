@@ -212,6 +212,66 @@ def equalize_device(syms, h, noise_var, coh=1, out=None, nv_out=None, stream=Non
     return out, nv_out
 
 
+MAX_BRANCHES = 8
+
+
+def combine_device(y, h, noise_var, coh=1, out=None, nv_out=None, stream=None):
+    """Maximal-ratio combiner of R receive branches: complex64
+    [B, R, S] device symbols, branch r of burst b received through the known gains
+    h[b, r], complex64 [B, R, ceil(S / coh)], -> (z complex64 [B, S], nv_sym float64 [B, S]),
+    what equalize_device gives for one branch, stream-ordered, for compute_llr_device /
+    demap_planes_device to read in place.  noise_var: a scalar or a float64 [B] device
+    tensor (common to a burst's branches: z = sum conj(h) y / sum |h|^2, nv_sym = noise_var /
+    sum |h|^2), or a float64 [B, R] device tensor (each branch its own: every term weighted
+    by 1 / noise_var[b, r], nv_sym = 1 / sum (|h|^2 / noise_var)).  A branch whose |h|^2 is
+    zero or not finite is skipped; with none left the symbol is an erasure, z = 0 and
+    nv_sym = +inf (zero LLRs).  R = 1 with a common noise_var is equalize_device bit for bit."""
+    import torch
+    if not isinstance(y, torch.Tensor) or y.dtype != torch.complex64:
+        raise TypeError(f"y must be a torch.complex64 tensor, got {getattr(y, 'dtype', type(y))}")
+    if not isinstance(h, torch.Tensor) or h.dtype != torch.complex64:
+        raise TypeError(f"h must be a torch.complex64 tensor, got {getattr(h, 'dtype', type(h))}")
+    if y.dim() != 3 or y.device.type != "cuda" or not y.is_contiguous():
+        raise ValueError("y must be a contiguous 3-D [B, R, S] tensor on a HIP device")
+    B, R, S = y.shape
+    if not 1 <= R <= MAX_BRANCHES:
+        raise ValueError(f"1 .. {MAX_BRANCHES} branches, got {R}")
+    coh = int(coh)
+    if coh < 1:
+        raise ValueError("coh must be >= 1")
+    nh = -(-S // coh)
+    if tuple(h.shape) != (B, R, nh) or not h.is_contiguous() or h.device != y.device:
+        raise ValueError(f"h must be a contiguous tensor of shape ({B}, {R}, {nh}) on the symbols' device, "
+                         f"got {tuple(h.shape)}")
+    rows = branches = None
+    if isinstance(noise_var, torch.Tensor):
+        if noise_var.dtype != torch.float64:
+            raise TypeError(f"noise_var must be torch.float64, got {noise_var.dtype}")
+        if tuple(noise_var.shape) not in ((B,), (B, R)) or not noise_var.is_contiguous():
+            raise ValueError(f"noise_var must be a contiguous tensor of shape ({B},) or ({B}, {R}), "
+                             f"got {tuple(noise_var.shape)}")
+        if noise_var.device != y.device:
+            raise ValueError("noise_var must be on the symbols' HIP device")
+        if noise_var.dim() == 2:
+            branches = noise_var
+        else:
+            rows = noise_var
+    if out is None:
+        out = torch.empty((B, S), dtype=torch.complex64, device=y.device)
+    elif out.dtype != torch.complex64 or tuple(out.shape) != (B, S) or not out.is_contiguous() or out.device != y.device:
+        raise ValueError(f"out must be a contiguous complex64 tensor of shape ({B}, {S}) on the symbols' device")
+    if nv_out is None:
+        nv_out = torch.empty((B, S), dtype=torch.float64, device=y.device)
+    else:
+        _nv_check(out, nv_out, "symbol", "nv_out")
+    dev = y.device.index or 0
+    st = _n.stream_ptr(stream) if stream is not None else torch.cuda.current_stream(dev).cuda_stream
+    _n.check(_n.lib().tdec_combine_dev(dev, _n.ptr(y), _n.ptr(h), B, R, S, coh,
+                                       0.0 if isinstance(noise_var, torch.Tensor) else float(noise_var),
+                                       _n.ptr(rows), _n.ptr(branches), _n.ptr(out), _n.ptr(nv_out), st))
+    return out, nv_out
+
+
 def estimate_noise_var_device(syms, mod_type, floor=0.02, out=None, stream=None):
     """The receiver's decision-directed noise variance (test_sdr_with_coding.py:459-467:
     hard decision, re-map, mean |rx - const|^2, max(nv, 0.02)) of each row of complex64

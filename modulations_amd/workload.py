@@ -38,7 +38,13 @@ def make_symbols(codec, B, mod, ebn0_db, seed, device, cw0=0, want_info=True, fa
     cfo > 0 rotates frame position t of codeword g by exp(j 2 pi f_g t), f_g uniform in
     (-cfo, cfo) cycles per symbol per global codeword.  The result is then (info, frames, N0,
     h_true), frames and h_true complex64 [B, T], h_true the gain each position went through
-    (rotation included); the data positions of a cfo = 0 frame are the unframed symbols."""
+    (rotation included); the data positions of a cfo = 0 frame are the unframed symbols.
+
+    fading={..., "branches": R} (1 <= R <= 8): R independently faded,
+    independently noisy copies of every codeword (tdec_workload_branches_dev, and
+    tdec_workload_frame_branches_dev with `pilots`); symbols and gains, or frames and h_true,
+    are then 3-D, [B, R, ...], branch 0 what the call without "branches" returns.  ebn0_db is
+    per branch: the array gain is not charged."""
     import torch
     from . import _native as _n
     bps = D.MODULATIONS[mod]["bps"]
@@ -55,12 +61,18 @@ def make_symbols(codec, B, mod, ebn0_db, seed, device, cw0=0, want_info=True, fa
     if pilots is None and cfo:
         raise ValueError("cfo needs pilots=PilotLayout(...)")
     if fading is not None:
-        unknown = set(fading) - {"K", "coh"}
+        unknown = set(fading) - {"K", "coh", "branches"}
         if unknown:
-            raise ValueError(f"fading takes the keys 'K' and 'coh', not {sorted(unknown)}")
+            raise ValueError(f"fading takes the keys 'K', 'coh' and 'branches', not {sorted(unknown)}")
         k, coh = float(fading.get("K", 0.0)), int(fading.get("coh", 1))
         if not (0.0 <= k < float("inf")) or coh < 1:
             raise ValueError("fading needs a finite K >= 0 and coh >= 1")
+        R = fading.get("branches")
+        if R is not None:
+            R = int(R)
+            if not 1 <= R <= D.MAX_BRANCHES:
+                raise ValueError(f"fading: 1 .. {D.MAX_BRANCHES} branches, got {R}")
+            return _make_branches(codec, B, R, S, bps, cons, table, n0, k, coh, seed, device, cw0, info, pilots, cfo)
         gains = torch.empty((B, -(-S // coh)), dtype=torch.complex64, device=device)
         h.call("tdec_workload_fading_dev", int(B), int(cw0), int(seed) & 0xFFFFFFFFFFFFFFFF, _n.ptr(table), len(cons),
                bps, float(np.sqrt(n0 / 2)), k, coh, _n.ptr(syms), _n.ptr(gains), _n.ptr(info), codec._stream(None))
@@ -82,6 +94,34 @@ def make_symbols(codec, B, mod, ebn0_db, seed, device, cw0=0, want_info=True, fa
     h.call("tdec_workload_dev", int(B), int(cw0), int(seed) & 0xFFFFFFFFFFFFFFFF, _n.ptr(table), len(cons), bps,
            float(np.sqrt(n0 / 2)), _n.ptr(syms), _n.ptr(info), codec._stream(None))
     return info, syms, n0
+
+
+def _make_branches(codec, B, R, S, bps, cons, table, n0, k, coh, seed, device, cw0, info, pilots, cfo):
+    """make_symbols' fading={..., "branches": R} form: (info, symbols [B, R, S], N0, gains
+    [B, R, nh]), or with pilots (info, frames [B, R, T], N0, h_true [B, R, T])."""
+    import torch
+    from . import _native as _n
+    if pilots is not None and not isinstance(pilots, D.PilotLayout):
+        raise TypeError(f"pilots must be a demap.PilotLayout, got {type(pilots)}")
+    if not (0.0 <= float(cfo) < float("inf")):
+        raise ValueError("cfo must be a finite value >= 0")
+    seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    sigma = float(np.sqrt(n0 / 2))
+    syms = torch.empty((B, R, S), dtype=torch.complex64, device=device)
+    gains = torch.empty((B, R, -(-S // coh)), dtype=torch.complex64, device=device)
+    codec.handle.call("tdec_workload_branches_dev", int(B), R, int(cw0), seed, _n.ptr(table), len(cons), bps, sigma, k,
+                      coh, _n.ptr(syms), _n.ptr(gains), _n.ptr(info), codec._stream(None))
+    if pilots is None:
+        return info, syms, n0, gains
+    T = pilots.frame_len(S)
+    frames = torch.empty((B, R, T), dtype=torch.complex64, device=device)
+    h_true = torch.empty((B, R, T), dtype=torch.complex64, device=device)
+    if B:
+        _n.check(_n.lib().tdec_workload_frame_branches_dev(
+            codec.handle.device, _n.ptr(syms), _n.ptr(gains), int(B), R, S, coh, pilots.plen, pilots.dlen,
+            _n.ptr(pilots.pilots_device(S, frames.device)), sigma, int(cw0), seed, float(cfo), _n.ptr(frames),
+            _n.ptr(h_true), codec._stream(None)))
+    return info, frames, n0, h_true
 
 
 def info_bits(codec, B, seed, device, cw0=0):
@@ -142,7 +182,12 @@ class DevicePipeline:
     with known gains and demaps them with a per-symbol noise variance:
     three launches on one stream; fused=True refuses it likewise.  run_frames() takes framed
     bursts with pilot blocks instead and estimates the gains (and, if asked, the noise
-    variance) from them in the launch that equalises."""
+    variance) from them in the launch that equalises.
+
+    Receive diversity: 3-D symbols [B, R, S] with csi [B, R, nh] go through
+    the maximal-ratio combiner (demap.combine_device) in place of the equaliser, 3-D frames
+    [B, R, T] through the pilot strip on all B * R rows and then the combiner; `z` and
+    `nv_sym` are the same buffers, and everything behind them is unchanged."""
 
     def __init__(self, codec, mod, B, device, fused=False, overlap=False, gate=True, demap="max-log", csi=False):
         import torch
@@ -165,6 +210,7 @@ class DevicePipeline:
         self.bits = torch.empty((B, codec.k_info), dtype=torch.int32, device=device)
         self.n_iter = torch.empty(B, dtype=torch.int32, device=device) if self.early_stop else None
         self.z = self.nv_sym = None
+        self._strip = {}                          # run_frames' per-branch buffers, by R (sized on first use)
         if csi:
             S = -(-codec.handle.enc_len // self.bps)
             self.z = torch.empty((B, S), dtype=torch.complex64, device=device)
@@ -201,16 +247,26 @@ class DevicePipeline:
         csi: the channel gains of `syms`, complex64 [B, ceil(S / coh)] on their device
         (symbol s of a row was received through csi[:, s // coh]); the symbols are
         equalised into `z` and demapped with `nv_sym` = noise_var / |csi|^2 per symbol.
-        Needs a pipeline built with csi=True."""
+        Needs a pipeline built with csi=True.
+
+        3-D `syms` [B, R, S] (with csi [B, R, nh]) are R receive branches of each burst: the
+        combiner takes the equaliser's place; noise_var may then also be a float64 [B, R]
+        tensor, one value per branch."""
+        if syms.dim() == 3 and csi is None:
+            raise ValueError("3-D symbols are receive branches: they need their gains (csi=h)")
         if csi is not None:
             if self.fused_asked:
                 raise ValueError("csi needs the two-launch pipeline: the fused demap+decode kernel has no "
                                  "per-symbol form (fused=True)")
             if self.z is None:
                 raise ValueError("csi needs a pipeline built with csi=True")
-            if syms.shape[0] > self.B or syms.shape[1] != self.z.shape[1]:
-                raise ValueError(f"csi: symbols must be [<= {self.B}, {self.z.shape[1]}], got {tuple(syms.shape)}")
+            if syms.shape[0] > self.B or syms.shape[-1] != self.z.shape[1]:
+                raise ValueError(f"csi: symbols must be [<= {self.B}, {self.z.shape[1]}] or [<= {self.B}, R, "
+                                 f"{self.z.shape[1]}], got {tuple(syms.shape)}")
         front = None
+        if csi is not None and syms.dim() == 3:
+            front = lambda st: self._combine(syms, csi, noise_var, coh, st)  # noqa: E731
+            return self._run(syms, 1.0, stream, events, syms_ready, front)
         if csi is not None:
             front = lambda st: self._equalize(syms, csi, noise_var, coh, st)  # noqa: E731
         return self._run(syms, noise_var, stream, events, syms_ready, front)
@@ -220,13 +276,20 @@ class DevicePipeline:
         estimate and the equalisation in one launch into `z` / `nv_sym`, the per-symbol
         demap, the decode, all on `stream`.  noise_var: a scalar, a float64 [B] device
         tensor, or None: each burst's own estimate from its pilots (plen >= 2).  Needs a
-        pipeline built with csi=True; fused=True refuses it as it refuses csi."""
+        pipeline built with csi=True; fused=True refuses it as it refuses csi.
+
+        3-D `frames` [B, R, T] are R receive branches of each burst: one strip
+        launch over the B * R rows (stripped data, interpolated gains and, for noise_var None,
+        each branch's own noise estimate), then the combiner; an estimated noise goes in per
+        branch, a scalar or [B] noise_var as the common one."""
         if self.fused_asked:
             raise ValueError("framed bursts need the two-launch pipeline: the fused demap+decode kernel has no "
                              "per-symbol form (fused=True)")
         if self.z is None:
             raise ValueError("run_frames needs a pipeline built with csi=True")
         S = self.z.shape[1]
+        if frames.dim() == 3:
+            return self._run_branch_frames(frames, layout, noise_var, mode, stream, events)
         if frames.dim() != 2 or frames.shape[0] > self.B or frames.shape[1] != layout.frame_len(S):
             raise ValueError(f"frames must be [<= {self.B}, {layout.frame_len(S)}], got {tuple(frames.shape)}")
         n = frames.shape[0]
@@ -234,6 +297,32 @@ class DevicePipeline:
         def front(st):
             z, nvs = D.estimate_csi_device(frames, layout, noise_var, mode=mode, out=self.z[:n],
                                            nv_out=self.nv_sym[:n], stream=st)
+            return z, nvs, D.demap_mode(np.complex64, self.cons.dtype, np.float64(1.0))[1]
+        return self._run(frames, 1.0, stream, events, None, front)
+
+    def _run_branch_frames(self, frames, layout, noise_var, mode, stream, events):
+        """run_frames for [B, R, T]: strip on B * R rows, then combine."""
+        import torch
+        S = self.z.shape[1]
+        n, R, T = frames.shape
+        if n > self.B or not 1 <= R <= D.MAX_BRANCHES or T != layout.frame_len(S):
+            raise ValueError(f"frames must be [<= {self.B}, 1 .. {D.MAX_BRANCHES}, {layout.frame_len(S)}], "
+                             f"got {tuple(frames.shape)}")
+        if not frames.is_contiguous():
+            raise ValueError("frames must be a contiguous tensor on a HIP device")
+        if R not in self._strip:
+            dev = self.z.device
+            self._strip[R] = (torch.empty((self.B * R, S), dtype=torch.complex64, device=dev),
+                              torch.empty((self.B * R, S), dtype=torch.complex64, device=dev),
+                              torch.empty(self.B * R, dtype=torch.float64, device=dev))
+        y, h, nvb = (t[:n * R] for t in self._strip[R])
+        estimate = noise_var is None
+
+        def front(st):
+            D.strip_pilots_device(frames.view(n * R, T), layout, mode=mode, out=y, h_out=h,
+                                  nv_rows_out=nvb if estimate else None, stream=st)
+            z, nvs = D.combine_device(y.view(n, R, S), h.view(n, R, S), nvb.view(n, R) if estimate else noise_var,
+                                      coh=1, out=self.z[:n], nv_out=self.nv_sym[:n], stream=st)
             return z, nvs, D.demap_mode(np.complex64, self.cons.dtype, np.float64(1.0))[1]
         return self._run(frames, 1.0, stream, events, None, front)
 
@@ -301,4 +390,10 @@ class DevicePipeline:
         division's dtype is the tensor forms'."""
         n = syms.shape[0]
         z, nvs = D.equalize_device(syms, csi, nv, coh=coh, out=self.z[:n], nv_out=self.nv_sym[:n], stream=stream)
+        return z, nvs, D.demap_mode(np.complex64, self.cons.dtype, np.float64(1.0))[1]
+
+    def _combine(self, syms, csi, nv, coh, stream):
+        """_equalize for [B, R, S] receive branches: the maximal-ratio combiner."""
+        n = syms.shape[0]
+        z, nvs = D.combine_device(syms, csi, nv, coh=coh, out=self.z[:n], nv_out=self.nv_sym[:n], stream=stream)
         return z, nvs, D.demap_mode(np.complex64, self.cons.dtype, np.float64(1.0))[1]
