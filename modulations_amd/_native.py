@@ -52,150 +52,61 @@ _vp = C.c_void_p
 
 
 def _declare(L):
-    L.tdec_create.argtypes = [C.c_int, C.c_int, C.c_int, _vp, C.c_int, C.c_int, _vp, _vp, _vp, C.POINTER(_vp)]
-    L.tdec_create.restype = C.c_int
-    L.tdec_destroy.argtypes = [_vp]
-    L.tdec_destroy.restype = None
-    L.tdec_last_error.argtypes = []
-    L.tdec_last_error.restype = C.c_char_p
-    L.tdec_llr_len.argtypes = [_vp]
-    L.tdec_llr_len.restype = C.c_long
-    L.tdec_encoded_len.argtypes = [_vp]
-    L.tdec_encoded_len.restype = C.c_long
-    L.tdec_siso_batch.argtypes = [_vp, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, C.c_double, _vp, _vp]
-    if hasattr(L, "tdec_siso_batch_f64"):   # (A/B tools also load older builds without it)
-        L.tdec_siso_batch_f64.argtypes = [_vp, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, C.c_double, _vp, _vp]
-        L.tdec_siso_batch_f64.restype = C.c_int
-        L.tdec_siso_staging.argtypes = [_vp, C.c_int, C.POINTER(_vp), C.POINTER(C.c_size_t)]
-        L.tdec_siso_staging.restype = C.c_int
-        L.tdec_siso_staged.argtypes = [_vp, C.c_int, C.c_int, C.c_double]
-        L.tdec_siso_staged.restype = C.c_int
-    if hasattr(L, "tdec_siso_stats"):
-        L.tdec_siso_stats.argtypes = [_vp, C.POINTER(C.c_long)]
-        L.tdec_siso_stats.restype = C.c_int
-    L.tdec_decode_batch.argtypes = [_vp, C.c_int, _vp, C.c_long, _vp, _vp]
-    L.tdec_reserve.argtypes = [_vp, C.c_int]
-    L.tdec_planes_bytes.argtypes = [_vp, C.c_int]
-    L.tdec_planes_bytes.restype = C.c_size_t
-    L.tdec_depuncture_dev.argtypes = [_vp, C.c_int, _vp, C.c_long, _vp, _vp]
-    L.tdec_decode_planes_dev.argtypes = [_vp, C.c_int, _vp, _vp, _vp, _vp]
-    L.tdec_decode_batch_dev.argtypes = [_vp, C.c_int, _vp, C.c_long, _vp, _vp, _vp]
-    if hasattr(L, "tdec_decode_batch_es"):   # (A/B tools also load older builds without early stop)
-        L.tdec_decode_batch_es.argtypes = [_vp, C.c_int, _vp, C.c_long, _vp, _vp, _vp]
-        L.tdec_decode_planes_es_dev.argtypes = [_vp, C.c_int, _vp, _vp, _vp, _vp, _vp]
-        L.tdec_decode_batch_es_dev.argtypes = [_vp, C.c_int, _vp, C.c_long, _vp, _vp, _vp, _vp]
-        L.tdec_es_capacity.argtypes = [_vp]
-        L.tdec_early_stop_available.argtypes = [C.c_int]
-        for f in (L.tdec_decode_batch_es, L.tdec_decode_planes_es_dev, L.tdec_decode_batch_es_dev, L.tdec_es_capacity,
-                  L.tdec_early_stop_available):
-            f.restype = C.c_int
-    if hasattr(L, "tdec_decode_batch_es_tile"):   # (A/B tools also load older builds without the tile early stop)
-        L.tdec_decode_batch_es_tile.argtypes = [_vp, C.c_int, _vp, C.c_long, _vp, _vp, _vp]
-        L.tdec_decode_planes_es_tile_dev.argtypes = [_vp, C.c_int, _vp, _vp, _vp, _vp, _vp]
-        L.tdec_decode_batch_es_tile_dev.argtypes = [_vp, C.c_int, _vp, C.c_long, _vp, _vp, _vp, _vp]
-        for f in (L.tdec_decode_batch_es_tile, L.tdec_decode_planes_es_tile_dev, L.tdec_decode_batch_es_tile_dev):
-            f.restype = C.c_int
-    if hasattr(L, "tdec_decode_batch_es_refill"):   # (A/B tools also load older builds without the refill early stop)
-        L.tdec_reserve_es_refill.argtypes = [_vp, C.c_int]
-        L.tdec_decode_batch_es_refill.argtypes = [_vp, C.c_int, _vp, C.c_long, _vp, _vp, _vp]
-        L.tdec_decode_planes_es_refill_dev.argtypes = [_vp, C.c_int, _vp, _vp, _vp, _vp, _vp]
-        L.tdec_decode_batch_es_refill_dev.argtypes = [_vp, C.c_int, _vp, C.c_long, _vp, _vp, _vp, _vp]
-        L.tdec_es_refill_stats.argtypes = [_vp, C.POINTER(C.c_long), C.POINTER(C.c_long)]
-        for f in (L.tdec_reserve_es_refill, L.tdec_decode_batch_es_refill, L.tdec_decode_planes_es_refill_dev,
-                  L.tdec_decode_batch_es_refill_dev, L.tdec_es_refill_stats):
-            f.restype = C.c_int
-    if hasattr(L, "tdec_tail_gate"):   # (A/B tools also load older builds without it)
-        L.tdec_tail_gate.argtypes = [_vp, _vp]
-    L.tdec_demap_dev.argtypes = [C.c_int, _vp, C.c_int, C.c_long, _vp, C.c_int, C.c_int, C.c_int, C.c_double,
-                                 C.c_int, C.c_int, _vp, _vp]
-    L.tdec_demap.argtypes = [C.c_int, _vp, C.c_int, C.c_long, _vp, C.c_int, C.c_int, C.c_int, C.c_double,
-                             C.c_int, C.c_int, _vp]
-    L.tdec_demap_planes_dev.argtypes = [_vp, C.c_int, _vp, C.c_int, _vp, C.c_int, C.c_int, C.c_int, C.c_double,
-                                        C.c_int, _vp, _vp]
-    if hasattr(L, "tdec_demap_logmap_dev"):   # (A/B tools also load older builds without the log-MAP demapper)
-        L.tdec_demap_logmap_dev.argtypes = [C.c_int, _vp, C.c_int, C.c_long, _vp, C.c_int, C.c_int, C.c_int,
-                                            C.c_double, C.c_int, _vp, _vp]
-        L.tdec_demap_logmap.argtypes = [C.c_int, _vp, C.c_int, C.c_long, _vp, C.c_int, C.c_int, C.c_int, C.c_double,
-                                        C.c_int, _vp]
-        L.tdec_demap_planes_logmap_dev.argtypes = [_vp, C.c_int, _vp, C.c_int, _vp, C.c_int, C.c_int, C.c_int,
-                                                   C.c_double, _vp, _vp]
-        for f in (L.tdec_demap_logmap_dev, L.tdec_demap_logmap, L.tdec_demap_planes_logmap_dev):
-            f.restype = C.c_int
-    if hasattr(L, "tdec_noise_var_dev"):   # (A/B tools also load older builds without the per-row noise variance)
-        L.tdec_noise_var_dev.argtypes = [C.c_int, _vp, C.c_int, C.c_int, _vp, C.c_int, C.c_int, C.c_double, _vp, _vp]
-        L.tdec_demap_rows_dev.argtypes = [C.c_int, _vp, C.c_int, C.c_int, C.c_int, _vp, C.c_int, C.c_int, C.c_int,
-                                          _vp, C.c_int, C.c_int, _vp, _vp]
-        L.tdec_demap_rows_logmap_dev.argtypes = [C.c_int, _vp, C.c_int, C.c_int, C.c_int, _vp, C.c_int, C.c_int,
-                                                 C.c_int, _vp, C.c_int, _vp, _vp]
-        L.tdec_demap_planes_nv_dev.argtypes = [_vp, C.c_int, _vp, C.c_int, _vp, C.c_int, C.c_int, C.c_int, _vp,
-                                               C.c_int, _vp, _vp]
-        L.tdec_demap_planes_logmap_nv_dev.argtypes = [_vp, C.c_int, _vp, C.c_int, _vp, C.c_int, C.c_int, C.c_int,
-                                                      _vp, _vp, _vp]
-        for f in (L.tdec_noise_var_dev, L.tdec_demap_rows_dev, L.tdec_demap_rows_logmap_dev,
-                  L.tdec_demap_planes_nv_dev, L.tdec_demap_planes_logmap_nv_dev):
-            f.restype = C.c_int
-    if hasattr(L, "tdec_equalize_dev"):   # (A/B tools also load older builds without the per-symbol noise variance)
-        L.tdec_symnv_demap_dev.argtypes = L.tdec_demap_rows_dev.argtypes
-        L.tdec_symnv_demap_logmap_dev.argtypes = L.tdec_demap_rows_logmap_dev.argtypes
-        L.tdec_symnv_demap_planes_dev.argtypes = L.tdec_demap_planes_nv_dev.argtypes
-        L.tdec_symnv_demap_planes_logmap_dev.argtypes = L.tdec_demap_planes_logmap_nv_dev.argtypes
-        L.tdec_equalize_dev.argtypes = [C.c_int, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_double, _vp, _vp, _vp, _vp]
-        L.tdec_workload_fading_dev.argtypes = [_vp, C.c_int, C.c_int64, C.c_uint64, _vp, C.c_int, C.c_int, C.c_double,
-                                               C.c_double, C.c_int, _vp, _vp, _vp, _vp]
-        for f in (L.tdec_symnv_demap_dev, L.tdec_symnv_demap_logmap_dev, L.tdec_symnv_demap_planes_dev,
-                  L.tdec_symnv_demap_planes_logmap_dev, L.tdec_equalize_dev, L.tdec_workload_fading_dev):
-            f.restype = C.c_int
-    if hasattr(L, "tdec_csi_pilots_dev"):   # (A/B tools also load older builds without the pilot estimator)
-        L.tdec_csi_pilots_dev.argtypes = [C.c_int, _vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, C.c_int, C.c_double,
-                                          _vp, C.c_double, _vp, _vp, _vp, _vp, _vp]
-        L.tdec_csi_strip_dev.argtypes = [C.c_int, _vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, C.c_int, C.c_double,
-                                         _vp, _vp, _vp, _vp]
-        L.tdec_workload_frame_dev.argtypes = [C.c_int, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp,
-                                              C.c_double, C.c_int64, C.c_uint64, C.c_double, _vp, _vp, _vp]
-        for f in (L.tdec_csi_pilots_dev, L.tdec_csi_strip_dev, L.tdec_workload_frame_dev):
-            f.restype = C.c_int
-    if hasattr(L, "tdec_combine_dev"):   # (A/B tools also load older builds without receive diversity)
-        L.tdec_combine_dev.argtypes = [C.c_int, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, _vp, _vp, _vp,
-                                       _vp, _vp]
-        L.tdec_workload_branches_dev.argtypes = [_vp, C.c_int, C.c_int, C.c_int64, C.c_uint64, _vp, C.c_int, C.c_int,
-                                                 C.c_double, C.c_double, C.c_int, _vp, _vp, _vp, _vp]
-        L.tdec_workload_frame_branches_dev.argtypes = [C.c_int, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
-                                                       C.c_int, _vp, C.c_double, C.c_int64, C.c_uint64, C.c_double, _vp,
-                                                       _vp, _vp]
-        for f in (L.tdec_combine_dev, L.tdec_workload_branches_dev, L.tdec_workload_frame_branches_dev):
-            f.restype = C.c_int
-    L.tdec_encode_dev.argtypes = [_vp, C.c_int, _vp, _vp, _vp]
-    L.tdec_demap_batch.argtypes = [C.c_int, C.c_int, C.c_int, _vp, C.c_long, C.c_float, _vp]
-    L.tdec_constellation.argtypes = [C.c_int, _vp, C.POINTER(C.c_int)]
-    L.tdec_workload_dev.argtypes = [_vp, C.c_int, C.c_int64, C.c_uint64, _vp, C.c_int, C.c_int, C.c_double, _vp,
-                                    _vp, _vp]
-    L.tdec_info_bits_dev.argtypes = [_vp, C.c_int, C.c_int64, C.c_uint64, _vp, _vp]
-    L.tdec_count_errors_dev.argtypes = [_vp, C.c_int, C.c_int64, C.c_uint64, _vp, _vp, _vp]
-    L.tdec_reserve_fused.argtypes = [_vp, C.c_int]
-    L.tdec_fused_available.argtypes = [_vp, C.c_int, C.c_int]
-    L.tdec_demap_decode_dev.argtypes = [_vp, C.c_int, _vp, C.c_int, _vp, C.c_int, C.c_int, C.c_int, C.c_double,
-                                        C.c_int, _vp, _vp, _vp]
-    L.tdec_selftest.argtypes = [C.c_int, C.c_int, C.c_longlong, C.c_ulonglong, C.POINTER(C.c_longlong)]
-    L.tdec_selftest_trans.argtypes = [C.c_int, C.c_int, C.c_uint32, C.c_longlong, _vp]
-    L.tdec_host_alloc.argtypes = [C.c_size_t, C.POINTER(_vp)]
-    L.tdec_host_free.argtypes = [_vp]
-    L.tdec_host_free.restype = None
-    if hasattr(L, "tdec_encode_host"):   # (A/B tools also load older builds without it)
-        L.tdec_encode_host.argtypes = [C.c_int, C.c_int, _vp, _vp, C.c_long, _vp, C.c_long, _vp, C.c_long]
-        L.tdec_encode_host.restype = C.c_long
+    """argtypes and restype of every export the loaded library has: the A/B tools also load older builds
+    through this, and an export such a build lacks is skipped."""
+    i, l, d, p, q, Q, z, ptr = C.c_int, C.c_long, C.c_double, _vp, C.c_int64, C.c_uint64, C.c_size_t, C.POINTER
+    siso = [p, i, p, p, p, p, p, p, d, p, p]
+    batch, batch_es, planes_es = [p, i, p, l, p, p], [p, i, p, l, p, p, p], [p, i, p, p, p, p, p]
+    flat = [i, p, i, l, p, i, i, i, d]                    # the flat demappers up to their scalar noise_var
+    rows = [i, p, i, i, i, p, i, i, i, p]                 # their per-row and per-symbol forms up to the tensor
+    planes = [p, i, p, i, p, i, i, i]                     # the plane demappers up to M, bps
+    symbols = [p, i, q, Q, p, i, i, d]                    # the symbol generators up to sigma
+    frame = [i, i, i, i, p, d, q, Q, d, p, p, p]          # the framing generators from S on
+    argtypes = {
+        "tdec_create": [i, i, i, p, i, i, p, p, p, ptr(p)], "tdec_destroy": [p], "tdec_last_error": [],
+        "tdec_llr_len": [p], "tdec_encoded_len": [p], "tdec_reserve": [p, i], "tdec_planes_bytes": [p, i],
+        "tdec_siso_batch": siso, "tdec_siso_batch_f64": siso, "tdec_siso_staging": [p, i, ptr(p), ptr(z)],
+        "tdec_siso_staged": [p, i, i, d], "tdec_siso_stats": [p, ptr(l)],
+        "tdec_depuncture_dev": batch, "tdec_tail_gate": [p, p],
+        "tdec_decode_batch": batch, "tdec_decode_planes_dev": [p, i, p, p, p, p], "tdec_decode_batch_dev": batch + [p],
+        "tdec_decode_batch_es": batch_es, "tdec_decode_planes_es_dev": planes_es,
+        "tdec_decode_batch_es_dev": batch_es + [p], "tdec_es_capacity": [p], "tdec_early_stop_available": [i],
+        "tdec_decode_batch_es_tile": batch_es, "tdec_decode_planes_es_tile_dev": planes_es,
+        "tdec_decode_batch_es_tile_dev": batch_es + [p],
+        "tdec_reserve_es_refill": [p, i], "tdec_decode_batch_es_refill": batch_es,
+        "tdec_decode_planes_es_refill_dev": planes_es, "tdec_decode_batch_es_refill_dev": batch_es + [p],
+        "tdec_es_refill_stats": [p, ptr(l), ptr(l)],
+        "tdec_demap_dev": flat + [i, i, p, p], "tdec_demap": flat + [i, i, p],
+        "tdec_demap_logmap_dev": flat + [i, p, p], "tdec_demap_logmap": flat + [i, p],
+        "tdec_demap_rows_dev": rows + [i, i, p, p], "tdec_demap_rows_logmap_dev": rows + [i, p, p],
+        "tdec_symnv_demap_dev": rows + [i, i, p, p], "tdec_symnv_demap_logmap_dev": rows + [i, p, p],
+        "tdec_demap_planes_dev": planes + [d, i, p, p], "tdec_demap_planes_logmap_dev": planes + [d, p, p],
+        "tdec_demap_planes_nv_dev": planes + [p, i, p, p], "tdec_demap_planes_logmap_nv_dev": planes + [p, p, p],
+        "tdec_symnv_demap_planes_dev": planes + [p, i, p, p], "tdec_symnv_demap_planes_logmap_dev": planes + [p, p, p],
+        "tdec_reserve_fused": [p, i], "tdec_fused_available": [p, i, i],
+        "tdec_demap_decode_dev": planes + [d, i, p, p, p],
+        "tdec_demap_batch": [i, i, i, p, l, C.c_float, p], "tdec_constellation": [i, p, ptr(i)],
+        "tdec_noise_var_dev": [i, p, i, i, p, i, i, d, p, p],
+        "tdec_equalize_dev": [i, p, p, i, i, i, d, p, p, p, p],
+        "tdec_combine_dev": [i, p, p, i, i, i, i, d, p, p, p, p, p],
+        "tdec_csi_pilots_dev": [i, p, i, i, i, i, p, i, d, p, d, p, p, p, p, p],
+        "tdec_csi_strip_dev": [i, p, i, i, i, i, p, i, d, p, p, p, p],
+        "tdec_encode_dev": [p, i, p, p, p], "tdec_encode_host": [i, i, p, p, l, p, l, p, l],
+        "tdec_info_bits_dev": [p, i, q, Q, p, p], "tdec_count_errors_dev": [p, i, q, Q, p, p, p],
+        "tdec_workload_dev": symbols + [p, p, p], "tdec_workload_fading_dev": symbols + [d, i, p, p, p, p],
+        "tdec_workload_branches_dev": [p, i, i, q, Q, p, i, i, d, d, i, p, p, p, p],
+        "tdec_workload_frame_dev": [i, p, p, i] + frame, "tdec_workload_frame_branches_dev": [i, p, p, i, i] + frame,
+        "tdec_selftest": [i, i, C.c_longlong, C.c_ulonglong, ptr(C.c_longlong)],
+        "tdec_selftest_trans": [i, i, C.c_uint32, C.c_longlong, p],
+        "tdec_host_alloc": [z, ptr(p)], "tdec_host_free": [p],
+    }
+    # int (a status, or a small count) is what every export returns but these
+    restype = {"tdec_destroy": None, "tdec_host_free": None, "tdec_last_error": C.c_char_p, "tdec_llr_len": l,
+               "tdec_encoded_len": l, "tdec_encode_host": l, "tdec_planes_bytes": z}
     for name in EXPORTS:
-        if not hasattr(L, name):
-            continue
-        f = getattr(L, name)
-        if f.restype is C.c_int or name in ("tdec_siso_batch", "tdec_decode_batch", "tdec_reserve",
-                                            "tdec_depuncture_dev", "tdec_decode_planes_dev",
-                                            "tdec_decode_batch_dev", "tdec_demap_dev", "tdec_demap",
-                                            "tdec_demap_planes_dev", "tdec_encode_dev", "tdec_demap_batch",
-                                            "tdec_constellation", "tdec_workload_dev", "tdec_info_bits_dev",
-                                            "tdec_count_errors_dev", "tdec_reserve_fused", "tdec_fused_available",
-                                            "tdec_demap_decode_dev", "tdec_selftest", "tdec_selftest_trans",
-                                            "tdec_host_alloc"):
-            f.restype = C.c_int
+        if hasattr(L, name):
+            f = getattr(L, name)
+            f.argtypes, f.restype = argtypes[name], restype.get(name, i)
 
 
 def lib():

@@ -1984,18 +1984,12 @@ static WorkloadArgs workload_args(const tdec_t *h, int B) {
 }
 static bool staged_encoder_ok(const tdec_t *h) { return h->N % 4 == 0 && h->N <= ENC_MAX_N; }
 
-extern "C" {
-
-int tdec_workload_dev(tdec_t *h, int B, int64_t cw0, uint64_t seed, const float *cons_iq, int M, int bps,
-                      double sigma, float *d_syms, uint8_t *d_info, void *stream) {
-    if (!h || B < 0 || cw0 < 0) return fail(TDEC_EINVAL, "bad workload arguments");
-    if (B == 0) return 0;
-    // every bps-bit label indexes the table, so it must hold all 2^bps points
-    if (!cons_iq || !d_syms || bps < 1 || bps > 8 || M != (1 << bps) || !(sigma >= 0.0))
-        return fail(TDEC_EINVAL, "bad workload arguments (the constellation must have 2^bps points)");
-    if (!staged_encoder_ok(h)) return fail(TDEC_EINVAL, "workload generation needs N % 4 == 0 and N <= 1024");
-    Guard g(h->device);
-    WorkloadArgs a = workload_args(h, B);
+// The symbol generators' WorkloadArgs, or false for a bad argument (the caller words the refusal).
+// Every bps-bit label indexes the table, so it must hold all 2^bps points.
+static bool symbol_args(WorkloadArgs &a, const tdec_t *h, int B, int64_t cw0, uint64_t seed, const float *cons_iq, int M,
+                        int bps, double sigma, float *d_syms, uint8_t *d_info) {
+    if (!cons_iq || !d_syms || bps < 1 || bps > 8 || M != (1 << bps) || !(sigma >= 0.0)) return false;
+    a = workload_args(h, B);
     a.bps = bps;
     a.M = M;
     a.S = (int)((h->enc_len + bps - 1) / bps);
@@ -2005,24 +1999,51 @@ int tdec_workload_dev(tdec_t *h, int B, int64_t cw0, uint64_t seed, const float 
     for (int m = 0; m < M; ++m) a.cons[m] = make_float2(cons_iq[2 * m], cons_iq[2 * m + 1]);
     a.info_out = d_info;
     a.syms = reinterpret_cast<float2 *>(d_syms);
-    hipLaunchKernelGGL(k_workload, dim3((unsigned)n_tiles_of(B)), dim3(64), 0, (hipStream_t)stream, a);
+    return true;
+}
+
+// Likewise the fading generators' FadeArgs (the base of a BranchArgs), S symbols per codeword.
+static bool fade_args(FadeArgs &f, double rician_k, int coh, int S, float *d_h) {
+    if (!d_h || coh < 1 || !(rician_k >= 0.0) || !(rician_k < INFINITY)) return false;
+    f.h = reinterpret_cast<float2 *>(d_h);
+    f.coh = coh;
+    f.nh = (S + coh - 1) / coh;
+    f.los = (float)std::sqrt(rician_k / (rician_k + 1.0));
+    f.scat = (float)std::sqrt(1.0 / (rician_k + 1.0));
+    return true;
+}
+static const char BAD_FADING[] = "bad workload arguments (the constellation must have 2^bps points; K >= 0, coh >= 1)";
+
+// A staged-encoder kernel over B codewords, one 64-codeword tile per block; its refusal is the last.
+template <typename... A> static int workload_launch(const tdec_t *h, int B, void (*k)(A...), void *stream, A... a) {
+    if (!staged_encoder_ok(h)) return fail(TDEC_EINVAL, "workload generation needs N % 4 == 0 and N <= 1024");
+    Guard g(h->device);
+    hipLaunchKernelGGL(k, dim3((unsigned)n_tiles_of(B)), dim3(64), 0, (hipStream_t)stream, a...);
     HIPCHK(hipGetLastError());
     return 0;
+}
+
+extern "C" {
+
+int tdec_workload_dev(tdec_t *h, int B, int64_t cw0, uint64_t seed, const float *cons_iq, int M, int bps,
+                      double sigma, float *d_syms, uint8_t *d_info, void *stream) {
+    if (!h || B < 0 || cw0 < 0) return fail(TDEC_EINVAL, "bad workload arguments");
+    if (B == 0) return 0;
+    WorkloadArgs a;
+    if (!symbol_args(a, h, B, cw0, seed, cons_iq, M, bps, sigma, d_syms, d_info))
+        return fail(TDEC_EINVAL, "bad workload arguments (the constellation must have 2^bps points)");
+    return workload_launch(h, B, k_workload, stream, a);
 }
 
 int tdec_info_bits_dev(tdec_t *h, int B, int64_t cw0, uint64_t seed, uint8_t *d_info, void *stream) {
     if (!h || B < 0 || cw0 < 0) return fail(TDEC_EINVAL, "bad info-bits arguments");
     if (B == 0) return 0;
     if (!d_info) return fail(TDEC_EINVAL, "bad info-bits arguments");
-    if (!staged_encoder_ok(h)) return fail(TDEC_EINVAL, "workload generation needs N % 4 == 0 and N <= 1024");
-    Guard g(h->device);
     WorkloadArgs a = workload_args(h, B);
     a.cw0 = (uint64_t)cw0;
     a.seed = seed;
     a.info_out = d_info;
-    hipLaunchKernelGGL(k_workload, dim3((unsigned)n_tiles_of(B)), dim3(64), 0, (hipStream_t)stream, a);
-    HIPCHK(hipGetLastError());
-    return 0;
+    return workload_launch(h, B, k_workload, stream, a);
 }
 
 int tdec_count_errors_dev(tdec_t *h, int B, int64_t cw0, uint64_t seed, const int32_t *d_bits, int32_t *d_errs,
@@ -2042,102 +2063,29 @@ int tdec_workload_fading_dev(tdec_t *h, int B, int64_t cw0, uint64_t seed, const
                              void *stream) {
     if (!h || B < 0 || cw0 < 0) return fail(TDEC_EINVAL, "bad workload arguments");
     if (B == 0) return 0;
-    if (!cons_iq || !d_syms || !d_h || bps < 1 || bps > 8 || M != (1 << bps) || !(sigma >= 0.0) || coh < 1 ||
-        !(rician_k >= 0.0) || !(rician_k < INFINITY))
-        return fail(TDEC_EINVAL, "bad workload arguments (the constellation must have 2^bps points; K >= 0, coh >= 1)");
-    if (!staged_encoder_ok(h)) return fail(TDEC_EINVAL, "workload generation needs N % 4 == 0 and N <= 1024");
-    Guard g(h->device);
-    WorkloadArgs a = workload_args(h, B);
-    a.bps = bps;
-    a.M = M;
-    a.S = (int)((h->enc_len + bps - 1) / bps);
-    a.cw0 = (uint64_t)cw0;
-    a.seed = seed;
-    a.sigma = (float)sigma;
-    for (int m = 0; m < M; ++m) a.cons[m] = make_float2(cons_iq[2 * m], cons_iq[2 * m + 1]);
-    a.info_out = d_info;
-    a.syms = reinterpret_cast<float2 *>(d_syms);
+    WorkloadArgs a;
     FadeArgs f{};
-    f.h = reinterpret_cast<float2 *>(d_h);
-    f.coh = coh;
-    f.nh = (a.S + coh - 1) / coh;
-    f.los = (float)std::sqrt(rician_k / (rician_k + 1.0));
-    f.scat = (float)std::sqrt(1.0 / (rician_k + 1.0));
-    hipLaunchKernelGGL(k_workload_fading, dim3((unsigned)n_tiles_of(B)), dim3(64), 0, (hipStream_t)stream, a, f);
-    HIPCHK(hipGetLastError());
-    return 0;
+    if (!symbol_args(a, h, B, cw0, seed, cons_iq, M, bps, sigma, d_syms, d_info) || !fade_args(f, rician_k, coh, a.S, d_h))
+        return fail(TDEC_EINVAL, BAD_FADING);
+    return workload_launch(h, B, k_workload_fading, stream, a, f);
 }
 
-int tdec_workload_frame_dev(int device, const float *d_y, const float *d_gains, int B, int S, int coh, int plen,
-                            int dlen, const float *d_pilots, double sigma, int64_t cw0, uint64_t seed, double cfo_max,
-                            float *d_frames, float *d_h_true, void *stream) {
-    if (B < 0 || cw0 < 0) return fail(TDEC_EINVAL, "bad frame arguments");
+// The framing generators.  branches: k_workload_frame_branches over B * R rows; else the single-branch
+// call, k_workload_frame over B rows, which passes R = 1.
+static int frame_launch(int device, const float *d_y, const float *d_gains, int B, bool branches, int R, int S, int coh,
+                        int plen, int dlen, const float *d_pilots, double sigma, int64_t cw0, uint64_t seed,
+                        double cfo_max, float *d_frames, float *d_h_true, void *stream) {
+    if (B < 0 || cw0 < 0 || R < 1 || R > 8)
+        return fail(TDEC_EINVAL, branches ? "bad frame arguments (1 <= R <= 8)" : "bad frame arguments");
     if (B == 0) return 0;
     if (!d_y || !d_gains || !d_pilots || !d_frames || S < 1 || coh < 1 || plen < 1 || dlen < 1 || !(sigma >= 0.0) ||
         !(cfo_max >= 0.0) || !(cfo_max < INFINITY))
         return fail(TDEC_EINVAL, "bad frame arguments (S, coh, plen, dlen >= 1; sigma >= 0; finite cfo_max >= 0)");
     const int J = (S + dlen - 1) / dlen;
     const long T = (long)S + (long)(J + 1) * plen;
-    if (T > INT32_MAX) return fail(TDEC_EINVAL, "bad frame arguments (frame too long)");
-    Guard g(device);
-    FrameArgs f{};
-    f.y = reinterpret_cast<const float2 *>(d_y);
-    f.gains = reinterpret_cast<const float2 *>(d_gains);
-    f.pilots = reinterpret_cast<const float2 *>(d_pilots);
-    f.B = B, f.S = S, f.coh = coh, f.nh = (S + coh - 1) / coh, f.plen = plen, f.dlen = dlen, f.J = J, f.T = (int)T;
-    f.cw0 = (uint64_t)cw0, f.seed = seed, f.sigma = (float)sigma, f.cfo_max = cfo_max;
-    f.frames = reinterpret_cast<float2 *>(d_frames), f.h_true = reinterpret_cast<float2 *>(d_h_true);
-    const dim3 grid((unsigned)(((long)B * T + BLOCK - 1) / BLOCK));
-    if (cfo_max > 0.0) hipLaunchKernelGGL(k_workload_frame<true>, grid, dim3(BLOCK), 0, (hipStream_t)stream, f);
-    else hipLaunchKernelGGL(k_workload_frame<false>, grid, dim3(BLOCK), 0, (hipStream_t)stream, f);
-    HIPCHK(hipGetLastError());
-    return 0;
-}
-
-// receive diversity (DESIGN.md §14)
-int tdec_workload_branches_dev(tdec_t *h, int B, int R, int64_t cw0, uint64_t seed, const float *cons_iq, int M, int bps,
-                               double sigma, double rician_k, int coh, float *d_syms, float *d_h, uint8_t *d_info,
-                               void *stream) {
-    if (!h || B < 0 || cw0 < 0 || R < 1 || R > 8) return fail(TDEC_EINVAL, "bad workload arguments (1 <= R <= 8)");
-    if (B == 0) return 0;
-    if (!cons_iq || !d_syms || !d_h || bps < 1 || bps > 8 || M != (1 << bps) || !(sigma >= 0.0) || coh < 1 ||
-        !(rician_k >= 0.0) || !(rician_k < INFINITY))
-        return fail(TDEC_EINVAL, "bad workload arguments (the constellation must have 2^bps points; K >= 0, coh >= 1)");
-    if (!staged_encoder_ok(h)) return fail(TDEC_EINVAL, "workload generation needs N % 4 == 0 and N <= 1024");
-    Guard g(h->device);
-    WorkloadArgs a = workload_args(h, B);
-    a.bps = bps;
-    a.M = M;
-    a.S = (int)((h->enc_len + bps - 1) / bps);
-    a.cw0 = (uint64_t)cw0;
-    a.seed = seed;
-    a.sigma = (float)sigma;
-    for (int m = 0; m < M; ++m) a.cons[m] = make_float2(cons_iq[2 * m], cons_iq[2 * m + 1]);
-    a.info_out = d_info;
-    a.syms = reinterpret_cast<float2 *>(d_syms);
-    BranchArgs f{};
-    f.h = reinterpret_cast<float2 *>(d_h);
-    f.coh = coh;
-    f.nh = (a.S + coh - 1) / coh;
-    f.los = (float)std::sqrt(rician_k / (rician_k + 1.0));
-    f.scat = (float)std::sqrt(1.0 / (rician_k + 1.0));
-    f.R = R;
-    hipLaunchKernelGGL(k_workload_faded<BranchArgs>, dim3((unsigned)n_tiles_of(B)), dim3(64), 0, (hipStream_t)stream, a, f);
-    HIPCHK(hipGetLastError());
-    return 0;
-}
-
-int tdec_workload_frame_branches_dev(int device, const float *d_y, const float *d_gains, int B, int R, int S, int coh,
-                                     int plen, int dlen, const float *d_pilots, double sigma, int64_t cw0, uint64_t seed,
-                                     double cfo_max, float *d_frames, float *d_h_true, void *stream) {
-    if (B < 0 || cw0 < 0 || R < 1 || R > 8) return fail(TDEC_EINVAL, "bad frame arguments (1 <= R <= 8)");
-    if (B == 0) return 0;
-    if (!d_y || !d_gains || !d_pilots || !d_frames || S < 1 || coh < 1 || plen < 1 || dlen < 1 || !(sigma >= 0.0) ||
-        !(cfo_max >= 0.0) || !(cfo_max < INFINITY))
-        return fail(TDEC_EINVAL, "bad frame arguments (S, coh, plen, dlen >= 1; sigma >= 0; finite cfo_max >= 0)");
-    const int J = (S + dlen - 1) / dlen;
-    const long T = (long)S + (long)(J + 1) * plen;
-    if (T > INT32_MAX || (long)B * R > INT32_MAX) return fail(TDEC_EINVAL, "bad frame arguments (frame or batch too long)");
+    if (T > INT32_MAX || (long)B * R > INT32_MAX)
+        return fail(TDEC_EINVAL, branches ? "bad frame arguments (frame or batch too long)"
+                                          : "bad frame arguments (frame too long)");
     Guard g(device);
     FrameArgs f{};
     f.y = reinterpret_cast<const float2 *>(d_y);
@@ -2147,35 +2095,58 @@ int tdec_workload_frame_branches_dev(int device, const float *d_y, const float *
     f.cw0 = (uint64_t)cw0, f.seed = seed, f.sigma = (float)sigma, f.cfo_max = cfo_max;
     f.frames = reinterpret_cast<float2 *>(d_frames), f.h_true = reinterpret_cast<float2 *>(d_h_true);
     const dim3 grid((unsigned)(((long)f.B * T + BLOCK - 1) / BLOCK));
-    if (cfo_max > 0.0) hipLaunchKernelGGL(k_workload_frame_branches<true>, grid, dim3(BLOCK), 0, (hipStream_t)stream, f, R);
-    else hipLaunchKernelGGL(k_workload_frame_branches<false>, grid, dim3(BLOCK), 0, (hipStream_t)stream, f, R);
+    const hipStream_t st = (hipStream_t)stream;
+    if (!branches && cfo_max > 0.0) hipLaunchKernelGGL(k_workload_frame<true>, grid, dim3(BLOCK), 0, st, f);
+    else if (!branches) hipLaunchKernelGGL(k_workload_frame<false>, grid, dim3(BLOCK), 0, st, f);
+    else if (cfo_max > 0.0) hipLaunchKernelGGL(k_workload_frame_branches<true>, grid, dim3(BLOCK), 0, st, f, R);
+    else hipLaunchKernelGGL(k_workload_frame_branches<false>, grid, dim3(BLOCK), 0, st, f, R);
     HIPCHK(hipGetLastError());
     return 0;
+}
+
+int tdec_workload_frame_dev(int device, const float *d_y, const float *d_gains, int B, int S, int coh, int plen,
+                            int dlen, const float *d_pilots, double sigma, int64_t cw0, uint64_t seed, double cfo_max,
+                            float *d_frames, float *d_h_true, void *stream) {
+    return frame_launch(device, d_y, d_gains, B, false, 1, S, coh, plen, dlen, d_pilots, sigma, cw0, seed, cfo_max,
+                        d_frames, d_h_true, stream);
+}
+
+// receive diversity (DESIGN.md §14)
+int tdec_workload_branches_dev(tdec_t *h, int B, int R, int64_t cw0, uint64_t seed, const float *cons_iq, int M, int bps,
+                               double sigma, double rician_k, int coh, float *d_syms, float *d_h, uint8_t *d_info,
+                               void *stream) {
+    if (!h || B < 0 || cw0 < 0 || R < 1 || R > 8) return fail(TDEC_EINVAL, "bad workload arguments (1 <= R <= 8)");
+    if (B == 0) return 0;
+    WorkloadArgs a;
+    BranchArgs f{};
+    if (!symbol_args(a, h, B, cw0, seed, cons_iq, M, bps, sigma, d_syms, d_info) || !fade_args(f, rician_k, coh, a.S, d_h))
+        return fail(TDEC_EINVAL, BAD_FADING);
+    f.R = R;
+    return workload_launch(h, B, k_workload_faded<BranchArgs>, stream, a, f);
+}
+
+int tdec_workload_frame_branches_dev(int device, const float *d_y, const float *d_gains, int B, int R, int S, int coh,
+                                     int plen, int dlen, const float *d_pilots, double sigma, int64_t cw0, uint64_t seed,
+                                     double cfo_max, float *d_frames, float *d_h_true, void *stream) {
+    return frame_launch(device, d_y, d_gains, B, true, R, S, coh, plen, dlen, d_pilots, sigma, cw0, seed, cfo_max,
+                        d_frames, d_h_true, stream);
 }
 
 int tdec_encode_dev(tdec_t *h, int B, const uint8_t *d_bits, uint8_t *d_coded, void *stream) {
     if (!h || B < 0) return fail(TDEC_EINVAL, "bad encode arguments");
     if (B == 0) return 0;
     if (!d_bits || !d_coded) return fail(TDEC_EINVAL, "bad encode arguments");
-    Guard g(h->device);
+    WorkloadArgs w = workload_args(h, B);
     if (staged_encoder_ok(h)) {   // coalesced LDS-staged encoder (tdec_workload.hip)
-        WorkloadArgs w = workload_args(h, B);
         w.bits_in = d_bits;
         w.coded_out = d_coded;
-        hipLaunchKernelGGL(k_workload, dim3((unsigned)n_tiles_of(B)), dim3(64), 0, (hipStream_t)stream, w);
-        HIPCHK(hipGetLastError());
-        return 0;
+        return workload_launch(h, B, k_workload, stream, w);
     }
+    Guard g(h->device);
     EncodeArgs a{};
-    a.B = B;
-    a.N = h->N;
-    a.period = h->period;
-    a.n_out = h->enc_len;
-    std::memcpy(a.punct, h->punct, 16);
-    std::memcpy(a.circ, h->circ, sizeof a.circ);
-    a.perm = h->d_perm;
-    a.bits = d_bits;
-    a.coded = d_coded;
+    a.B = B, a.N = w.N, a.period = w.period, a.n_out = w.n_out, a.perm = w.perm, a.bits = d_bits, a.coded = d_coded;
+    std::memcpy(a.punct, w.punct, 16);
+    std::memcpy(a.circ, w.circ, sizeof a.circ);
     hipLaunchKernelGGL(k_encode, dim3((B + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, (hipStream_t)stream, a);
     HIPCHK(hipGetLastError());
     return 0;

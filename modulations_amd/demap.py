@@ -172,6 +172,47 @@ def nv_tensor_form(syms, nv):
     return "rows"
 
 
+def _stream_of(dev, stream):
+    """The native handle of `stream`, or of the current stream of device index `dev`."""
+    import torch
+    return _n.stream_ptr(stream) if stream is not None else torch.cuda.current_stream(dev).cuda_stream
+
+
+def _out_tensor(t, like, shape, dtype, name):
+    """An output argument: a new tensor on the device of the input `like`, or the caller's, which must fit."""
+    import torch
+    if t is None:
+        return torch.empty(shape, dtype=dtype, device=like.device)
+    if (not isinstance(t, torch.Tensor) or t.dtype != dtype or tuple(t.shape) != tuple(shape) or not t.is_contiguous()
+            or t.device != like.device):
+        raise ValueError(f"{name} must be a contiguous {dtype} tensor of shape {tuple(shape)} on the input's device")
+    return t
+
+
+MAX_BRANCHES = 8
+
+
+def _syms_and_gains(syms, name, h, coh):
+    """What equalize_device ([B, S] `syms`) and combine_device ([B, R, S] `y`) ask of their inputs:
+    complex64 contiguous tensors on one HIP device, h with ceil(S / coh) gains per row.  -> int(coh)."""
+    import torch
+    for t, n in ((syms, name), (h, "h")):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.complex64:
+            raise TypeError(f"{n} must be a torch.complex64 tensor, got {getattr(t, 'dtype', type(t))}")
+    ndim, dims = (2, "2-D [B, S]") if name == "syms" else (3, "3-D [B, R, S]")
+    if syms.dim() != ndim or syms.device.type != "cuda" or not syms.is_contiguous():
+        raise ValueError(f"{name} must be a contiguous {dims} tensor on a HIP device")
+    if syms.dim() == 3 and not 1 <= syms.shape[1] <= MAX_BRANCHES:
+        raise ValueError(f"1 .. {MAX_BRANCHES} branches, got {syms.shape[1]}")
+    coh = int(coh)
+    if coh < 1:
+        raise ValueError("coh must be >= 1")
+    want = (*syms.shape[:-1], -(-syms.shape[-1] // coh))
+    if tuple(h.shape) != want or not h.is_contiguous() or h.device != syms.device:
+        raise ValueError(f"h must be a contiguous tensor of shape {want} on the symbols' device, got {tuple(h.shape)}")
+    return coh
+
+
 def equalize_device(syms, h, noise_var, coh=1, out=None, nv_out=None, stream=None):
     """Flat-fading equaliser: received complex64 [B, S] device
     symbols y = h x + n with known gains h, complex64 [B, ceil(S / coh)] (symbol s uses
@@ -180,39 +221,18 @@ def equalize_device(syms, h, noise_var, coh=1, out=None, nv_out=None, stream=Non
     stream-ordered, for compute_llr_device / demap_planes_device to read in place.
     |h|^2 zero or not finite marks an erasure: z = 0, nv_sym = +inf (zero LLRs)."""
     import torch
-    if not isinstance(syms, torch.Tensor) or syms.dtype != torch.complex64:
-        raise TypeError(f"syms must be a torch.complex64 tensor, got {getattr(syms, 'dtype', type(syms))}")
-    if not isinstance(h, torch.Tensor) or h.dtype != torch.complex64:
-        raise TypeError(f"h must be a torch.complex64 tensor, got {getattr(h, 'dtype', type(h))}")
-    if syms.dim() != 2 or syms.device.type != "cuda" or not syms.is_contiguous():
-        raise ValueError("syms must be a contiguous 2-D [B, S] tensor on a HIP device")
+    coh = _syms_and_gains(syms, "syms", h, coh)
     B, S = syms.shape
-    coh = int(coh)
-    if coh < 1:
-        raise ValueError("coh must be >= 1")
-    nh = -(-S // coh)
-    if tuple(h.shape) != (B, nh) or not h.is_contiguous() or h.device != syms.device:
-        raise ValueError(f"h must be a contiguous tensor of shape ({B}, {nh}) on the symbols' device, "
-                         f"got {tuple(h.shape)}")
     rows = isinstance(noise_var, torch.Tensor)
     if rows:
         _nv_check(syms, noise_var, "row")
-    if out is None:
-        out = torch.empty_like(syms)
-    elif out.dtype != torch.complex64 or tuple(out.shape) != (B, S) or not out.is_contiguous() or out.device != syms.device:
-        raise ValueError(f"out must be a contiguous complex64 tensor of shape ({B}, {S}) on the symbols' device")
-    if nv_out is None:
-        nv_out = torch.empty((B, S), dtype=torch.float64, device=syms.device)
-    else:
-        _nv_check(syms, nv_out, "symbol", "nv_out")
+    out = _out_tensor(out, syms, (B, S), torch.complex64, "out")
+    nv_out = _out_tensor(nv_out, syms, (B, S), torch.float64, "nv_out")
     dev = syms.device.index or 0
-    st = _n.stream_ptr(stream) if stream is not None else torch.cuda.current_stream(dev).cuda_stream
     _n.check(_n.lib().tdec_equalize_dev(dev, _n.ptr(syms), _n.ptr(h), B, S, coh, 0.0 if rows else float(noise_var),
-                                        _n.ptr(noise_var) if rows else None, _n.ptr(out), _n.ptr(nv_out), st))
+                                        _n.ptr(noise_var) if rows else None, _n.ptr(out), _n.ptr(nv_out),
+                                        _stream_of(dev, stream)))
     return out, nv_out
-
-
-MAX_BRANCHES = 8
 
 
 def combine_device(y, h, noise_var, coh=1, out=None, nv_out=None, stream=None):
@@ -227,22 +247,8 @@ def combine_device(y, h, noise_var, coh=1, out=None, nv_out=None, stream=None):
     zero or not finite is skipped; with none left the symbol is an erasure, z = 0 and
     nv_sym = +inf (zero LLRs).  R = 1 with a common noise_var is equalize_device bit for bit."""
     import torch
-    if not isinstance(y, torch.Tensor) or y.dtype != torch.complex64:
-        raise TypeError(f"y must be a torch.complex64 tensor, got {getattr(y, 'dtype', type(y))}")
-    if not isinstance(h, torch.Tensor) or h.dtype != torch.complex64:
-        raise TypeError(f"h must be a torch.complex64 tensor, got {getattr(h, 'dtype', type(h))}")
-    if y.dim() != 3 or y.device.type != "cuda" or not y.is_contiguous():
-        raise ValueError("y must be a contiguous 3-D [B, R, S] tensor on a HIP device")
+    coh = _syms_and_gains(y, "y", h, coh)
     B, R, S = y.shape
-    if not 1 <= R <= MAX_BRANCHES:
-        raise ValueError(f"1 .. {MAX_BRANCHES} branches, got {R}")
-    coh = int(coh)
-    if coh < 1:
-        raise ValueError("coh must be >= 1")
-    nh = -(-S // coh)
-    if tuple(h.shape) != (B, R, nh) or not h.is_contiguous() or h.device != y.device:
-        raise ValueError(f"h must be a contiguous tensor of shape ({B}, {R}, {nh}) on the symbols' device, "
-                         f"got {tuple(h.shape)}")
     rows = branches = None
     if isinstance(noise_var, torch.Tensor):
         if noise_var.dtype != torch.float64:
@@ -256,19 +262,13 @@ def combine_device(y, h, noise_var, coh=1, out=None, nv_out=None, stream=None):
             branches = noise_var
         else:
             rows = noise_var
-    if out is None:
-        out = torch.empty((B, S), dtype=torch.complex64, device=y.device)
-    elif out.dtype != torch.complex64 or tuple(out.shape) != (B, S) or not out.is_contiguous() or out.device != y.device:
-        raise ValueError(f"out must be a contiguous complex64 tensor of shape ({B}, {S}) on the symbols' device")
-    if nv_out is None:
-        nv_out = torch.empty((B, S), dtype=torch.float64, device=y.device)
-    else:
-        _nv_check(out, nv_out, "symbol", "nv_out")
+    out = _out_tensor(out, y, (B, S), torch.complex64, "out")
+    nv_out = _out_tensor(nv_out, y, (B, S), torch.float64, "nv_out")
     dev = y.device.index or 0
-    st = _n.stream_ptr(stream) if stream is not None else torch.cuda.current_stream(dev).cuda_stream
     _n.check(_n.lib().tdec_combine_dev(dev, _n.ptr(y), _n.ptr(h), B, R, S, coh,
                                        0.0 if isinstance(noise_var, torch.Tensor) else float(noise_var),
-                                       _n.ptr(rows), _n.ptr(branches), _n.ptr(out), _n.ptr(nv_out), st))
+                                       _n.ptr(rows), _n.ptr(branches), _n.ptr(out), _n.ptr(nv_out),
+                                       _stream_of(dev, stream)))
     return out, nv_out
 
 
@@ -294,7 +294,7 @@ def estimate_noise_var_device(syms, mod_type, floor=0.02, out=None, stream=None)
     f64 = cons.dtype == np.complex128
     c = np.ascontiguousarray(cons.astype(np.complex128 if f64 else np.complex64))
     dev = syms.device.index or 0
-    st = _n.stream_ptr(stream) if stream is not None else torch.cuda.current_stream(dev).cuda_stream
+    st = _stream_of(dev, stream)
     _n.check(_n.lib().tdec_noise_var_dev(dev, _n.ptr(syms), B, S, _n.ptr(c), int(f64), len(c), float(floor),
                                          _n.ptr(out), st))
     return out
@@ -329,7 +329,7 @@ def compute_llr_device(syms, mod_type, noise_var, out=None, sign=+1, stream=None
                           dtype=torch.float64, device=syms.device)
     if out.dtype != torch.float64 or not out.is_contiguous() or out.numel() < n_sym * m['bps'] or out.device != syms.device:
         raise ValueError("out must be a contiguous float64 tensor of n_sym*bps elements on the symbols' device")
-    st = _n.stream_ptr(stream) if stream is not None else torch.cuda.current_stream(dev).cuda_stream
+    st = _stream_of(dev, stream)
     # tdec_demap[_rows][_logmap]_dev, or tdec_symnv_demap[_logmap]_dev for a per-symbol tensor:
     # (B, S) and the tensor for rows / syms, else n_sym and the scalar; no div_f32 for log-MAP
     stem = "tdec_symnv_demap" if form == "syms" else f"tdec_demap{'_rows' if rows else ''}"
@@ -459,16 +459,6 @@ def _csi_device_check(frames):
         raise ValueError("frames must be a contiguous tensor on a HIP device")
 
 
-def _csi_out(t, frames, shape, dtype, name):
-    import torch
-    if t is None:
-        return torch.empty(shape, dtype=dtype, device=frames.device)
-    if (not isinstance(t, torch.Tensor) or t.dtype != dtype or tuple(t.shape) != tuple(shape) or not t.is_contiguous()
-            or t.device != frames.device):
-        raise ValueError(f"{name} must be a contiguous {dtype} tensor of shape {tuple(shape)} on the frames' device")
-    return t
-
-
 def estimate_csi_device(frames, layout, noise_var=None, mode="linear", floor=0.02, out=None, nv_out=None, h_out=None,
                         nv_rows_out=None, stream=None):
     """Pilot-aided channel estimation and equalisation in one launch:
@@ -495,14 +485,14 @@ def estimate_csi_device(frames, layout, noise_var=None, mode="linear", floor=0.0
     if rows and noise_var.device != frames.device:
         raise ValueError("noise_var must be on the frames' HIP device")
     pil = layout.pilots_device(S, frames.device)
-    out = _csi_out(out, frames, (B, S), torch.complex64, "out")
-    nv_out = _csi_out(nv_out, frames, (B, S), torch.float64, "nv_out")
+    out = _out_tensor(out, frames, (B, S), torch.complex64, "out")
+    nv_out = _out_tensor(nv_out, frames, (B, S), torch.float64, "nv_out")
     if h_out is not None:
-        h_out = _csi_out(h_out, frames, (B, S), torch.complex64, "h_out")
+        h_out = _out_tensor(h_out, frames, (B, S), torch.complex64, "h_out")
     if nv_rows_out is not None:
-        nv_rows_out = _csi_out(nv_rows_out, frames, (B,), torch.float64, "nv_rows_out")
+        nv_rows_out = _out_tensor(nv_rows_out, frames, (B,), torch.float64, "nv_rows_out")
     dev = frames.device.index or 0
-    st = _n.stream_ptr(stream) if stream is not None else torch.cuda.current_stream(dev).cuda_stream
+    st = _stream_of(dev, stream)
     _n.check(_n.lib().tdec_csi_pilots_dev(dev, _n.ptr(frames), B, S, layout.plen, layout.dlen, _n.ptr(pil),
                                           CSI_MODES[mode], -1.0 if rows or noise_var is None else float(noise_var),
                                           _n.ptr(noise_var) if rows else None, float(floor), _n.ptr(out),
@@ -518,12 +508,12 @@ def strip_pilots_device(frames, layout, mode="linear", floor=0.02, out=None, h_o
     B, S = _csi_frames_check(frames, layout, mode, need_residual=nv_rows_out is not None)
     _csi_device_check(frames)
     pil = layout.pilots_device(S, frames.device)
-    out = _csi_out(out, frames, (B, S), torch.complex64, "out")
-    h_out = _csi_out(h_out, frames, (B, S), torch.complex64, "h_out")
+    out = _out_tensor(out, frames, (B, S), torch.complex64, "out")
+    h_out = _out_tensor(h_out, frames, (B, S), torch.complex64, "h_out")
     if nv_rows_out is not None:
-        nv_rows_out = _csi_out(nv_rows_out, frames, (B,), torch.float64, "nv_rows_out")
+        nv_rows_out = _out_tensor(nv_rows_out, frames, (B,), torch.float64, "nv_rows_out")
     dev = frames.device.index or 0
-    st = _n.stream_ptr(stream) if stream is not None else torch.cuda.current_stream(dev).cuda_stream
+    st = _stream_of(dev, stream)
     _n.check(_n.lib().tdec_csi_strip_dev(dev, _n.ptr(frames), B, S, layout.plen, layout.dlen, _n.ptr(pil),
                                          CSI_MODES[mode], float(floor), _n.ptr(out), _n.ptr(h_out),
                                          _n.ptr(nv_rows_out), st))

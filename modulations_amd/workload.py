@@ -54,73 +54,50 @@ def make_symbols(codec, B, mod, ebn0_db, seed, device, cw0=0, want_info=True, fa
     S = -(-h.enc_len // bps)
     n0 = noise_n0(cons, rate, bps, ebn0_db)
     table = np.ascontiguousarray(cons.astype(np.complex64)).view(np.float32)
-    syms = torch.empty((B, S), dtype=torch.complex64, device=device)
     info = torch.empty((B, codec.k_info), dtype=torch.uint8, device=device) if want_info else None
     if pilots is not None and fading is None:
         raise ValueError("pilots frames a fading channel's symbols: pass fading={...} as well")
     if pilots is None and cfo:
         raise ValueError("cfo needs pilots=PilotLayout(...)")
-    if fading is not None:
-        unknown = set(fading) - {"K", "coh", "branches"}
-        if unknown:
-            raise ValueError(f"fading takes the keys 'K', 'coh' and 'branches', not {sorted(unknown)}")
-        k, coh = float(fading.get("K", 0.0)), int(fading.get("coh", 1))
-        if not (0.0 <= k < float("inf")) or coh < 1:
-            raise ValueError("fading needs a finite K >= 0 and coh >= 1")
-        R = fading.get("branches")
-        if R is not None:
-            R = int(R)
-            if not 1 <= R <= D.MAX_BRANCHES:
-                raise ValueError(f"fading: 1 .. {D.MAX_BRANCHES} branches, got {R}")
-            return _make_branches(codec, B, R, S, bps, cons, table, n0, k, coh, seed, device, cw0, info, pilots, cfo)
-        gains = torch.empty((B, -(-S // coh)), dtype=torch.complex64, device=device)
-        h.call("tdec_workload_fading_dev", int(B), int(cw0), int(seed) & 0xFFFFFFFFFFFFFFFF, _n.ptr(table), len(cons),
-               bps, float(np.sqrt(n0 / 2)), k, coh, _n.ptr(syms), _n.ptr(gains), _n.ptr(info), codec._stream(None))
-        if pilots is not None:
-            if not isinstance(pilots, D.PilotLayout):
-                raise TypeError(f"pilots must be a demap.PilotLayout, got {type(pilots)}")
-            if not (0.0 <= float(cfo) < float("inf")):
-                raise ValueError("cfo must be a finite value >= 0")
-            T = pilots.frame_len(S)
-            frames = torch.empty((B, T), dtype=torch.complex64, device=device)
-            h_true = torch.empty((B, T), dtype=torch.complex64, device=device)
-            if B:
-                _n.check(_n.lib().tdec_workload_frame_dev(
-                    h.device, _n.ptr(syms), _n.ptr(gains), int(B), S, coh, pilots.plen, pilots.dlen,
-                    _n.ptr(pilots.pilots_device(S, frames.device)), float(np.sqrt(n0 / 2)), int(cw0),
-                    int(seed) & 0xFFFFFFFFFFFFFFFF, float(cfo), _n.ptr(frames), _n.ptr(h_true), codec._stream(None)))
-            return info, frames, n0, h_true
-        return info, syms, n0, gains
-    h.call("tdec_workload_dev", int(B), int(cw0), int(seed) & 0xFFFFFFFFFFFFFFFF, _n.ptr(table), len(cons), bps,
-           float(np.sqrt(n0 / 2)), _n.ptr(syms), _n.ptr(info), codec._stream(None))
-    return info, syms, n0
-
-
-def _make_branches(codec, B, R, S, bps, cons, table, n0, k, coh, seed, device, cw0, info, pilots, cfo):
-    """make_symbols' fading={..., "branches": R} form: (info, symbols [B, R, S], N0, gains
-    [B, R, nh]), or with pilots (info, frames [B, R, T], N0, h_true [B, R, T])."""
-    import torch
-    from . import _native as _n
-    if pilots is not None and not isinstance(pilots, D.PilotLayout):
-        raise TypeError(f"pilots must be a demap.PilotLayout, got {type(pilots)}")
-    if not (0.0 <= float(cfo) < float("inf")):
-        raise ValueError("cfo must be a finite value >= 0")
-    seed = int(seed) & 0xFFFFFFFFFFFFFFFF
-    sigma = float(np.sqrt(n0 / 2))
-    syms = torch.empty((B, R, S), dtype=torch.complex64, device=device)
-    gains = torch.empty((B, R, -(-S // coh)), dtype=torch.complex64, device=device)
-    codec.handle.call("tdec_workload_branches_dev", int(B), R, int(cw0), seed, _n.ptr(table), len(cons), bps, sigma, k,
-                      coh, _n.ptr(syms), _n.ptr(gains), _n.ptr(info), codec._stream(None))
+    cw0, seed, sigma = int(cw0), int(seed) & 0xFFFFFFFFFFFFFFFF, float(np.sqrt(n0 / 2))
+    if fading is None:
+        syms = torch.empty((B, S), dtype=torch.complex64, device=device)
+        h.call("tdec_workload_dev", int(B), cw0, seed, _n.ptr(table), len(cons), bps, sigma, _n.ptr(syms),
+               _n.ptr(info), codec._stream(None))
+        return info, syms, n0
+    unknown = set(fading) - {"K", "coh", "branches"}
+    if unknown:
+        raise ValueError(f"fading takes the keys 'K', 'coh' and 'branches', not {sorted(unknown)}")
+    k, coh = float(fading.get("K", 0.0)), int(fading.get("coh", 1))
+    if not (0.0 <= k < float("inf")) or coh < 1:
+        raise ValueError("fading needs a finite K >= 0 and coh >= 1")
+    R = fading.get("branches")
+    if R is not None:
+        R = int(R)
+        if not 1 <= R <= D.MAX_BRANCHES:
+            raise ValueError(f"fading: 1 .. {D.MAX_BRANCHES} branches, got {R}")
+    if pilots is not None:
+        if not isinstance(pilots, D.PilotLayout):
+            raise TypeError(f"pilots must be a demap.PilotLayout, got {type(pilots)}")
+        if not (0.0 <= float(cfo) < float("inf")):
+            raise ValueError("cfo must be a finite value >= 0")
+    # R is None: 2-D results of the single-branch entry points; else [B, R, ...] of the branch ones (R behind B)
+    rows, fade, frame = (((B,), "tdec_workload_fading_dev", "tdec_workload_frame_dev") if R is None else
+                         ((B, R), "tdec_workload_branches_dev", "tdec_workload_frame_branches_dev"))
+    syms = torch.empty((*rows, S), dtype=torch.complex64, device=device)
+    gains = torch.empty((*rows, -(-S // coh)), dtype=torch.complex64, device=device)
+    h.call(fade, *map(int, rows), cw0, seed, _n.ptr(table), len(cons), bps, sigma, k, coh, _n.ptr(syms), _n.ptr(gains),
+           _n.ptr(info), codec._stream(None))
     if pilots is None:
         return info, syms, n0, gains
     T = pilots.frame_len(S)
-    frames = torch.empty((B, R, T), dtype=torch.complex64, device=device)
-    h_true = torch.empty((B, R, T), dtype=torch.complex64, device=device)
+    frames = torch.empty((*rows, T), dtype=torch.complex64, device=device)
+    h_true = torch.empty((*rows, T), dtype=torch.complex64, device=device)
     if B:
-        _n.check(_n.lib().tdec_workload_frame_branches_dev(
-            codec.handle.device, _n.ptr(syms), _n.ptr(gains), int(B), R, S, coh, pilots.plen, pilots.dlen,
-            _n.ptr(pilots.pilots_device(S, frames.device)), sigma, int(cw0), seed, float(cfo), _n.ptr(frames),
-            _n.ptr(h_true), codec._stream(None)))
+        _n.check(getattr(_n.lib(), frame)(
+            h.device, _n.ptr(syms), _n.ptr(gains), *map(int, rows), S, coh, pilots.plen, pilots.dlen,
+            _n.ptr(pilots.pilots_device(S, frames.device)), sigma, cw0, seed, float(cfo), _n.ptr(frames), _n.ptr(h_true),
+            codec._stream(None)))
     return info, frames, n0, h_true
 
 
@@ -196,6 +173,8 @@ class DevicePipeline:
         self.cons = D.constellation(mod)
         self.demap = demap
         lm = D.check_algo(demap)
+        # the division's dtype when the noise variance is a tensor: what a numpy float64 scalar gives
+        self.div_f32_t = D.demap_mode(np.complex64, self.cons.dtype, np.float64(1.0))[1]
         self.early_stop = bool(getattr(codec, "early_stop", False))
         self.fused_asked = bool(fused)
         self.fused = (bool(fused) and not lm and not self.early_stop
@@ -265,10 +244,10 @@ class DevicePipeline:
                                  f"{self.z.shape[1]}], got {tuple(syms.shape)}")
         front = None
         if csi is not None and syms.dim() == 3:
-            front = lambda st: self._combine(syms, csi, noise_var, coh, st)  # noqa: E731
+            front = lambda st: self._front(D.combine_device, syms, csi, noise_var, coh, st)  # noqa: E731
             return self._run(syms, 1.0, stream, events, syms_ready, front)
         if csi is not None:
-            front = lambda st: self._equalize(syms, csi, noise_var, coh, st)  # noqa: E731
+            front = lambda st: self._front(D.equalize_device, syms, csi, noise_var, coh, st)  # noqa: E731
         return self._run(syms, noise_var, stream, events, syms_ready, front)
 
     def run_frames(self, frames, layout, noise_var=None, mode="linear", stream=None, events=None):
@@ -297,7 +276,7 @@ class DevicePipeline:
         def front(st):
             z, nvs = D.estimate_csi_device(frames, layout, noise_var, mode=mode, out=self.z[:n],
                                            nv_out=self.nv_sym[:n], stream=st)
-            return z, nvs, D.demap_mode(np.complex64, self.cons.dtype, np.float64(1.0))[1]
+            return z, nvs, self.div_f32_t
         return self._run(frames, 1.0, stream, events, None, front)
 
     def _run_branch_frames(self, frames, layout, noise_var, mode, stream, events):
@@ -321,9 +300,8 @@ class DevicePipeline:
         def front(st):
             D.strip_pilots_device(frames.view(n * R, T), layout, mode=mode, out=y, h_out=h,
                                   nv_rows_out=nvb if estimate else None, stream=st)
-            z, nvs = D.combine_device(y.view(n, R, S), h.view(n, R, S), nvb.view(n, R) if estimate else noise_var,
-                                      coh=1, out=self.z[:n], nv_out=self.nv_sym[:n], stream=st)
-            return z, nvs, D.demap_mode(np.complex64, self.cons.dtype, np.float64(1.0))[1]
+            return self._front(D.combine_device, y.view(n, R, S), h.view(n, R, S),
+                               nvb.view(n, R) if estimate else noise_var, 1, st)
         return self._run(frames, 1.0, stream, events, None, front)
 
     def _run(self, syms, noise_var, stream, events, syms_ready, front):
@@ -334,8 +312,7 @@ class DevicePipeline:
             if self.fused_asked:
                 raise ValueError("a per-row noise_var tensor needs the two-launch pipeline: the fused "
                                  "demap+decode kernel has no per-row form (fused=True)")
-            _, div32, _ = D.demap_mode(np.complex64, self.cons.dtype, np.float64(1.0))
-            nve = noise_var
+            div32, nve = self.div_f32_t, noise_var
         else:
             _, div32, nve = D.demap_mode(np.complex64, self.cons.dtype, np.float64(noise_var))
         bits = self.bits[:syms.shape[0]]          # the first rows: a contiguous view
@@ -384,16 +361,11 @@ class DevicePipeline:
             events[1].record(stream)
         return bits
 
-    def _equalize(self, syms, csi, nv, coh, stream):
-        """(z, nv_sym, div_f32) for the demapper: `syms` equalised by `csi` into this
-        pipeline's buffers on `stream` (nv unfloored: the demapper floors nv / |h|^2); the
-        division's dtype is the tensor forms'."""
+    def _front(self, fn, syms, csi, nv, coh, stream):
+        """(z, nv_sym, div_f32) for the demapper: `syms` equalised by `csi` (fn = demap.equalize_device)
+        or its [B, R, S] receive branches combined (demap.combine_device) into this pipeline's buffers
+        on `stream` (nv unfloored: the demapper floors nv / |h|^2); the division's dtype is the
+        tensor forms'."""
         n = syms.shape[0]
-        z, nvs = D.equalize_device(syms, csi, nv, coh=coh, out=self.z[:n], nv_out=self.nv_sym[:n], stream=stream)
-        return z, nvs, D.demap_mode(np.complex64, self.cons.dtype, np.float64(1.0))[1]
-
-    def _combine(self, syms, csi, nv, coh, stream):
-        """_equalize for [B, R, S] receive branches: the maximal-ratio combiner."""
-        n = syms.shape[0]
-        z, nvs = D.combine_device(syms, csi, nv, coh=coh, out=self.z[:n], nv_out=self.nv_sym[:n], stream=stream)
-        return z, nvs, D.demap_mode(np.complex64, self.cons.dtype, np.float64(1.0))[1]
+        z, nvs = fn(syms, csi, nv, coh=coh, out=self.z[:n], nv_out=self.nv_sym[:n], stream=stream)
+        return z, nvs, self.div_f32_t

@@ -17,6 +17,7 @@ pytestmark = pytest.mark.gpu
 
 import early_stop_ref as ES  # noqa: E402
 import fading_ref as F  # noqa: E402
+import generator_abi as GA  # noqa: E402
 from oracle import oracle as O  # noqa: E402
 from oracle import workload_ref as WR  # noqa: E402
 from modulations_amd import _native as N  # noqa: E402
@@ -420,3 +421,9 @@ def test_new_calls_refuse_bad_arguments_and_accept_empty_batches():
     assert bool(torch.isnan(z.real).all()) and bool(torch.isnan(y.real).all())
     with pytest.raises(ValueError):
         W.make_symbols(c, B, "16QAM", 2.0, 1, "cuda", fading={"K": 0.0, "coh": 1, "doppler": 3})
+
+
+# ---- ABI argument errors of the fading generator (tests/generator_abi.py) ----
+@pytest.mark.parametrize("call,case", GA.params("tdec_workload_fading_dev"))
+def test_generator_abi_refusals(call, case):
+    GA.check(call, case)

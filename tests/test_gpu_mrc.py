@@ -15,6 +15,7 @@ pytestmark = pytest.mark.gpu
 
 import early_stop_ref as ES  # noqa: E402
 import fading_ref as F  # noqa: E402
+import generator_abi as GA  # noqa: E402
 import mrc_ref as MR  # noqa: E402
 import pilot_csi_ref as P  # noqa: E402
 from oracle import oracle as O  # noqa: E402
@@ -481,3 +482,65 @@ def test_abi_refusals_write_nothing():
     for bad in ({"K": 0.0, "coh": 1, "branches": 0}, {"K": 0.0, "coh": 1, "branches": 9}, {"K": 0.0, "branches": 2, "x": 1}):
         with pytest.raises(ValueError):
             W.make_symbols(c, B, "16QAM", 2.0, 1, "cuda", fading=bad)
+
+
+# ---- ABI argument errors of the branch generators (tests/generator_abi.py) ----
+@pytest.mark.parametrize("call,case", GA.params("tdec_workload_branches_dev", "tdec_workload_frame_branches_dev"))
+def test_generator_abi_refusals(call, case):
+    GA.check(call, case)
+
+
+# ---- the generators on a ragged shape -------------------------------------------------------------
+@pytest.mark.parametrize("cfo", [0.0, 1e-3])
+def test_generators_on_a_ragged_shape(cfo):
+    """65 codewords (two tiles, the second ragged) of N = 64 r = 1/2 on 8PSK: 256 coded bits in
+    S = 86 symbols, the last one padded (every rate of N = 48 gives a multiple of 3 bits, so the
+    next block size stands in); coh = 7 does not divide S; R = 3; plen = 2, dlen = 5.
+    One launch of each generator.  Branch 0 is the single-branch calls' output and the frames
+    hold the symbols and gains, all bit for bit; the gains are their restatements' to the 2e-5
+    of the float32 Box-Muller (as above); the rotation is within one ulp of its restatement;
+    and the equaliser, combiner and estimator on these arrays are IEEE == their restatements."""
+    c, lay = _codec(64, "1/2"), D.PilotLayout(2, 5)
+    B, R, coh, K, mod, seed, cw0 = 65, 3, 7, 2.0, "8PSK", 99, 11
+    S, one = -(-c.n_coded // 3), {"K": K, "coh": coh}
+    nh = -(-S // coh)
+    assert c.n_coded % 3 and S % coh and S % lay.dlen
+    gen = lambda f, **kw: W.make_symbols(c, B, mod, 6.0, seed, "cuda", cw0=cw0, fading=f, **kw)  # noqa: E731
+    info, syms, n0, h = gen({**one, "branches": R})
+    info1, syms1, _, h1 = gen(one)
+    _, frames, _, ht = gen({**one, "branches": R}, pilots=lay, cfo=cfo)
+    _, frames1, _, ht1 = gen(one, pilots=lay, cfo=cfo)
+    T_ = lay.frame_len(S)
+    assert tuple(syms.shape) == (B, R, S) and tuple(h.shape) == (B, R, nh) and tuple(frames.shape) == (B, R, T_) == tuple(ht.shape)
+    assert torch.equal(info, info1) and torch.equal(syms[:, 0], syms1) and torch.equal(h[:, 0], h1)
+    assert torch.equal(frames[:, 0], frames1) and torch.equal(ht[:, 0], ht1)
+    assert torch.equal(info, W.info_bits(c, B, seed, "cuda", cw0=cw0))
+    g, y = h.cpu().numpy(), syms.cpu().numpy()
+    for got, ref in ((g, MR.gains(np.arange(cw0, cw0 + B), R, nh, seed, K)), (g[:, 0], F.gains(np.arange(cw0, cw0 + B), nh, seed, K))):
+        print("max |gain - restatement|", np.max(np.abs(got - ref)))
+        assert np.max(np.abs(got - ref)) < 2e-5
+    dpos, ppos = P.data_positions(S, 2, 5), lay.pilot_positions(S)
+    blk = g[:, :, np.minimum(np.arange(lay.n_blocks(S)) * 5, S - 1) // coh]               # [B, R, J + 1]
+    if cfo == 0.0:
+        f, t = frames.cpu().numpy(), ht.cpu().numpy()
+        assert _eq(f[:, :, dpos], y) and _eq(t[:, :, dpos], g[:, :, np.arange(S) // coh])
+        assert _eq(t[:, :, ppos], np.repeat(blk, 2, axis=2))
+    else:
+        _, f0, _, t0 = gen({**one, "branches": R}, pilots=lay)
+        fg = np.repeat(P.cfo_of(np.arange(cw0, cw0 + B), seed, cfo), R)
+        for got, base in ((frames, f0), (ht, t0)):
+            ref = P.rotate(base.cpu().numpy().reshape(B * R, T_), fg).view(np.float32)
+            d = got.cpu().numpy().reshape(B * R, T_).view(np.float32)
+            worst = np.max(np.abs(d.astype(np.float64) - ref) / np.spacing(np.maximum(np.abs(ref), np.abs(d))))
+            print("max |device - restatement| in ulp", worst)
+            assert worst <= 1.0
+    # the receivers' front ends on these arrays
+    z, nvs = D.combine_device(syms, h, n0, coh=coh)
+    rz, rnv = MR.combine(y, g, n0, coh)
+    assert _eq(z.cpu().numpy(), rz) and _eq(nvs.cpu().numpy(), rnv)
+    z, nvs = D.equalize_device(syms1, h1, n0, coh=coh)
+    rz, rnv = F.equalize(y[:, 0], g[:, 0], n0, coh)
+    assert _eq(z.cpu().numpy(), rz) and _eq(nvs.cpu().numpy(), rnv)
+    z, nvs = D.estimate_csi_device(frames1, lay, n0)
+    want = P.estimate(frames1.cpu().numpy(), lay.pilots(S), S, 2, 5, "linear", n0)
+    assert _eq(z.cpu().numpy(), want["z"]) and _eq(nvs.cpu().numpy(), want["nv_sym"])

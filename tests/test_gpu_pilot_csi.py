@@ -10,6 +10,7 @@ pytestmark = pytest.mark.gpu
 
 import early_stop_ref as ES  # noqa: E402
 import fading_ref as F  # noqa: E402
+import generator_abi as GA  # noqa: E402
 import pilot_csi_ref as P  # noqa: E402
 from oracle import oracle as O  # noqa: E402
 from modulations_amd import _native as N  # noqa: E402
@@ -405,3 +406,9 @@ def test_abi_refusals_write_nothing():
     assert call() == 0 and call(nv=-1.0, nvi=p(nvi)) == 0
     torch.cuda.synchronize()
     assert not bool(torch.isnan(z.real).any()) and not bool(torch.isnan(nvo).any())
+
+
+# ---- ABI argument errors of the framing generator (tests/generator_abi.py) ----
+@pytest.mark.parametrize("call,case", GA.params("tdec_workload_frame_dev"))
+def test_generator_abi_refusals(call, case):
+    GA.check(call, case)

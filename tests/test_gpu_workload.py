@@ -25,6 +25,8 @@ pytestmark = pytest.mark.gpu
 
 from oracle import oracle as O  # noqa: E402
 from oracle import workload_ref as W  # noqa: E402
+import generator_abi as GA  # noqa: E402
+from modulations_amd import _native as N  # noqa: E402
 from modulations_amd import demap as D  # noqa: E402
 from modulations_amd import dvb_rcs2_turbo as M  # noqa: E402
 from modulations_amd import tables as T  # noqa: E402
@@ -179,3 +181,21 @@ def test_overlapped_pipeline_gives_the_serial_bits():
     torch.cuda.synchronize()
     for w, g in zip(want, got):
         assert torch.equal(w, g)
+
+
+# ---- ABI argument errors of the AWGN generator, the info bits and the encoder (tests/generator_abi.py) ----
+@pytest.mark.parametrize("call,case", GA.params("tdec_workload_dev", "tdec_info_bits_dev", "tdec_encode_dev"))
+def test_generator_abi_refusals(call, case):
+    GA.check(call, case)
+
+
+def test_row_encoder_serves_a_block_size_that_is_no_multiple_of_four():
+    """N = 50 has no staged encoder: tdec_encode_dev runs the row kernel, against the oracle."""
+    e = GA._env()
+    n, punct, perm = 50, T.PUNCTURE_PATTERNS["1/3"], ((7 * np.arange(50) + 3) % 50).astype(np.int32)
+    bits = np.random.default_rng(50).integers(0, 2, (5, 2 * n)).astype(np.uint8)
+    coded = torch.zeros((5, e["odd"].enc_len), dtype=torch.uint8, device="cuda")
+    e["odd"].call("tdec_encode_dev", 5, N.ptr(torch.from_numpy(bits).cuda()), N.ptr(coded), None)
+    t, G = O.trellis()
+    want = np.stack([O.encode(b, n, punct["period"], T.puncture_matrix(punct), perm, t, G) for b in bits])
+    assert np.array_equal(coded.cpu().numpy(), want)
