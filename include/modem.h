@@ -63,7 +63,9 @@ int mdm_map(int device, const uint8_t *bits, long n_bits, int bps, const void *t
 /* Hard demodulation of n_sym symbols (f32 or f64 pairs) into n_sym*bps bit
  * bytes (MSB first).  labels (host, nullable = identity): constellation index
  * -> label, 2^bps entries (PSK8: the inverse Gray map; QAM_AXIS: per-axis
- * inverse Gray map of 2^(bps/2) entries).  scale: QAM_AXIS multiplier
+ * inverse Gray map of 2^(bps/2) entries).  bps: 1 (GT0), 2 (QPSK), 3 (PSK8),
+ * an even 2..8 (QAM_AXIS: up to 256QAM, the mappers' M <= 256; anything larger
+ * is MDM_EINVAL) or 1..6 (ARGMIN).  scale: QAM_AXIS multiplier
  * (np.sqrt(10/42/170)).  cons (host f64 pairs, M = 2^bps <= 64): ARGMIN table.
  * nan_raises: 1 = a NaN symbol is an error (the reference's int(NaN) in its
  * per-symbol loops: MDM_ENAN from the host entry point, counted into

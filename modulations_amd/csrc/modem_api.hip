@@ -152,9 +152,9 @@ static int demod_args(int kind, int bps, const int32_t *labels, double scale, co
         want = 8;
         break;
     case MDM_DEMOD_QAM_AXIS:
-        if (bps < 2 || bps > 16 || bps % 2) return fail(MDM_EINVAL, "QAM demod needs an even bps");
+        // 2..8: the kernel builds a symbol's bits in eight bytes (256QAM, the mappers' M <= 256)
+        if (bps < 2 || bps > 8 || bps % 2) return fail(MDM_EINVAL, "QAM demod needs an even bps of 2..8");
         a.levels = 1 << (bps / 2);
-        if (a.levels > 256) return fail(MDM_EINVAL, "too many QAM levels");
         want = a.levels;
         break;
     case MDM_DEMOD_ARGMIN:
