@@ -239,9 +239,10 @@ def mix(sig, w, fs, dc=None, i0=0, device=0):
     """(sig - dc) * exp(1j * w * (i0 + arange(n)) / fs), complex128 (mdm_mix, _correct_freq)."""
     s = _syms_c(sig)
     out = np.empty(s.size, np.complex128)
+    dcv = _dc(dc)              # held here: the library reads it during the call
     if s.size:
         _n.modem_check(_n.modem_lib().mdm_mix(device, _n.ptr(s), int(s.dtype == np.complex128), s.size,
-                                              int(i0), _n.ptr(_dc(dc)), float(w), float(fs), _n.ptr(out)))
+                                              int(i0), _n.ptr(dcv), float(w), float(fs), _n.ptr(out)))
     return out
 
 
@@ -252,8 +253,9 @@ def burst_find(sig, preamble_len, win=1000, dc=None, want_smooth=False, device=0
     _check_burst(s.size, win, preamble_len)
     start, mx = np.zeros(1, np.int64), np.zeros(1, np.float64)
     smooth = np.empty(s.size, np.float64) if want_smooth else None
+    dcv = _dc(dc)
     _n.modem_check(_n.modem_lib().mdm_burst_find(device, _n.ptr(s), int(s.dtype == np.complex128), s.size,
-                                                 _n.ptr(_dc(dc)), int(win), int(preamble_len), _n.ptr(start),
+                                                 _n.ptr(dcv), int(win), int(preamble_len), _n.ptr(start),
                                                  _n.ptr(mx), _n.ptr(smooth)))
     return int(start[0]), float(mx[0]), smooth
 
@@ -290,8 +292,9 @@ def mix_device(sig, w, fs, dc=None, i0=0, out=None, stream=None):
     import torch
     if out is None:
         out = torch.empty(sig.numel(), dtype=torch.complex128, device=sig.device)
+    dcv = _dc(dc)
     _n.modem_check(_n.modem_lib().mdm_mix_dev(sig.device.index or 0, _n.ptr(sig), int(sig.dtype == torch.complex128),
-                                              sig.numel(), int(i0), _n.ptr(_dc(dc)), float(w), float(fs),
+                                              sig.numel(), int(i0), _n.ptr(dcv), float(w), float(fs),
                                               _n.ptr(out), _n.stream_ptr(stream)))
     return out
 
@@ -310,8 +313,9 @@ def burst_find_device(sig, preamble_len, win=1000, dc=None, smooth=None, result=
     if result is None:
         result = torch.empty(2, dtype=torch.int64, device=sig.device)
     scratch = _rx_scratch(sig.numel(), scratch, sig.device)
+    dcv = _dc(dc)
     _n.modem_check(_n.modem_lib().mdm_burst_find_dev(sig.device.index or 0, _n.ptr(sig),
-                                                     int(sig.dtype == torch.complex128), sig.numel(), _n.ptr(_dc(dc)),
+                                                     int(sig.dtype == torch.complex128), sig.numel(), _n.ptr(dcv),
                                                      int(win), int(preamble_len), _n.ptr(smooth), _n.ptr(result),
                                                      _n.ptr(scratch), _n.stream_ptr(stream)))
     return result
