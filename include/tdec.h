@@ -443,7 +443,9 @@ long tdec_encode_host(int n_couples, int period, const uint8_t *punct, const int
 /* info bits -> encode (as tdec_encode_dev) -> label-ordered constellation
  * (cons_iq: M = 2^bps host (re, im) float pairs, label = bps coded bits MSB
  * first, the last symbol zero-padded; any other M is TDEC_EINVAL) -> complex AWGN of std-dev sigma per dimension
- * (Box-Muller on philox4x32_10({g_lo, g_hi, s/2, 0x2B0E}, seed)).  d_syms:
+ * (Box-Muller on philox4x32_10({g_lo, g_hi, s/2, 0x2B0E}, seed), words x, y for even s and
+ * z, w for odd s; each uniform is ((x >> 8) + 0.5) 2^-24 in (0, 1], formed in float32, so the
+ * largest draw is exactly 1: radius 0, or angle 2 pi).  d_syms:
  * complex64 [B][ceil(n_out / bps)]; d_info (nullable): uint8 [B][2N]. */
 int tdec_workload_dev(tdec_t *h, int B, int64_t cw0, uint64_t seed, const float *cons_iq, int M, int bps,
                       double sigma, float *d_syms, uint8_t *d_info, void *stream);

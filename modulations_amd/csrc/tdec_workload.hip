@@ -16,7 +16,8 @@
 // b in the upper 16 bits of the domain word (0x2B0E | b << 16, ...): branch 0 is the
 // streams above; the info bits and the rotation are the codeword's, shared by its branches.
 // Info bit j of a codeword is bit j % 32 of word (j % 128) / 32 of block j / 128.
-// Noise: Box-Muller, u = (x >> 8 + 0.5) * 2^-24 in (0, 1): one complex sample
+// Noise: Box-Muller, u = (x >> 8 + 0.5) * 2^-24 in (0, 1], formed in float32
+// (x >> 8 = 2^24 - 1 rounds to u = 1: radius 0, or angle 2 pi): one complex sample
 // per symbol from two words, r = sigma * sqrt(-2 ln u1), theta = 2 pi u2.
 //
 // Layout (MI355X-first): one wave owns a tile of 64 codewords.  The tile's info

@@ -5,15 +5,14 @@
 TEST INFRASTRUCTURE.  The equaliser is build-defined and stated so that this float64
 restatement matches it bit for bit: the products of float32 values are exact in
 float64, so every sum, quotient and the final cast to float32 rounds once, on the
-device as here.  The gain draw is the device's Box-Muller in float64 (the device
-works in float32), as oracle/workload_ref.py restates the noise.
+device as here.  The gain draw is the device's Box-Muller in float64 of the device's
+float32 uniforms (the device goes on in float32), as oracle/workload_ref.py restates the noise.
 """
 import numpy as np
 
-from oracle.workload_ref import philox4x32_10
+from oracle.workload_ref import box_muller, stream_words
 
 FADE_DOMAIN = 0x3C5D
-_M = np.uint64(0xFFFFFFFF)
 
 
 def equalize(y, h, nv, coh=1):
@@ -39,21 +38,21 @@ def equalize(y, h, nv, coh=1):
     return z, np.where(erased, np.inf, nvs)
 
 
-def gains(cw_global, n_blocks, seed, K=0.0):
+def los_scat(K):
+    """(los, scat) = (sqrt(K / (K + 1)), sqrt(1 / (K + 1))) rounded to float32, as the device
+    holds them, returned as float64."""
+    K = np.float64(K)
+    return np.float64(np.float32(np.sqrt(K / (K + 1.0)))), np.float64(np.float32(np.sqrt(1.0 / (K + 1.0))))
+
+
+def gains(cw_global, n_blocks, seed, K=0.0, branch=0):
     """complex128 [len(cw_global), n_blocks]: h = sqrt(K / (K + 1)) + sqrt(1 / (K + 1)) w,
-    w ~ CN(0, 1) by Box-Muller on philox4x32_10({g_lo, g_hi, j / 2, FADE_DOMAIN}, seed)
-    for gain block j of global codeword g, the noise stream's uniform mapping."""
-    cw = np.asarray(cw_global, np.uint64)[:, None]
-    j = np.arange(n_blocks, dtype=np.uint64)[None, :]
-    r = philox4x32_10(cw & _M, cw >> np.uint64(32), j >> np.uint64(1), FADE_DOMAIN, seed & 0xFFFFFFFF, seed >> 32)
-    odd = (j & np.uint64(1)).astype(bool)
-    a = np.where(odd, r[2], r[0])
-    b = np.where(odd, r[3], r[1])
-    u1 = ((a >> 8).astype(np.float64) + 0.5) * 2.0 ** -24
-    u2 = ((b >> 8).astype(np.float64) + 0.5) * 2.0 ** -24
-    rad = np.sqrt(0.5) * np.sqrt(-2.0 * np.log(u1))
-    w = rad * np.cos(2 * np.pi * u2) + 1j * rad * np.sin(2 * np.pi * u2)
-    return np.sqrt(K / (K + 1.0)) + np.sqrt(1.0 / (K + 1.0)) * w
+    w ~ CN(0, 1) by Box-Muller on philox4x32_10({g_lo, g_hi, j / 2, FADE_DOMAIN | branch << 16},
+    seed) for gain block j of global codeword g (words x, y for even j, z, w for odd j), the
+    noise stream's uniform mapping: oracle.workload_ref.box_muller with sigma = sqrt(1/2)."""
+    w = box_muller(*stream_words(cw_global, n_blocks, seed, FADE_DOMAIN | (branch << 16)), np.sqrt(0.5))
+    los, scat = los_scat(K)
+    return los + scat * w
 
 
 def demap_per_symbol(z, cons, bps, nv_sym, div_f32):

@@ -1,12 +1,14 @@
 """Argument refusals of the workload generators' C ABI (include/tdec.h): the cases of
 tdec_workload_dev, tdec_info_bits_dev, tdec_encode_dev, tdec_workload_fading_dev,
-tdec_workload_branches_dev, tdec_workload_frame_dev and tdec_workload_frame_branches_dev, as
+tdec_workload_branches_dev, tdec_workload_frame_dev, tdec_workload_frame_branches_dev and
+tdec_count_errors_dev, as
 (return code, substring of tdec_last_error()) per bad argument, for the GPU test file that owns
 each call.  Every case is refused (or is an empty batch) before anything is launched.
 
 The order of the checks is part of what is pinned: a bad handle, B or cw0 (and, in the branch
 calls, R) is refused even when B == 0; B == 0 returns 0 whatever the pointers; the N % 4
-refusal comes after every other one."""
+refusal comes after every other one, and N = 1028 (a multiple of 4 the staged encoder does not hold)
+is refused in the same place."""
 import numpy as np
 
 from modulations_amd import _native as N
@@ -20,16 +22,19 @@ _KEEP = {}
 
 
 def _env():
-    """Handles (N = 48, and N = 50: no multiple of 4) and device buffers, made once."""
+    """Handles (N = 48, N = 50: no multiple of 4, and N = 1028: above the staged encoder's 1024) and
+    device buffers, made once."""
     import torch
     if not _KEEP:
         c = M.DVBRCS2_Turbo(48, "1/3")
         perm = ((7 * np.arange(50) + 3) % 50).astype(np.int32)
-        odd = M._Handle(0, 50, T.PUNCTURE_PATTERNS["1/3"], 8, 0, perm, np.argsort(perm).astype(np.int32),
-                        T.packed_tables(c.next_state, c.out_W, c.out_Y, c.prev_state, c.prev_input))
+        tables = T.packed_tables(c.next_state, c.out_W, c.out_Y, c.prev_state, c.prev_input)
+        odd = M._Handle(0, 50, T.PUNCTURE_PATTERNS["1/3"], 8, 0, perm, np.argsort(perm).astype(np.int32), tables)
+        pbig = ((7 * np.arange(1028) + 3) % 1028).astype(np.int32)
+        big = M._Handle(0, 1028, T.PUNCTURE_PATTERNS["1/3"], 8, 0, pbig, np.argsort(pbig).astype(np.int32), tables)
         tab = np.ascontiguousarray(D.constellation("16QAM").astype(np.complex64)).view(np.float32)
         buf = torch.full((B * R * 1024,), np.nan, dtype=torch.complex64, device="cuda")   # any output fits
-        _KEEP.update(c=c, h=c.handle.h, odd=odd, tab=tab, buf=buf, p=N.ptr(buf), t=N.ptr(tab))
+        _KEEP.update(c=c, h=c.handle.h, odd=odd, big=big, tab=tab, buf=buf, p=N.ptr(buf), t=N.ptr(tab))
     return _KEEP
 
 
@@ -44,6 +49,7 @@ def _good(name):
         "tdec_workload_branches_dev": [h, B, R, 0, 1, t, 16, 4, 0.1, 0.0, 1, p, p, p, None],
         "tdec_workload_frame_dev": [0, p, p, B, S, 1, 2, 7, p, 0.1, 0, 1, 0.0, p, None, None],
         "tdec_workload_frame_branches_dev": [0, p, p, B, R, S, 1, 2, 7, p, 0.1, 0, 1, 0.0, p, None, None],
+        "tdec_count_errors_dev": [h, B, 0, 1, p, p, None],
     }[name]
 
 
@@ -57,6 +63,7 @@ def _symbol_cases(o, head, body):
         "bps 0": ({6 + o: 0}, EINVAL, body), "bps 9": ({5 + o: 512, 6 + o: 9}, EINVAL, body),
         "sigma < 0": ({7 + o: -0.1}, EINVAL, body), "sigma NaN": ({7 + o: np.nan}, EINVAL, body),
         "N % 4": ({0: "odd"}, EINVAL, "N % 4 == 0"), "N % 4 comes last": ({0: "odd", 4 + o: None}, EINVAL, body),
+        "N = 1028": ({0: "big"}, EINVAL, "N <= 1024"), "N = 1028 comes last": ({0: "big", 4 + o: None}, EINVAL, body),
     }
 
 
@@ -96,7 +103,8 @@ CASES = {
         "null handle": ({0: None}, EINVAL, "bad info-bits"), "B < 0": ({1: -1}, EINVAL, "bad info-bits"),
         "cw0 < 0": ({2: -1}, EINVAL, "bad info-bits"), "cw0 < 0, B == 0": ({1: 0, 2: -1}, EINVAL, "bad info-bits"),
         "B == 0, null pointer": ({1: 0, 4: None}, 0, ""), "null bits": ({4: None}, EINVAL, "bad info-bits"),
-        "N % 4": ({0: "odd"}, EINVAL, "N % 4 == 0"), "N % 4 comes last": ({0: "odd", 4: None}, EINVAL, "bad info-bits")},
+        "N % 4": ({0: "odd"}, EINVAL, "N % 4 == 0"), "N % 4 comes last": ({0: "odd", 4: None}, EINVAL, "bad info-bits"),
+        "N = 1028": ({0: "big"}, EINVAL, "N <= 1024"), "N = 1028 comes last": ({0: "big", 4: None}, EINVAL, "bad info-bits")},
     "tdec_encode_dev": {
         "null handle": ({0: None}, EINVAL, "bad encode"), "B < 0": ({1: -1}, EINVAL, "bad encode"),
         "null handle, B == 0": ({0: None, 1: 0}, EINVAL, "bad encode"),
@@ -109,6 +117,12 @@ CASES = {
     "tdec_workload_frame_branches_dev": _frame_cases(1, _RF, "(frame or batch too long)") | {
         "R 0": ({4: 0}, EINVAL, _RF), "R 9": ({4: 9}, EINVAL, _RF), "R 9, B == 0": ({3: 0, 4: 9}, EINVAL, _RF),
         "B R > INT32_MAX": ({3: 1 << 30, 4: 4}, EINVAL, "(frame or batch too long)")},
+    "tdec_count_errors_dev": {
+        "null handle": ({0: None}, EINVAL, "bad count-errors"), "B < 0": ({1: -1}, EINVAL, "bad count-errors"),
+        "cw0 < 0": ({2: -1}, EINVAL, "bad count-errors"), "null handle, B == 0": ({0: None, 1: 0}, EINVAL, "bad count-errors"),
+        "cw0 < 0, B == 0": ({1: 0, 2: -1}, EINVAL, "bad count-errors"),
+        "null bits": ({4: None}, EINVAL, "bad count-errors"), "null counts": ({5: None}, EINVAL, "bad count-errors"),
+        "B == 0, null pointers": ({1: 0, 4: None, 5: None}, 0, "")},
 }
 PARAMS = [(name, case) for name in CASES for case in CASES[name]]
 
@@ -126,7 +140,7 @@ def check(name, case):
     change, rc, msg = CASES[name][case]
     a = _good(name)
     for i, v in change.items():
-        a[i] = e["odd"].h if isinstance(v, str) else v
+        a[i] = e[v].h if isinstance(v, str) else v
     L = N.lib()
     assert getattr(L, name)(*a) == rc, L.tdec_last_error().decode()
     if rc:

@@ -11,9 +11,6 @@ The sums over the branches are plain loops over r = 0 .. R-1, the definition's o
 import numpy as np
 
 import fading_ref as F
-from oracle.workload_ref import philox4x32_10
-
-_M = np.uint64(0xFFFFFFFF)
 
 
 def combine(y, h, nv, coh=1):
@@ -59,16 +56,4 @@ def combine(y, h, nv, coh=1):
 def gains(cw_global, R, n_blocks, seed, K=0.0):
     """complex128 [len(cw_global), R, n_blocks]: fading_ref.gains with branch b's draw on
     the domain word FADE_DOMAIN | b << 16 (branch 0: fading_ref.gains itself)."""
-    cw = np.asarray(cw_global, np.uint64)[:, None]
-    j = np.arange(n_blocks, dtype=np.uint64)[None, :]
-    odd = (j & np.uint64(1)).astype(bool)
-    out = np.empty((cw.shape[0], R, n_blocks), np.complex128)
-    for b in range(R):
-        r = philox4x32_10(cw & _M, cw >> np.uint64(32), j >> np.uint64(1), F.FADE_DOMAIN | (b << 16), seed & 0xFFFFFFFF,
-                          seed >> 32)
-        u1 = ((np.where(odd, r[2], r[0]) >> 8).astype(np.float64) + 0.5) * 2.0 ** -24
-        u2 = ((np.where(odd, r[3], r[1]) >> 8).astype(np.float64) + 0.5) * 2.0 ** -24
-        rad = np.sqrt(0.5) * np.sqrt(-2.0 * np.log(u1))
-        w = rad * np.cos(2 * np.pi * u2) + 1j * rad * np.sin(2 * np.pi * u2)
-        out[:, b] = np.sqrt(K / (K + 1.0)) + np.sqrt(1.0 / (K + 1.0)) * w
-    return out
+    return np.stack([F.gains(cw_global, n_blocks, seed, K, branch=b) for b in range(R)], axis=1)

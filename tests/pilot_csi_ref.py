@@ -12,7 +12,7 @@ behind it is tests/fading_ref.py's.
 import numpy as np
 
 import fading_ref as F
-from oracle.workload_ref import philox4x32_10
+from oracle.workload_ref import box_muller, philox4x32_10, stream_words
 
 PILOT_DOMAIN = 0x4D6C
 CFO_DOMAIN = 0x5E7B
@@ -135,6 +135,14 @@ def cfo_of(cw_global, seed, cfo_max):
     r = philox4x32_10(cw & _M, cw >> np.uint64(32), z, CFO_DOMAIN, seed & 0xFFFFFFFF, seed >> 32)
     u = ((r[0] >> 8).astype(np.float64) + 0.5) * 2.0 ** -24
     return np.float64(cfo_max) * (2.0 * u - 1.0)
+
+
+def pilot_noise(cw_global, n_pilots, seed, sigma, branch=0):
+    """complex128 [n, n_pilots]: the noise of pilot k (over the frame's pilots alone) of receive
+    branch `branch`, Box-Muller in oracle.workload_ref.awgn's form on a stream of its own,
+    philox4x32_10({g_lo, g_hi, k >> 1, PILOT_DOMAIN | branch << 16}, seed): words x, y for even
+    k and z, w for odd k."""
+    return box_muller(*stream_words(cw_global, n_pilots, seed, PILOT_DOMAIN | (branch << 16)), sigma)
 
 
 def rotate(frames0, f_g):
