@@ -109,6 +109,25 @@ def _declare(L):
             f.argtypes, f.restype = argtypes[name], restype.get(name, i)
 
 
+# every symbol include/harq.h declares (hybrid ARQ): built into libtdec.so,
+# kept apart from EXPORTS as MODEM_EXPORTS is
+HARQ_EXPORTS = ("harq_depuncture_acc_dev", "harq_workload_tx_dev")
+
+
+def _declare_harq(L):
+    """argtypes and restype of include/harq.h's exports; a library that lacks them (an older
+    build loaded by the A/B tools) is left as it is, and a call then fails by name."""
+    i, l, d, p, q, Q = C.c_int, C.c_long, C.c_double, _vp, C.c_int64, C.c_uint64
+    argtypes = {
+        "harq_depuncture_acc_dev": [p, i, p, i, l, i, p, p, p],
+        "harq_workload_tx_dev": [p, i, i, q, Q, p, i, i, d, i, d, i, p, p, p, p],
+    }
+    for name in HARQ_EXPORTS:
+        if hasattr(L, name):
+            f = getattr(L, name)
+            f.argtypes, f.restype = argtypes[name], i
+
+
 def lib():
     """Load libtdec.so (building it first if this is a build tree without it)."""
     global _lib
@@ -120,6 +139,7 @@ def lib():
                     build.build()
                 L = C.CDLL(LIB_PATH)
                 _declare(L)
+                _declare_harq(L)
                 _lib = L
     return _lib
 

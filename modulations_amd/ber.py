@@ -35,6 +35,14 @@ The pilots' energy is not charged to Eb/N0.
 faded, independently noisy branches and combines them (maximal ratio) in front of the
 demapper, with --csi known or pilots.  Eb/N0 is per branch: the array gain (10 log10 R dB
 of collected energy) is not charged, so the curves show it together with the diversity gain.
+
+--harq chase | ir with --max-tx T sends a codeword again while its decode is
+wrong, up to T transmissions, and soft-combines them (workload.HarqPipeline): chase repeats
+the --rate pattern, ir cycles through its redundancy versions into a rate-1/3 decoder.  The
+ACK is genie-aided (the error count against the known info bits).  awgn or a fading channel
+with known gains, one branch; every transmission has fresh noise and gains.  Eb/N0 is per
+transmission: the retransmissions' energy is not charged, mean_tx says how many there were.
+Each point records the residual BER / FER after T, tx_hist and mean_tx.
 """
 from __future__ import annotations
 
@@ -80,6 +88,8 @@ def sweep_config(a, inv_perm=None):
                        cfo=float(a.cfo), csi_noise=a.csi_noise)
         if "branches" in fading:   # (absent for one branch, likewise)
             cfg["rx_branches"] = fading["branches"]
+    if getattr(a, "harq", None):   # (absent without the flag, likewise)
+        cfg.update(harq=a.harq, max_tx=int(a.max_tx))
     if inv_perm is not None:
         cfg["inv_perm_digest"] = interleaver_digest(inv_perm)
     return cfg
@@ -178,6 +188,37 @@ def run_point(pipe, codec, mod, ebn0, start, count, batch, seed, device, times=N
     return cnt
 
 
+def run_point_harq(pipe, mod, ebn0, start, count, batch, seed, device, tx_hist, fading=None):
+    """run_point through a workload.HarqPipeline: global codewords [start, start + count) are sent up
+    to pipe.max_tx times, a row again while its decode has bit errors (genie-aided ACK), each
+    transmission with its codec (pipe.codec(t)), fresh noise and fresh gains.  Returns the residual
+    counters; tx_hist (int64 [max_tx + 1] device tensor) gains at entry i the codewords that used i
+    transmissions (the ones still wrong after the last count there)."""
+    import torch
+    from . import demap as D
+    from . import sharding as S
+    from .workload import count_errors, make_symbols
+    cnt = torch.zeros(3, dtype=torch.int64, device=device)
+    for off, n in S.batches(count, batch):
+        active, used, e = None, torch.zeros(n, dtype=torch.int64, device=device), None
+        for t in range(pipe.max_tx):
+            out = make_symbols(pipe.codec(t), n, mod, ebn0, seed, device, cw0=start + off, want_info=False,
+                               fading=fading, tx=t)
+            if fading is None:
+                bits = pipe.receive(t, out[1], out[2], active=active)
+            else:
+                z, nvs = D.equalize_device(out[1], out[3], out[2], coh=fading["coh"])
+                bits = pipe.receive(t, z, nvs, active=active)
+            used += 1 if active is None else active
+            e = count_errors(pipe.mother, bits, seed, cw0=start + off)
+            active = e != 0
+            if not bool(active.any()):   # (the tool's only host round trip: nothing left to send)
+                break
+        tx_hist += torch.bincount(used, minlength=tx_hist.numel())[:tx_hist.numel()]
+        cnt += torch.stack([e.sum(dtype=torch.int64), (e > 0).sum(), torch.tensor(n, device=device)]).to(torch.int64)
+    return cnt
+
+
 def arg_parser():
     ap = argparse.ArgumentParser()
     ap.add_argument("--mod", default="256QAM")
@@ -219,6 +260,11 @@ def arg_parser():
                     help="fading channels: receive branches per burst (1 .. 8), independently faded and noisy, "
                          "maximal-ratio combined in front of the demapper; Eb/N0 is per branch (the array gain "
                          "is not charged)")
+    ap.add_argument("--harq", choices=["chase", "ir"], default=None,
+                    help="hybrid ARQ with a genie-aided ACK: resend a codeword while its decode is wrong and "
+                         "soft-combine; chase repeats the pattern, ir cycles its redundancy versions into a "
+                         "rate-1/3 decoder (known CSI, one branch)")
+    ap.add_argument("--max-tx", type=int, default=4, help="--harq: transmissions per codeword at most")
     ap.add_argument("--out", default=None)
     ap.add_argument("--dist-backend", default="nccl", help="nccl (= RCCL) on the node; gloo to rehearse")
     ap.add_argument("--all-on-device0", action="store_true", help="every rank on GPU 0 (rehearsal on a 1-GPU box)")
@@ -231,10 +277,12 @@ def main(argv=None):
     import torch.distributed as dist
     from . import dvb_rcs2_turbo as M
     from . import sharding as S
-    from .workload import DevicePipeline
+    from .workload import DevicePipeline, HarqPipeline
 
     ap = arg_parser()
     a = ap.parse_args(argv)
+    if a.harq and (a.csi == "pilots" or a.rx_branches > 1 or not 1 <= a.max_tx <= 65536):
+        ap.error("--harq takes --csi known, one receive branch and 1 <= --max-tx <= 65536")
     if a.coherence < 1 or not (0.0 <= a.rician_k < float("inf")):
         ap.error("--coherence must be >= 1 and --rician-k a finite value >= 0")
     if not 1 <= a.rx_branches <= 8:
@@ -283,11 +331,22 @@ def main(argv=None):
                             device=device.index, early_stop=a.early_stop, es_decoder=a.es_decoder)
     if world > 1:   # every rank must decode with the same de-interleaver
         S.check_same_interleaver(codec.inv_perm, dist, device if a.dist_backend == "nccl" else "cpu")
-    pipe = DevicePipeline(codec, a.mod, a.batch, device, demap=a.demap, csi=fading is not None)
     results = list(done.values())
-    # one untimed batch first: code-object loading and first-launch costs stay out of
-    # the first point's figures
-    run_point(pipe, codec, a.mod, 2.0, 0, min(a.batch, 65536), a.batch, a.seed, device, fading=fading, pilots=pilots)
+    if a.harq:
+        kw = dict(algo=a.algo, interleaver=a.interleaver, device=device.index)
+        versions = range(codec.punct["period"]) if a.harq == "ir" else (0,)
+        codecs = [codec if r == 0 else M.DVBRCS2_Turbo(a.n, a.rate, a.iterations, rv=r, **kw) for r in versions]
+        mother = codec if a.harq == "chase" else M.DVBRCS2_Turbo(a.n, "1/3", a.iterations, early_stop=a.early_stop,
+                                                                 es_decoder=a.es_decoder, **kw)
+        pipe = HarqPipeline(codecs, mother, a.mod, a.batch, device, demap=a.demap, max_tx=a.max_tx)
+        run_point_harq(pipe, a.mod, 2.0, 0, min(a.batch, 65536), a.batch, a.seed, device,
+                       torch.zeros(a.max_tx + 1, dtype=torch.int64, device=device), fading=fading)
+    else:
+        pipe = DevicePipeline(codec, a.mod, a.batch, device, demap=a.demap, csi=fading is not None)
+        # one untimed batch first: code-object loading and first-launch costs stay out of
+        # the first point's figures
+        run_point(pipe, codec, a.mod, 2.0, 0, min(a.batch, 65536), a.batch, a.seed, device, fading=fading,
+                  pilots=pilots)
     for e in parse_points(a.ebn0):
         if e in done:
             continue
@@ -295,8 +354,13 @@ def main(argv=None):
         t0 = time.time()
         times = []
         hist = torch.zeros(a.iterations + 1, dtype=torch.int64, device=device) if a.early_stop else None
-        cnt = run_point(pipe, codec, a.mod, e, start, count, a.batch, ebn0_seed(a.seed, e), device, times, hist,
-                        fading=fading, pilots=pilots)
+        if a.harq:   # (no iteration histogram: a row is decoded once per transmission)
+            hist = torch.zeros(a.max_tx + 1, dtype=torch.int64, device=device)
+            cnt = run_point_harq(pipe, a.mod, e, start, count, a.batch, ebn0_seed(a.seed, e), device, hist,
+                                 fading=fading)
+        else:
+            cnt = run_point(pipe, codec, a.mod, e, start, count, a.batch, ebn0_seed(a.seed, e), device, times, hist,
+                            fading=fading, pilots=pilots)
         if hist is not None:
             cnt = torch.cat([cnt, hist])   # one reduction for the error counters and the histogram
         if world > 1 and a.dist_backend != "nccl":
@@ -322,7 +386,16 @@ def main(argv=None):
         if pilots is not None:
             rec.update(csi="pilots", pilot_len=a.pilot_len, pilot_spacing=a.pilot_spacing, cfo=a.cfo,
                        csi_noise=a.csi_noise)
-        if a.early_stop:
+        if a.harq:
+            h = [int(x) for x in cnt[3:].tolist()]
+            for k in ("step_ms", "decode_ms", "step_codewords_per_s", "decode_codewords_per_s"):
+                del rec[k]   # (the bench step's figures: not taken here)
+            # ber / fer are the residual ones after max_tx; tx_hist[i]: codewords that used i transmissions
+            rec.update(harq=a.harq, max_tx=a.max_tx, tx_hist=h,
+                       mean_tx=sum(i * c for i, c in enumerate(h)) / max(1, ncw))
+            if a.early_stop:
+                rec["early_stop"] = True
+        elif a.early_stop:
             h = [int(x) for x in cnt[3:].tolist()]
             rec["early_stop"] = True
             if a.es_decoder != "frame":

@@ -6,7 +6,7 @@
 //
 // One translation unit: the kernel files, the kernel-order manifest, the handle and the
 // decoder's entry points here, the soft demapper's host code in tdec_demap_api.hip, then
-// the self-tests and the workload generators.
+// the self-tests, the workload generators and hybrid ARQ's host code (tdec_harq.hip).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -72,6 +72,7 @@ namespace {
     (void)k_combine<0, true>, (void)k_combine<0, false>, (void)k_combine<1, true>, (void)k_combine<1, false>,
         (void)k_combine<2, true>, (void)k_combine<2, false>;                                       // diversity (§14)
     (void)k_workload_faded<BranchArgs>, (void)k_workload_frame_branches<false>, (void)k_workload_frame_branches<true>;
+    (void)k_depuncture_acc<true>, (void)k_depuncture_acc<false>, (void)k_workload_faded<TxArgs>;   // HARQ (§15)
 }
 #undef EACH_BPS
 #undef BOTH
@@ -2153,3 +2154,6 @@ int tdec_encode_dev(tdec_t *h, int B, const uint8_t *d_bits, uint8_t *d_coded, v
 }
 
 }  // extern "C"
+
+// ---- hybrid ARQ: soft combining into the planes, retransmissions of the generator (§15) ----
+#include "tdec_harq.hip"

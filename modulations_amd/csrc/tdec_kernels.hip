@@ -29,6 +29,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #include "npmath.hip"
 
 namespace tdec {
@@ -2048,6 +2050,45 @@ __global__ __launch_bounds__(BLOCK) void k_depuncture(int B, int N, const float 
     float *base = planes + tile * tile_floats(N);
     reinterpret_cast<float4 *>(base)[(long)k * WAVE + lane] = make_float4(v[0], v[1], v[2], v[3]);
     reinterpret_cast<float2 *>(base + (long)N * WAVE * 4)[(long)k * WAVE + lane] = make_float2(v[4], v[5]);
+}
+
+// HARQ soft combining: a retransmission's LLR rows ADDED to planes that hold
+// what the receiver has so far, k_depuncture's thread shape (one thread per (tile, step,
+// lane), src[] by scalar loads, the tile's float4 + float2).  Gather form: plane slot c takes
+// LLR row row_of[c] (null: row c), so no two threads touch one plane element; a slot whose
+// entry is outside [0, n_rows) is neither read nor written, nor is a lane past n_slots.
+// A component the pattern transmits becomes plane + (float)llr[j], one f32 add (F64 rows are
+// rounded to f32 first, :466); one it does not transmit is stored back as it was loaded.
+template <bool F64>
+__global__ __launch_bounds__(BLOCK) void k_depuncture_acc(int n_slots, int N, const void *llr, long stride, int n_rows,
+                                                         const int *__restrict__ row_of,
+                                                         const int *__restrict__ src, float *planes, long total) {
+    using T = typename std::conditional<F64, double, float>::type;
+    const long t = (long)blockIdx.x * BLOCK + threadIdx.x;
+    if (t >= total) return;                 // total = tiles * N * 64
+    const int lane = (int)(t & (WAVE - 1));
+    const long q = t >> 6;
+    const int k = __builtin_amdgcn_readfirstlane((int)(q % N));
+    const long tile = __builtin_amdgcn_readfirstlane((int)(q / N));
+    const long slot = tile * WAVE + lane;
+    if (slot >= n_slots) return;
+    const long r = row_of ? (long)row_of[slot] : slot;
+    if (r < 0 || r >= n_rows) return;
+    const T *row = static_cast<const T *>(llr) + r * stride;
+    float *base = planes + tile * tile_floats(N);
+    float4 *px = reinterpret_cast<float4 *>(base) + ((long)k * WAVE + lane);
+    float2 *pz = reinterpret_cast<float2 *>(base + (long)N * WAVE * 4) + ((long)k * WAVE + lane);
+    float4 x = *px;
+    float2 z = *pz;
+    float *v[6] = {&x.x, &x.y, &x.z, &x.w, &z.x, &z.y};
+    const int comp[6] = {0, 1, 2, 3, 6, 7};
+#pragma unroll
+    for (int c = 0; c < 6; ++c) {
+        const int j = src[(long)comp[c] * N + k];
+        if (j >= 0) *v[c] = *v[c] + (float)row[j];
+    }
+    *px = x;
+    *pz = z;
 }
 
 }  // namespace tdec

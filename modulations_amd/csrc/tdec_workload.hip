@@ -15,6 +15,7 @@
 // Receive branch b of a codeword draws its noise, gains and pilot noise with
 // b in the upper 16 bits of the domain word (0x2B0E | b << 16, ...): branch 0 is the
 // streams above; the info bits and the rotation are the codeword's, shared by its branches.
+// Retransmission tx of a codeword takes the same tag, tx << 16 (tx <= 65535).
 // Info bit j of a codeword is bit j % 32 of word (j % 128) / 32 of block j / 128.
 // Noise: Box-Muller, u = (x >> 8 + 0.5) * 2^-24 in (0, 1], formed in float32
 // (x >> 8 = 2^24 - 1 rounds to u = 1: radius 0, or angle 2 pi): one complex sample
@@ -192,6 +193,11 @@ struct FadeArgs {
 struct BranchArgs : FadeArgs {
     int R;
 };
+// TxArgs: transmission tx of every codeword, its noise and gains tagged as
+// branch tx's; fade = 0: no gains, x + n
+struct TxArgs : FadeArgs {
+    int tx, fade;
+};
 __device__ __forceinline__ float2 fade_gain(uint64_t cw, long j, uint64_t seed, const FadeArgs &f,
                                             uint32_t domain = FADE_DOMAIN) {
     const Philox4 r = philox4x32_10(Philox4{(uint32_t)cw, (uint32_t)(cw >> 32), (uint32_t)(j >> 1), domain},
@@ -202,6 +208,20 @@ __device__ __forceinline__ float2 fade_gain(uint64_t cw, long j, uint64_t seed, 
     float sn, cs;
     sincospif(2.0f * u2, &sn, &cs);
     return make_float2(f.los + f.scat * (rad * cs), f.scat * (rad * sn));
+}
+
+// Copy b of symbol s of codeword cw at row `row` of syms and h: table point x through gain
+// block s / coh of the streams tagged b (b << 16 in the domain word) plus that stream's noise
+// (n: the untagged sample, which is stream 0's).  A receive branch (BranchArgs) or a
+// retransmission (TxArgs): the same tag, hence the same samples.
+__device__ __forceinline__ void branch_symbol(const WorkloadArgs &p, const FadeArgs &f, uint64_t cw, long s, float2 x,
+                                              float2 n, int b, long row) {
+    const long j = s / f.coh;
+    const uint32_t tag = (uint32_t)b << 16;
+    const float2 g = fade_gain(cw, j, p.seed, f, FADE_DOMAIN | tag);
+    const float2 nb = b ? awgn(cw, s, p, NOISE_DOMAIN | tag) : n;
+    if (s == j * f.coh) f.h[row * f.nh + j] = g;
+    p.syms[row * p.S + s] = make_float2((g.x * x.x - g.y * x.y) + nb.x, (g.x * x.y + g.y * x.x) + nb.y);
 }
 
 // Row-order flush of a chunk of symbol labels lab[k][lane] (k < ns): symbols
@@ -218,14 +238,12 @@ __device__ __forceinline__ void flush_syms(const WorkloadArgs &p, const F &f, lo
             const uint64_t cw = p.cw0 + (uint64_t)(base + l);
             const float2 x = cons[lab[k][l]], n = awgn(cw, s0 + k, p);
             if constexpr (std::is_same<F, BranchArgs>::value) {
-                const long s = s0 + k, j = s / f.coh;
-                for (int b = 0; b < f.R; ++b) {
-                    const uint32_t tag = (uint32_t)b << 16;
-                    const float2 g = fade_gain(cw, j, p.seed, f, FADE_DOMAIN | tag);
-                    const float2 nb = b ? awgn(cw, s, p, NOISE_DOMAIN | tag) : n;
-                    const long row = (base + l) * f.R + b;
-                    if (s == j * f.coh) f.h[row * f.nh + j] = g;
-                    p.syms[row * p.S + s] = make_float2((g.x * x.x - g.y * x.y) + nb.x, (g.x * x.y + g.y * x.x) + nb.y);
+                for (int b = 0; b < f.R; ++b) branch_symbol(p, f, cw, s0 + k, x, n, b, (base + l) * f.R + b);
+            } else if constexpr (std::is_same<F, TxArgs>::value) {
+                if (f.fade) branch_symbol(p, f, cw, s0 + k, x, n, f.tx, base + l);
+                else {
+                    const float2 nt = f.tx ? awgn(cw, s0 + k, p, NOISE_DOMAIN | (uint32_t)f.tx << 16) : n;
+                    p.syms[(base + l) * (long)p.S + s0 + k] = make_float2(x.x + nt.x, x.y + nt.y);
                 }
             } else if constexpr (FADE) {
                 const long s = s0 + k, j = s / f.coh;

@@ -164,14 +164,22 @@ class DVBRCS2_Turbo:
                           'tile': batches, every block size, any TDEC_FRAME.
                           reserve() also sizes one plane buffer per wave;
                           refill_stats() reports the last launch's trips.
+      rv         redundancy version 0 .. period-1 of the rate's puncture pattern
+                 (tables.redundancy_version; hybrid ARQ): every parity
+                 row shifted by rv phases.  `punct`, `n_coded`, the handle and with it
+                 encode / decode / the demappers / the workload generator use the
+                 shifted pattern; 0 (default) is the table's pattern.
     """
 
     def __init__(self, N_couples, code_rate, iterations=8, *, algo="max-log", inv_perm="numpy",
-                 interleaver="reference", device=None, early_stop=False, es_decoder="frame"):
+                 interleaver="reference", device=None, early_stop=False, es_decoder="frame", rv=0):
         self.N = N_couples
         self.k_info = N_couples * 2
         self.iterations = iterations
         self.punct = PUNCTURE_PATTERNS[code_rate]          # KeyError for an unknown rate, as :292
+        self.rv = int(rv)
+        if self.rv:
+            self.punct = _t.redundancy_version(self.punct, self.rv)
         if self.N not in INTERLEAVER_PARAMS:
             raise ValueError(f"Block size {self.N} not in standard tables.")
         self.rate = code_rate
@@ -406,6 +414,36 @@ class DVBRCS2_Turbo:
             raise ValueError("planes buffer smaller than planes_bytes(B)")
         self.handle.call("tdec_depuncture_dev", llr.shape[0], _n.ptr(llr),
                          llr.stride(0) if llr.shape[0] > 1 else llr.shape[1], _n.ptr(planes), self._stream(stream))
+        return planes
+
+    def depuncture_accumulate_device(self, llr, planes, B, row_of=None, stream=None):
+        """planes += this codec's de-puncture of `llr` (hybrid ARQ soft combining, DESIGN.md §15;
+        harq_depuncture_acc_dev): plane slot c of the B slots takes row row_of[c] of llr, a
+        float32 or float64 [n_rows, >= llr_len] device tensor with contiguous rows (float64 values
+        are rounded to float32 first).  row_of: int32 [B] device tensor; an entry outside
+        [0, n_rows), -1 by convention, leaves the slot untouched; None: row c, n_rows == B.
+        What the pattern does not transmit keeps its bits.  `planes` may have been written
+        by any codec of the same N, and is read by the decoder of any."""
+        import torch
+        if not isinstance(llr, torch.Tensor) or llr.dtype not in (torch.float32, torch.float64):
+            raise TypeError("llr must be a float32 or float64 tensor")
+        self._dev_check(llr, "llr", llr.dtype, rows_contig=True)
+        self._dev_check(planes, "planes", torch.float32)
+        B = int(B)
+        if B < 0:
+            raise ValueError("B must be >= 0")
+        if planes.numel() * 4 < self.planes_bytes(B):
+            raise ValueError("planes buffer smaller than planes_bytes(B)")
+        n_rows = llr.shape[0]
+        if B and llr.shape[1] < self.handle.llr_len:
+            raise IndexError(f"index {llr.shape[1]} is out of bounds for axis 0 with size {llr.shape[1]}")
+        if row_of is not None:
+            self._dev_check(row_of, "row_of", torch.int32, (B,))
+        elif n_rows != B:
+            raise ValueError(f"without row_of every slot takes its own row: llr must have {B} rows, got {n_rows}")
+        self.handle.call("harq_depuncture_acc_dev", B, _n.ptr(llr), int(llr.dtype == torch.float64),
+                         llr.stride(0) if n_rows > 1 else llr.shape[1], n_rows, _n.ptr(row_of), _n.ptr(planes),
+                         self._stream(stream))
         return planes
 
     def tail_gate(self, stream=None):

@@ -139,6 +139,20 @@ def puncture_matrix(punct):
     return m
 
 
+def redundancy_version(punct, rv):
+    """Redundancy version `rv` of a puncture pattern (hybrid ARQ):
+    every parity row shifted cyclically by rv phases, row_rv[p] = row[(p + rv) % period],
+    so that over rv = 0 .. period-1 each parity the mother code has in a row the pattern
+    uses at all is sent once.  rv = 0 is the pattern itself."""
+    per = punct['period']
+    rv = int(rv)
+    if not 0 <= rv < per:
+        raise ValueError(f"redundancy version {rv} outside 0 .. {per - 1} (the pattern's period is {per})")
+    if rv == 0:
+        return punct
+    return {'period': per, **{k: [punct[k][(p + rv) % per] for p in range(per)] for k in ('W1', 'Y1', 'W2', 'Y2')}}
+
+
 def coded_size(n, punct):
     """n_coded of :398-402 (what the codec advertises)."""
     per = punct['period']

@@ -17,7 +17,8 @@ def noise_n0(constellation, rate, bps, ebn0_db):
     return es / (rate * bps * 10 ** (ebn0_db / 10.0))
 
 
-def make_symbols(codec, B, mod, ebn0_db, seed, device, cw0=0, want_info=True, fading=None, pilots=None, cfo=0.0):
+def make_symbols(codec, B, mod, ebn0_db, seed, device, cw0=0, want_info=True, fading=None, pilots=None, cfo=0.0,
+                 tx=0):
     """(info uint8 [B, 2N] or None, received symbols complex64 [B, S], N0) on `device`.
 
     One launch of the counter-based generator (tdec_workload_dev): Philox info
@@ -44,7 +45,13 @@ def make_symbols(codec, B, mod, ebn0_db, seed, device, cw0=0, want_info=True, fa
     independently noisy copies of every codeword (tdec_workload_branches_dev, and
     tdec_workload_frame_branches_dev with `pilots`); symbols and gains, or frames and h_true,
     are then 3-D, [B, R, ...], branch 0 what the call without "branches" returns.  ebn0_db is
-    per branch: the array gain is not charged."""
+    per branch: the array gain is not charged.
+
+    tx=t (1 .. 65535; hybrid ARQ): transmission t of the same codewords
+    (harq_workload_tx_dev): the same info bits through `codec`'s pattern (a codec built
+    with rv= sends another redundancy version), noise and gains of streams of their own,
+    those of receive branch t.  With or without `fading`; neither `pilots` nor
+    "branches".  tx=0 (default) is the calls above."""
     import torch
     from . import _native as _n
     bps = D.MODULATIONS[mod]["bps"]
@@ -60,6 +67,17 @@ def make_symbols(codec, B, mod, ebn0_db, seed, device, cw0=0, want_info=True, fa
     if pilots is None and cfo:
         raise ValueError("cfo needs pilots=PilotLayout(...)")
     cw0, seed, sigma = int(cw0), int(seed) & 0xFFFFFFFFFFFFFFFF, float(np.sqrt(n0 / 2))
+    tx = int(tx)
+    if tx:
+        if not 0 < tx <= 65535:
+            raise ValueError(f"tx must be 0 .. 65535, got {tx}")
+        if pilots is not None or (fading is not None and fading.get("branches") is not None):
+            raise ValueError("a retransmission (tx > 0) takes neither pilots nor receive branches")
+    if fading is None and tx:
+        syms = torch.empty((B, S), dtype=torch.complex64, device=device)
+        h.call("harq_workload_tx_dev", int(B), tx, cw0, seed, _n.ptr(table), len(cons), bps, sigma, 0, 0.0, 1,
+               _n.ptr(syms), None, _n.ptr(info), codec._stream(None))
+        return info, syms, n0
     if fading is None:
         syms = torch.empty((B, S), dtype=torch.complex64, device=device)
         h.call("tdec_workload_dev", int(B), cw0, seed, _n.ptr(table), len(cons), bps, sigma, _n.ptr(syms),
@@ -86,6 +104,10 @@ def make_symbols(codec, B, mod, ebn0_db, seed, device, cw0=0, want_info=True, fa
                          ((B, R), "tdec_workload_branches_dev", "tdec_workload_frame_branches_dev"))
     syms = torch.empty((*rows, S), dtype=torch.complex64, device=device)
     gains = torch.empty((*rows, -(-S // coh)), dtype=torch.complex64, device=device)
+    if tx:
+        h.call("harq_workload_tx_dev", int(B), tx, cw0, seed, _n.ptr(table), len(cons), bps, sigma, 1, k, coh,
+               _n.ptr(syms), _n.ptr(gains), _n.ptr(info), codec._stream(None))
+        return info, syms, n0, gains
     h.call(fade, *map(int, rows), cw0, seed, _n.ptr(table), len(cons), bps, sigma, k, coh, _n.ptr(syms), _n.ptr(gains),
            _n.ptr(info), codec._stream(None))
     if pilots is None:
@@ -369,3 +391,102 @@ class DevicePipeline:
         n = syms.shape[0]
         z, nvs = fn(syms, csi, nv, coh=coh, out=self.z[:n], nv_out=self.nv_sym[:n], stream=stream)
         return z, nvs, self.div_f32_t
+
+
+class HarqPipeline:
+    """Hybrid ARQ receiver: every transmission of a batch of codewords is
+    soft-combined into one plane buffer, which `mother`'s decoder reads after each.
+
+    codecs: the codec of each transmission, cycled (transmission t uses codecs[t % len]).
+    Chase combining is [c]; incremental redundancy is
+    [DVBRCS2_Turbo(N, rate, rv=r, ...) for r in range(period)].  mother: the codec whose
+    decoder reads the combined planes -- for Chase the same codec, for incremental
+    redundancy a rate-1/3 codec of the same N, interleaver and inv_perm (its early_stop /
+    es_decoder / algo choose the decoder).  A codec whose N, perm or inv_perm differs from
+    mother's is refused: the planes would mean something else to the decoder.
+
+    receive(t, syms, noise_var, active=None) queues, on one stream and with no host round
+    trip: transmission 0 through codecs[0]'s fused plane demapper straight into the planes;
+    transmission t > 0 through the flat demapper (demap.compute_llr_device, decoder sign) and
+    the combining kernel (depuncture_accumulate_device); then mother.decode_planes_device.
+    max_tx bounds t.  Buffers are sized once."""
+
+    def __init__(self, codecs, mother, mod, B, device, demap="max-log", max_tx=4):
+        import torch
+        codecs = list(codecs)
+        if not codecs:
+            raise ValueError("HarqPipeline needs at least one transmission codec")
+        for i, c in enumerate(codecs):
+            if c.N != mother.N or not np.array_equal(c.perm, mother.perm) or not np.array_equal(c.inv_perm, mother.inv_perm):
+                raise ValueError(f"codecs[{i}] and mother differ in N, perm or inv_perm: their planes are not "
+                                 "the same code's")
+            if c.device != mother.device:
+                raise ValueError(f"codecs[{i}] and mother are on different devices")
+        if int(max_tx) < 1:
+            raise ValueError("max_tx must be >= 1")
+        self.codecs, self.mother, self.mod, self.B, self.max_tx = codecs, mother, mod, int(B), int(max_tx)
+        self.bps = D.MODULATIONS[mod]["bps"]
+        self.cons = D.constellation(mod)
+        self.demap = demap
+        D.check_algo(demap)
+        self.div_f32_t = D.demap_mode(np.complex64, self.cons.dtype, np.float64(1.0))[1]
+        self.early_stop = bool(getattr(mother, "early_stop", False))
+        mother.reserve(self.B)
+        self.planes = torch.empty(mother.planes_bytes(self.B) // 4, dtype=torch.float32, device=device)
+        self.bits = torch.empty((self.B, mother.k_info), dtype=torch.int32, device=device)
+        self.n_iter = torch.empty(self.B, dtype=torch.int32, device=device) if self.early_stop else None
+        # symbols per codeword of each transmission codec (the versions of one rate differ where N % period != 0)
+        self.S = [-(-c.handle.enc_len // self.bps) for c in codecs]
+        self.llr = torch.empty(self.B * max(self.S) * self.bps, dtype=torch.float64, device=device)
+        self.row_of = torch.empty(self.B, dtype=torch.int32, device=device)
+        self._iota = torch.arange(self.B, dtype=torch.int32, device=device)
+        self._none = torch.full((self.B,), -1, dtype=torch.int32, device=device)
+
+    def codec(self, t):
+        """The codec transmission t is sent with."""
+        return self.codecs[t % len(self.codecs)]
+
+    def receive(self, t, syms, noise_var, active=None, stream=None):
+        """Transmission t (0 .. max_tx - 1) of the batch: complex64 [n <= B, S_t] device symbols,
+        S_t the symbols of codec(t); equalised ones (demap.equalize_device's z) for a fading
+        channel.  noise_var: a scalar, a float64 [n] device tensor (one per row) or a
+        float64 [n, S_t] one (one per symbol, equalize_device's nv_sym).  active (t > 0): a bool
+        or int32 [n] device tensor; rows with 0 are not combined, so their planes and hence
+        their bits stay as they were (None: every row).  Returns the bits, int32 [n, 2N]
+        (a view of `bits`), ready for work queued on `stream` afterwards."""
+        import torch
+        t = int(t)
+        if not 0 <= t < self.max_tx:
+            raise ValueError(f"transmission {t} outside 0 .. {self.max_tx - 1} (max_tx)")
+        c, S = self.codec(t), self.S[t % len(self.codecs)]
+        if not isinstance(syms, torch.Tensor) or syms.dim() != 2 or syms.shape[0] > self.B or syms.shape[1] != S:
+            raise ValueError(f"transmission {t}: symbols must be [<= {self.B}, {S}], got "
+                             f"{tuple(getattr(syms, 'shape', ()))}")
+        n = syms.shape[0]
+        if isinstance(noise_var, torch.Tensor):
+            div32, nve = self.div_f32_t, noise_var
+        else:
+            _, div32, nve = D.demap_mode(np.complex64, self.cons.dtype, np.float64(noise_var))
+        if t == 0:
+            if active is not None:
+                raise ValueError("transmission 0 writes every row's planes: it takes no `active`")
+            c.demap_planes_device(syms, self.cons, self.bps, nve, self.planes, div_f32=div32, stream=stream,
+                                  algo=self.demap)
+        else:
+            row_of = None
+            if active is not None:
+                if (not isinstance(active, torch.Tensor) or active.dtype not in (torch.bool, torch.int32)
+                        or tuple(active.shape) != (n,) or active.device != self.row_of.device):
+                    raise ValueError(f"active must be a bool or int32 [{n}] tensor on the pipeline's device")
+                row_of = self.row_of[:n]
+                with torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream(c.device)):
+                    torch.where(active != 0, self._iota[:n], self._none[:n], out=row_of)
+            llr = self.llr[:n * S * self.bps].view(n, S * self.bps)
+            # (a numpy float64 scalar: the division's dtype of transmission 0's plane demapper)
+            D.compute_llr_device(syms, self.mod, nve if isinstance(nve, torch.Tensor) else np.float64(noise_var),
+                                 out=llr, sign=-1, stream=stream, algo=self.demap)
+            c.depuncture_accumulate_device(llr, self.planes, n, row_of=row_of, stream=stream)
+        bits = self.bits[:n]
+        es = {"n_iter": self.n_iter[:n]} if self.early_stop else {}
+        self.mother.decode_planes_device(self.planes, n, bits, stream=stream, **es)
+        return bits
