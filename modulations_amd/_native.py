@@ -192,29 +192,25 @@ _mlib = None
 
 
 def _declare_modem(L):
-    i, l, d = C.c_int, C.c_long, C.c_double
-    L.mdm_map_dev.argtypes = [i, _vp, l, i, _vp, i, _vp, _vp]
-    L.mdm_map.argtypes = [i, _vp, l, i, _vp, i, _vp]
-    L.mdm_demod_dev.argtypes = [i, i, _vp, i, l, i, _vp, d, _vp, i, _vp, _vp, _vp]
-    L.mdm_demod.argtypes = [i, i, _vp, i, l, i, _vp, d, _vp, i, _vp]
-    L.mdm_fir_dev.argtypes = [i, _vp, i, l, _vp, i, i, i, l, l, _vp, _vp]
-    L.mdm_fir.argtypes = [i, _vp, i, l, _vp, i, i, i, l, l, _vp]
-    L.mdm_iq_quantize_dev.argtypes = [i, _vp, i, l, _vp, _vp, _vp]
-    L.mdm_iq_quantize.argtypes = [i, _vp, i, l, _vp]
-    L.mdm_iq_dequantize_dev.argtypes = [i, _vp, l, _vp, _vp]
-    L.mdm_iq_dequantize.argtypes = [i, _vp, l, _vp]
-    L.mdm_mix_dev.argtypes = [i, _vp, i, l, l, _vp, d, d, _vp, _vp]
-    L.mdm_mix.argtypes = [i, _vp, i, l, l, _vp, d, d, _vp]
-    L.mdm_burst_find_dev.argtypes = [i, _vp, i, l, _vp, i, l, _vp, _vp, _vp, _vp]
-    L.mdm_burst_find.argtypes = [i, _vp, i, l, _vp, i, l, _vp, _vp, _vp]
-    L.mdm_xcorr_peak_dev.argtypes = [i, _vp, l, _vp, i, _vp, _vp, _vp, _vp]
-    L.mdm_xcorr_peak.argtypes = [i, _vp, l, _vp, i, _vp, _vp, _vp]
-    L.mdm_carrier_dev.argtypes = [i, _vp, i, l, _vp, _vp, _vp, _vp, _vp, _vp, _vp]
-    L.mdm_carrier.argtypes = [i, _vp, i, l, _vp, _vp, _vp, _vp, _vp, _vp]
-    for name in MODEM_EXPORTS:
-        getattr(L, name).restype = C.c_int
-    L.mdm_last_error.argtypes = []
-    L.mdm_last_error.restype = C.c_char_p
+    """argtypes and restype of every export of include/modem.h.  A _dev form takes its host form's
+    arguments and then a stream, after the NaN counter (demod) or the scratch (iq_quantize) where it has one."""
+    i, l, d, p = C.c_int, C.c_long, C.c_double, _vp
+    host = {
+        "mdm_map": [i, p, l, i, p, i, p], "mdm_demod": [i, i, p, i, l, i, p, d, p, i, p],
+        "mdm_fir": [i, p, i, l, p, i, i, i, l, l, p], "mdm_iq_quantize": [i, p, i, l, p],
+        "mdm_iq_dequantize": [i, p, l, p], "mdm_mix": [i, p, i, l, l, p, d, d, p],
+        "mdm_carrier": [i, p, i, l, p, p, p, p, p, p],
+    }
+    burst, xcorr = [i, p, i, l, p, i, l], [i, p, l, p, i, p]   # the two with other outputs: up to preamble_len, corr
+    argtypes = {
+        "mdm_last_error": [], **host, **{n + "_dev": a + [p] for n, a in host.items()},
+        "mdm_demod_dev": host["mdm_demod"] + [p, p], "mdm_iq_quantize_dev": host["mdm_iq_quantize"] + [p, p],
+        "mdm_burst_find": burst + [p, p, p], "mdm_burst_find_dev": burst + [p, p, p, p],   # dev: smooth, result, ...
+        "mdm_xcorr_peak": xcorr + [p, p], "mdm_xcorr_peak_dev": xcorr + [p, p, p],         # ... scratch, stream
+    }
+    for name in MODEM_EXPORTS:   # int (a status) is what every export returns but the message
+        f = getattr(L, name)
+        f.argtypes, f.restype = argtypes[name], C.c_char_p if name == "mdm_last_error" else i
 
 
 def modem_lib():

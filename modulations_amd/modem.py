@@ -52,16 +52,46 @@ def _bits_u8(bits):
     return u
 
 
+_p = _n.ptr
+
+
+def _call(name, *args):
+    """One call of the libmodem.so export `name`, its status through modem_check."""
+    _n.modem_check(getattr(_n.modem_lib(), name)(*args))
+
+
+def _ordinal(t):
+    """The device ordinal of a tensor, as the _dev forms take it."""
+    return t.device.index or 0
+
+
+_F64 = {}
+
+
+def _f64(a):
+    """The library's sample-type flag of an array or a tensor: 1 for complex128, 0 for complex64."""
+    f = _F64.get(a.dtype)
+    if f is None:      # numpy's and torch's complex128, each dtype's name looked at once
+        f = _F64[a.dtype] = int(str(a.dtype).endswith("complex128"))
+    return f
+
+
+def _out(t, like, shape, dtype):
+    """An output argument of a device form: the caller's as it is, or a new tensor on the device of `like`."""
+    if t is not None:
+        return t
+    import torch
+    return torch.empty(shape, dtype=getattr(torch, dtype), device=like.device)
+
+
 def map_bits(bits, bps, table, device=0):
     """Labels (MSB first, zero-padded to whole symbols) -> table[label] on the GPU."""
     table = np.ascontiguousarray(table)
     assert table.dtype in (np.complex64, np.complex128) and table.size == 1 << bps
     u = _bits_u8(bits)
-    n_sym = -(-u.size // bps)
-    out = np.empty(n_sym, table.dtype)
+    out = np.empty(-(-u.size // bps), table.dtype)
     if u.size:
-        _n.modem_check(_n.modem_lib().mdm_map(device, _n.ptr(u), u.size, bps, _n.ptr(table),
-                                              int(table.dtype == np.complex128), _n.ptr(out)))
+        _call("mdm_map", device, _p(u), u.size, bps, _p(table), _f64(table), _p(out))
     return out
 
 
@@ -72,16 +102,19 @@ def _syms_c(syms):
     return np.ascontiguousarray(s.ravel())
 
 
+def _demod_tables(labels, cons):
+    return (None if labels is None else np.ascontiguousarray(labels, np.int32),
+            None if cons is None else np.ascontiguousarray(cons, np.complex128))
+
+
 def hard_demod(syms, kind, bps, labels=None, scale=0.0, cons=None, nan_raises=True, device=0):
     """uint8 bits [n_sym * bps] of the given rule (include/modem.h MDM_DEMOD_*)."""
     s = _syms_c(syms)
     out = np.empty(s.size * bps, np.uint8)
-    lab = None if labels is None else np.ascontiguousarray(labels, np.int32)
-    c = None if cons is None else np.ascontiguousarray(cons, np.complex128)
+    lab, c = _demod_tables(labels, cons)
     if s.size:
-        _n.modem_check(_n.modem_lib().mdm_demod(device, kind, _n.ptr(s), int(s.dtype == np.complex128), s.size, bps,
-                                                _n.ptr(lab), float(scale), _n.ptr(c), int(bool(nan_raises)),
-                                                _n.ptr(out)))
+        _call("mdm_demod", device, kind, _p(s), _f64(s), s.size, bps, _p(lab), float(scale), _p(c),
+              int(bool(nan_raises)), _p(out))
     return out
 
 
@@ -91,22 +124,17 @@ def fir(x, taps, up=1, down=1, offset=0, n_out=None, device=0):
     h = np.ascontiguousarray(taps, np.float64)
     out = np.empty(n_out, np.complex128)
     if n_out:
-        _n.modem_check(_n.modem_lib().mdm_fir(device, _n.ptr(s), int(s.dtype == np.complex128), s.size, _n.ptr(h),
-                                              h.size, up, down, offset, n_out, _n.ptr(out)))
+        _call("mdm_fir", device, _p(s), _f64(s), s.size, _p(h), h.size, up, down, offset, n_out, _p(out))
     return out
 
 
 def iq_quantize(sig, device=0):
     """_save_iq's int8 interleaved samples of a complex signal."""
-    s = np.asarray(sig)
-    if s.dtype not in (np.complex64, np.complex128):
-        s = s.astype(np.complex128)
-    s = np.ascontiguousarray(s.ravel())
+    s = _syms_c(sig)
     if s.size == 0:
         raise ValueError("zero-size array to reduction operation maximum which has no identity")
     out = np.empty(2 * s.size, np.int8)
-    _n.modem_check(_n.modem_lib().mdm_iq_quantize(device, _n.ptr(s), int(s.dtype == np.complex128), s.size,
-                                                  _n.ptr(out)))
+    _call("mdm_iq_quantize", device, _p(s), _f64(s), s.size, _p(out))
     return out
 
 
@@ -125,67 +153,48 @@ def iq_dequantize(raw, device=0):
                              f"({r.size // 2},)")
     out = np.empty(r.size // 2, np.complex64)
     if out.size:
-        _n.modem_check(_n.modem_lib().mdm_iq_dequantize(device, _n.ptr(r), out.size, _n.ptr(out)))
+        _call("mdm_iq_dequantize", device, _p(r), out.size, _p(out))
     return out
 
 
 # ---- device-resident forms (torch tensors on the GPU, stream-ordered) ----------------------
 def map_device(bits, bps, table, out=None, stream=None):
-    import torch
     table = np.ascontiguousarray(table)
-    f64 = table.dtype == np.complex128
-    n_sym = -(-bits.numel() // bps)
-    if out is None:
-        out = torch.empty(n_sym, dtype=torch.complex128 if f64 else torch.complex64, device=bits.device)
-    _n.modem_check(_n.modem_lib().mdm_map_dev(bits.device.index or 0, _n.ptr(bits), bits.numel(), bps, _n.ptr(table),
-                                              int(f64), _n.ptr(out), _n.stream_ptr(stream)))
+    out = _out(out, bits, -(-bits.numel() // bps), "complex128" if _f64(table) else "complex64")
+    _call("mdm_map_dev", _ordinal(bits), _p(bits), bits.numel(), bps, _p(table), _f64(table), _p(out),
+          _n.stream_ptr(stream))
     return out
 
 
 def demod_device(syms, kind, bps, labels=None, scale=0.0, cons=None, nan_raises=True, out=None, nan_count=None,
                  stream=None):
-    import torch
-    lab = None if labels is None else np.ascontiguousarray(labels, np.int32)
-    c = None if cons is None else np.ascontiguousarray(cons, np.complex128)
-    if out is None:
-        out = torch.empty(syms.numel() * bps, dtype=torch.uint8, device=syms.device)
-    _n.modem_check(_n.modem_lib().mdm_demod_dev(syms.device.index or 0, kind, _n.ptr(syms),
-                                                int(syms.dtype == torch.complex128), syms.numel(), bps, _n.ptr(lab),
-                                                float(scale), _n.ptr(c), int(bool(nan_raises)), _n.ptr(out),
-                                                _n.ptr(nan_count), _n.stream_ptr(stream)))
+    lab, c = _demod_tables(labels, cons)
+    out = _out(out, syms, syms.numel() * bps, "uint8")
+    _call("mdm_demod_dev", _ordinal(syms), kind, _p(syms), _f64(syms), syms.numel(), bps, _p(lab), float(scale), _p(c),
+          int(bool(nan_raises)), _p(out), _p(nan_count), _n.stream_ptr(stream))
     return out
 
 
 def fir_device(x, taps, up=1, down=1, offset=0, n_out=None, out=None, stream=None):
-    import torch
     h = np.ascontiguousarray(taps, np.float64)
-    if out is None:
-        out = torch.empty(n_out, dtype=torch.complex128, device=x.device)
-    _n.modem_check(_n.modem_lib().mdm_fir_dev(x.device.index or 0, _n.ptr(x), int(x.dtype == torch.complex128),
-                                              x.numel(), _n.ptr(h), h.size, up, down, offset, n_out, _n.ptr(out),
-                                              _n.stream_ptr(stream)))
+    out = _out(out, x, n_out, "complex128")
+    _call("mdm_fir_dev", _ordinal(x), _p(x), _f64(x), x.numel(), _p(h), h.size, up, down, offset, n_out, _p(out),
+          _n.stream_ptr(stream))
     return out
 
 
 def iq_quantize_device(sig, out=None, scratch=None, stream=None):
-    import torch
-    if out is None:
-        out = torch.empty(2 * sig.numel(), dtype=torch.int8, device=sig.device)
-    if scratch is None:
-        scratch = torch.empty(1, dtype=torch.int64, device=sig.device)
-    _n.modem_check(_n.modem_lib().mdm_iq_quantize_dev(sig.device.index or 0, _n.ptr(sig),
-                                                      int(sig.dtype == torch.complex128), sig.numel(), _n.ptr(out),
-                                                      _n.ptr(scratch), _n.stream_ptr(stream)))
+    out = _out(out, sig, 2 * sig.numel(), "int8")
+    scratch = _out(scratch, sig, 1, "int64")
+    _call("mdm_iq_quantize_dev", _ordinal(sig), _p(sig), _f64(sig), sig.numel(), _p(out), _p(scratch),
+          _n.stream_ptr(stream))
     return out
 
 
 def iq_dequantize_device(raw, out=None, stream=None):
-    import torch
     n = raw.numel() // 2
-    if out is None:
-        out = torch.empty(n, dtype=torch.complex64, device=raw.device)
-    _n.modem_check(_n.modem_lib().mdm_iq_dequantize_dev(raw.device.index or 0, _n.ptr(raw), n, _n.ptr(out),
-                                                        _n.stream_ptr(stream)))
+    out = _out(out, raw, n, "complex64")
+    _call("mdm_iq_dequantize_dev", _ordinal(raw), _p(raw), n, _p(out), _n.stream_ptr(stream))
     return out
 
 
@@ -241,8 +250,7 @@ def mix(sig, w, fs, dc=None, i0=0, device=0):
     out = np.empty(s.size, np.complex128)
     dcv = _dc(dc)              # held here: the library reads it during the call
     if s.size:
-        _n.modem_check(_n.modem_lib().mdm_mix(device, _n.ptr(s), int(s.dtype == np.complex128), s.size,
-                                              int(i0), _n.ptr(dcv), float(w), float(fs), _n.ptr(out)))
+        _call("mdm_mix", device, _p(s), _f64(s), s.size, int(i0), _p(dcv), float(w), float(fs), _p(out))
     return out
 
 
@@ -254,9 +262,8 @@ def burst_find(sig, preamble_len, win=1000, dc=None, want_smooth=False, device=0
     start, mx = np.zeros(1, np.int64), np.zeros(1, np.float64)
     smooth = np.empty(s.size, np.float64) if want_smooth else None
     dcv = _dc(dc)
-    _n.modem_check(_n.modem_lib().mdm_burst_find(device, _n.ptr(s), int(s.dtype == np.complex128), s.size,
-                                                 _n.ptr(dcv), int(win), int(preamble_len), _n.ptr(start),
-                                                 _n.ptr(mx), _n.ptr(smooth)))
+    _call("mdm_burst_find", device, _p(s), _f64(s), s.size, _p(dcv), int(win), int(preamble_len), _p(start), _p(mx),
+          _p(smooth))
     return int(start[0]), float(mx[0]), smooth
 
 
@@ -267,8 +274,7 @@ def xcorr_peak(region, wave, want_corr=False, device=0):
     _check_xcorr(r.size, h.size)
     idx, peak = np.zeros(1, np.int64), np.zeros(1, np.float64)
     corr = np.empty(r.size - h.size + 1, np.float64) if want_corr else None
-    _n.modem_check(_n.modem_lib().mdm_xcorr_peak(device, _n.ptr(r), r.size, _n.ptr(h), h.size, _n.ptr(corr),
-                                                 _n.ptr(idx), _n.ptr(peak)))
+    _call("mdm_xcorr_peak", device, _p(r), r.size, _p(h), h.size, _p(corr), _p(idx), _p(peak))
     return int(idx[0]), float(peak[0]), corr
 
 
@@ -283,41 +289,30 @@ def carrier_recovery(syms, init_phase, init_freq, alpha, kind, device=0):
     out = np.empty(s.shape, np.complex128)
     fin = np.empty((s.shape[0], 2), np.float64)
     if s.shape[0]:
-        _n.modem_check(_n.modem_lib().mdm_carrier(device, _n.ptr(s), s.shape[0], s.shape[1], _n.ptr(ph), _n.ptr(fr),
-                                                  _n.ptr(al), _n.ptr(kd), _n.ptr(out), _n.ptr(fin)))
+        _call("mdm_carrier", device, _p(s), s.shape[0], s.shape[1], _p(ph), _p(fr), _p(al), _p(kd), _p(out), _p(fin))
     return out, fin
 
 
 def mix_device(sig, w, fs, dc=None, i0=0, out=None, stream=None):
-    import torch
-    if out is None:
-        out = torch.empty(sig.numel(), dtype=torch.complex128, device=sig.device)
+    out = _out(out, sig, sig.numel(), "complex128")
     dcv = _dc(dc)
-    _n.modem_check(_n.modem_lib().mdm_mix_dev(sig.device.index or 0, _n.ptr(sig), int(sig.dtype == torch.complex128),
-                                              sig.numel(), int(i0), _n.ptr(dcv), float(w), float(fs),
-                                              _n.ptr(out), _n.stream_ptr(stream)))
+    _call("mdm_mix_dev", _ordinal(sig), _p(sig), _f64(sig), sig.numel(), int(i0), _p(dcv), float(w), float(fs), _p(out),
+          _n.stream_ptr(stream))
     return out
 
 
-def _rx_scratch(n_out, scratch, device):
-    import torch
-    if scratch is None:
-        scratch = torch.empty(2 * -(-n_out // _RX_TILE), dtype=torch.int64, device=device)
-    return scratch
+def _rx_scratch(n_out, scratch, like):
+    return _out(scratch, like, 2 * -(-n_out // _RX_TILE), "int64")
 
 
 def burst_find_device(sig, preamble_len, win=1000, dc=None, smooth=None, result=None, scratch=None, stream=None):
     """Stream-ordered; returns the int64[2] result record (burst_result decodes it)."""
-    import torch
     _check_burst(sig.numel(), win, preamble_len)
-    if result is None:
-        result = torch.empty(2, dtype=torch.int64, device=sig.device)
-    scratch = _rx_scratch(sig.numel(), scratch, sig.device)
+    result = _out(result, sig, 2, "int64")
+    scratch = _rx_scratch(sig.numel(), scratch, sig)
     dcv = _dc(dc)
-    _n.modem_check(_n.modem_lib().mdm_burst_find_dev(sig.device.index or 0, _n.ptr(sig),
-                                                     int(sig.dtype == torch.complex128), sig.numel(), _n.ptr(dcv),
-                                                     int(win), int(preamble_len), _n.ptr(smooth), _n.ptr(result),
-                                                     _n.ptr(scratch), _n.stream_ptr(stream)))
+    _call("mdm_burst_find_dev", _ordinal(sig), _p(sig), _f64(sig), sig.numel(), _p(dcv), int(win), int(preamble_len),
+          _p(smooth), _p(result), _p(scratch), _n.stream_ptr(stream))
     return result
 
 
@@ -333,12 +328,10 @@ def xcorr_peak_device(region, wave, corr=None, result=None, scratch=None, stream
     _check_xcorr(region.numel(), wave.numel())
     if region.dtype != torch.complex128 or wave.dtype != torch.complex128:
         raise ValueError("xcorr_peak_device takes complex128 tensors")
-    if result is None:
-        result = torch.empty(2, dtype=torch.int64, device=region.device)
-    scratch = _rx_scratch(region.numel() - wave.numel() + 1, scratch, region.device)
-    _n.modem_check(_n.modem_lib().mdm_xcorr_peak_dev(region.device.index or 0, _n.ptr(region), region.numel(),
-                                                     _n.ptr(wave), wave.numel(), _n.ptr(corr), _n.ptr(result),
-                                                     _n.ptr(scratch), _n.stream_ptr(stream)))
+    result = _out(result, region, 2, "int64")
+    scratch = _rx_scratch(region.numel() - wave.numel() + 1, scratch, region)
+    _call("mdm_xcorr_peak_dev", _ordinal(region), _p(region), region.numel(), _p(wave), wave.numel(), _p(corr),
+          _p(result), _p(scratch), _n.stream_ptr(stream))
     return result
 
 
@@ -356,14 +349,11 @@ def carrier_recovery_device(syms, init_phase, init_freq, alpha, kind, out=None, 
         raise ValueError("syms must be a contiguous complex128 tensor of shape (candidates, symbols)")
     C, n = syms.shape
     ph, fr, al, kd = (torch.from_numpy(a).to(syms.device) for a in _carrier_params(C, init_phase, init_freq, alpha, kind))
-    if out is None:
-        out = torch.empty((C, n), dtype=torch.complex128, device=syms.device)
-    if final is None:
-        final = torch.empty((C, 2), dtype=torch.float64, device=syms.device)
+    out = _out(out, syms, (C, n), "complex128")
+    final = _out(final, syms, (C, 2), "float64")
     if C:
-        _n.modem_check(_n.modem_lib().mdm_carrier_dev(syms.device.index or 0, _n.ptr(syms), C, n, _n.ptr(ph),
-                                                      _n.ptr(fr), _n.ptr(al), _n.ptr(kd), _n.ptr(out), _n.ptr(final),
-                                                      _n.stream_ptr(stream)))
+        _call("mdm_carrier_dev", _ordinal(syms), _p(syms), C, n, _p(ph), _p(fr), _p(al), _p(kd), _p(out), _p(final),
+              _n.stream_ptr(stream))
     return out, final
 
 

@@ -8,8 +8,8 @@ kernel is launched -- the good arguments are small, so nothing here depends on t
 The order of the checks is part of what is pinned where a caller can observe it: the
 demodulator's rule and bps, the FIR's shape and its taps pointer are looked at before the empty
 call; the data pointers only after it, so an empty call with null buffers is MDM_OK.  One
-refusal is made after the host form has staged its input: a complex128 table with bps 8, which
-mdm_map hands to mdm_map_dev to refuse."""
+refusal is made after the host form has staged its input: a complex128 table with bps 8, whose
+size mdm_map looks at only then (mdm_map_dev looks at it at once, before the empty call)."""
 import ctypes as C
 
 import numpy as np
@@ -102,8 +102,14 @@ DEQUANT_CASES = {"n_pairs < 0": (dict(n_pairs=-1), EINVAL, "negative sample coun
                  "null raw": (dict(raw=None), EINVAL, _NULL), "null sig": (dict(sig=None), EINVAL, _NULL),
                  "n_pairs 0, null buffers": (dict(n_pairs=0, raw=None, sig=None), OK, "")}
 CASES = {
-    "mdm_map": MAP_CASES, "mdm_map_dev": MAP_CASES | {
-        "complex128 table, bps 8, n_bits 0": (dict(table_f64=1, bps=8, n_bits=0), EINVAL, "complex128 mapper tables")},
+    # the two forms look at a complex128 table's size at different moments: mdm_map_dev at once, mdm_map only
+    # after staging, so that its empty call is MDM_OK and its null buffers are refused first
+    "mdm_map": MAP_CASES | {
+        "complex128 table, bps 8, n_bits 0": (dict(table_f64=1, bps=8, n_bits=0), OK, ""),
+        "complex128 table, bps 8, null bits": (dict(table_f64=1, bps=8, bits=None), EINVAL, _NULL)},
+    "mdm_map_dev": MAP_CASES | {
+        "complex128 table, bps 8, n_bits 0": (dict(table_f64=1, bps=8, n_bits=0), EINVAL, "complex128 mapper tables"),
+        "complex128 table, bps 8, null bits": (dict(table_f64=1, bps=8, bits=None), EINVAL, "complex128 mapper tables")},
     "mdm_demod": DEMOD_CASES, "mdm_demod_dev": DEMOD_CASES,
     "mdm_fir": FIR_CASES, "mdm_fir_dev": FIR_CASES,
     "mdm_iq_quantize": QUANT_CASES,

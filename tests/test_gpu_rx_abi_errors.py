@@ -88,7 +88,10 @@ CASES = {
     "mdm_carrier": CARRIER_CASES | {
         "kind 3": (dict(kind=np.array([0, 3], np.int32)), EINVAL, "unknown carrier detector kind"),
         "kind -1": (dict(kind=np.array([-1, 0], np.int32)), EINVAL, "unknown carrier detector kind"),
-        "kind 3, n 0": (dict(kind=np.array([2, 3], np.int32), n=0), EINVAL, "unknown carrier detector kind")},
+        "kind 3, n 0": (dict(kind=np.array([2, 3], np.int32), n=0), EINVAL, "unknown carrier detector kind"),
+        # the kinds are read after the pointers are checked, and not at all for an empty batch
+        "kind 3, null final": (dict(kind=np.array([0, 3], np.int32), final=None), EINVAL, _NULL),
+        "kind 3, n_cand 0": (dict(kind=np.array([0, 3], np.int32), n_cand=0), OK, "")},
     "mdm_carrier_dev": CARRIER_CASES,
 }
 PARAMS = [(name, case) for name in CASES for case in CASES[name]]

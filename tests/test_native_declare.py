@@ -1,6 +1,7 @@
-"""The ctypes declarations of libtdec.so (_native._declare): every export's argument and
-return types against a literal table, written out from the assignments _declare consisted of
-before it became one table, and not from the code under test."""
+"""The ctypes declarations of libtdec.so (_native._declare) and of libmodem.so
+(_native._declare_modem): every export's argument and return types against a literal table,
+written out from the assignments each consisted of before it became one table, and not from the
+code under test."""
 import ctypes as C
 
 from modulations_amd import _native
@@ -85,6 +86,40 @@ DECLARED = {
     "tdec_workload_frame_branches_dev": ("int", "int void* void* int int int int int int void* double int64 uint64 "
                                                 "double void* void* void*"),
 }
+
+
+# libmodem.so (_native._declare_modem), dumped from the one assignment per export it consisted of before
+DECLARED_MODEM = {
+    "mdm_map_dev": ("int", "int void* long int void* int void* void*"),
+    "mdm_map": ("int", "int void* long int void* int void*"),
+    "mdm_demod_dev": ("int", "int int void* int long int void* double void* int void* void* void*"),
+    "mdm_demod": ("int", "int int void* int long int void* double void* int void*"),
+    "mdm_fir_dev": ("int", "int void* int long void* int int int long long void* void*"),
+    "mdm_fir": ("int", "int void* int long void* int int int long long void*"),
+    "mdm_iq_quantize_dev": ("int", "int void* int long void* void* void*"),
+    "mdm_iq_quantize": ("int", "int void* int long void*"),
+    "mdm_iq_dequantize_dev": ("int", "int void* long void* void*"),
+    "mdm_iq_dequantize": ("int", "int void* long void*"),
+    "mdm_last_error": ("char*", ""),
+    "mdm_mix_dev": ("int", "int void* int long long void* double double void* void*"),
+    "mdm_mix": ("int", "int void* int long long void* double double void*"),
+    "mdm_burst_find_dev": ("int", "int void* int long void* int long void* void* void* void*"),
+    "mdm_burst_find": ("int", "int void* int long void* int long void* void* void*"),
+    "mdm_xcorr_peak_dev": ("int", "int void* long void* int void* void* void* void*"),
+    "mdm_xcorr_peak": ("int", "int void* long void* int void* void* void*"),
+    "mdm_carrier_dev": ("int", "int void* int long void* void* void* void* void* void* void*"),
+    "mdm_carrier": ("int", "int void* int long void* void* void* void* void* void*"),
+}
+
+
+def test_every_modem_export_is_declared_as_before():
+    L = _native.modem_lib()
+    assert sorted(DECLARED_MODEM) == sorted(_native.MODEM_EXPORTS)
+    for name in _native.MODEM_EXPORTS:
+        f = getattr(L, name)
+        res, args = DECLARED_MODEM[name]
+        assert f.restype is TYPES[res], name
+        assert list(f.argtypes) == [TYPES[t] for t in args.split()], name
 
 
 def test_every_export_is_declared_as_before():
