@@ -859,7 +859,9 @@ static size_t es_prev_rows_of(const tdec_t *h) { return ((size_t)h->N + 15) / 16
 // (static striding) below 4 tiles per wave.  Measured (same bits): 1 M codewords
 // (8 tiles per wave) 243.8 -> 241.6 ms; at 2 tiles per wave the queue was no
 // faster (max-log 61.8 vs 62.6, log-MAP 381.2 vs 385.9 ms per 262 144), hence the
-// threshold.
+// threshold.  TDEC_TILE_WAVES (read per call) caps the persistent waves of the
+// fixed-iteration and the fused launch before this threshold sees them: tests make one
+// to three waves serve ten tiles with it, through the queue or by static striding.
 static int *tile_queue(tdec_t *h, int tiles, int waves, hipStream_t st) {
     if (tiles < 4 * waves) return nullptr;
     if (hipMemsetAsync(h->d_tile_ctr, 0, sizeof(int), st) != hipSuccess) return nullptr;
@@ -1312,8 +1314,10 @@ int tdec_decode_planes_dev(tdec_t *h, int B, const float *d_planes, int32_t *d_b
         HIPCHK(hipGetLastError());
         return mark_used(h, st);
     }
-    const int tiles = n_tiles_of(B), waves = std::min(tiles, h->max_waves);
+    const int tiles = n_tiles_of(B);
+    int waves = std::min(tiles, h->max_waves);
     if (waves > h->ws_waves) return fail(TDEC_ECAPACITY, "workspace too small: call tdec_reserve first");
+    if (const char *pc = getenv("TDEC_TILE_WAVES")) waves = std::max(1, std::min(waves, atoi(pc)));
     if (int rc = order_on(h, st)) return rc;
     // the tile queue from 4 tiles per wave (tile_queue()); the one launch that raises the tail flag
     return launch_tiles(h, decode_kernel(h->algo, h->N % win_of(h->algo) != 0), DEC_WAVES, B, waves, d_planes, d_bits,

@@ -496,9 +496,11 @@ int tdec_demap_decode_dev(tdec_t *h, int B, const float *d_syms, int S, const vo
     const void *k = fused_kernel(h->algo, h->N % win_unstaged(h->algo) != 0, cons_f64 != 0, bps);
     if (!k) return fail(TDEC_EUNSUPPORTED, "no fused demap-decode kernel for this modulation / algorithm");
     Guard g(h->device);
-    const int tiles = n_tiles_of(B), waves = waves_for(h, B);
+    const int tiles = n_tiles_of(B);
+    int waves = waves_for(h, B);
     if (waves > h->ws_waves || 2 * (size_t)waves * tile_floats(h->N) * sizeof(float) > h->planes_w.cap)
         return fail(TDEC_ECAPACITY, "workspace too small: call tdec_reserve_fused first");
+    if (const char *pc = getenv("TDEC_TILE_WAVES")) waves = std::max(1, std::min(waves, atoi(pc)));
     hipStream_t st = (hipStream_t)stream;
     if (int rc = handle_table(h, cons, cons_f64, M, bps, st)) return rc;
     const FusedDemapArgs fa{d_syms, S, std::min<long>((long)S * bps, h->llr_len), (const int *)h->d_src,

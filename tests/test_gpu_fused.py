@@ -4,7 +4,8 @@ L_final must be those of the two-launch path (k_demap_planes -> planes ->
 k_turbo_decode), which the other tests pin to the oracle, for every
 instantiated configuration, ragged batches and batches past the resident waves
 (the persistent loop reuses each wave's plane buffer, so stale L1 lines would
-show up here), plus an oracle spot check."""
+show up here), plus an oracle spot check.  Several tiles per wave at test-sized
+batches, on every instantiation, are in tests/test_gpu_fused_tiles.py."""
 import numpy as np
 import pytest
 
