@@ -128,6 +128,28 @@ def _declare_harq(L):
             f.argtypes, f.restype = argtypes[name], i
 
 
+# every symbol include/crc.h declares (frame check): built into libtdec.so,
+# kept apart as HARQ_EXPORTS is
+CRC_EXPORTS = ("crc_attach_dev", "crc_check_dev", "crc_check_u8_dev", "crc_workload_tx_dev")
+CRC_KINDS = {"crc16": 16, "crc32": 32}          # the header's CRC_KIND16 / CRC_KIND32: the width r
+
+
+def _declare_crc(L):
+    """argtypes and restype of include/crc.h's exports; a library that lacks them (an older
+    build loaded by the A/B tools) is left as it is, and a call then fails by name."""
+    i, l, d, p, q, Q = C.c_int, C.c_long, C.c_double, _vp, C.c_int64, C.c_uint64
+    argtypes = {
+        "crc_attach_dev": [i, i, l, i, p, p],
+        "crc_check_dev": [i, i, l, i, p, p, p, p],
+        "crc_check_u8_dev": [i, i, l, i, p, p, p, p],
+        "crc_workload_tx_dev": [p, i, i, q, Q, p, i, i, d, i, d, i, p, p, p, p],
+    }
+    for name in CRC_EXPORTS:
+        if hasattr(L, name):
+            f = getattr(L, name)
+            f.argtypes, f.restype = argtypes[name], i
+
+
 def lib():
     """Load libtdec.so (building it first if this is a build tree without it)."""
     global _lib
@@ -140,6 +162,7 @@ def lib():
                 L = C.CDLL(LIB_PATH)
                 _declare(L)
                 _declare_harq(L)
+                _declare_crc(L)
                 _lib = L
     return _lib
 

@@ -43,6 +43,16 @@ ACK is genie-aided (the error count against the known info bits).  awgn or a fad
 with known gains, one branch; every transmission has fresh noise and gains.  Eb/N0 is per
 transmission: the retransmissions' energy is not charged, mean_tx says how many there were.
 Each point records the residual BER / FER after T, tx_hist and mean_tx.
+
+--crc crc16 | crc32 puts a check field into the last r info bits of every
+codeword (crc.attach_device) and verifies the decoded bits on the device (crc.check_device).  A
+point then reports what a link sees: the payload BER, the FER (frames with a wrong bit, payload
+or check field), crc_fail (frames the check rejects) and undetected (frames that pass it with a
+payload bit error); fer = (crc_fail + undetected) / codewords.  With --harq, --ack crc lets the
+check drive the retransmissions (a row is sent again while it fails) in place of the genie
+(--ack genie, the default, which then compares with the info bits that carry the check field);
+the two can differ only on undetected rows.  The rate loss of the check field is not charged to
+Eb/N0, as for pilots.
 """
 from __future__ import annotations
 
@@ -90,6 +100,10 @@ def sweep_config(a, inv_perm=None):
             cfg["rx_branches"] = fading["branches"]
     if getattr(a, "harq", None):   # (absent without the flag, likewise)
         cfg.update(harq=a.harq, max_tx=int(a.max_tx))
+    if getattr(a, "crc", None):   # (absent without the flag, likewise)
+        cfg["crc"] = a.crc
+    if getattr(a, "ack", None):   # (absent unless given, likewise)
+        cfg["ack"] = a.ack
     if inv_perm is not None:
         cfg["inv_perm_digest"] = interleaver_digest(inv_perm)
     return cfg
@@ -139,8 +153,25 @@ def parse_points(spec):
     return [float(x) for x in spec.split(",")]
 
 
+def frame_check_counts(bits, info, kind, ok=None):
+    """int64 [5] on the device: payload bit errors, frames with a wrong bit anywhere (payload or
+    check field: what the genie NACKs), frames, frames the check rejects, frames that pass it
+    with a payload bit error -- decoded `bits` (int32 [n, 2N]) against the info bits that carry
+    the check field (uint8 [n, 2N]); ok: the rows' frame check where it has been taken already.
+    An error confined to the check field is a burst of at most r bits, which the check rejects,
+    so frames in error = rejected + undetected."""
+    import torch
+    from . import crc as CRC
+    payload = bits.shape[1] - CRC.KINDS[kind]["r"]
+    wrong = bits != info
+    e = wrong[:, :payload].sum(dim=1)
+    ok = CRC.check_device(bits, kind) if ok is None else ok
+    return torch.stack([e.sum(), wrong.any(dim=1).sum(), torch.tensor(bits.shape[0], device=bits.device),
+                        (ok == 0).sum(), ((ok != 0) & (e > 0)).sum()]).to(torch.int64)
+
+
 def run_point(pipe, codec, mod, ebn0, start, count, batch, seed, device, times=None, iter_hist=None, fading=None,
-              pilots=None):
+              pilots=None, crc=None):
     """Bit errors, frame errors and codewords of global codewords
     [start, start + count) at one Eb/N0 point.  The data of codeword g is a
     counter-based stream of (seed, g) (workload.make_symbols), so the counters
@@ -153,15 +184,22 @@ def run_point(pipe, codec, mod, ebn0, start, count, batch, seed, device, times=N
     with csi=True) equalises with the generator's gains.  pilots (optional, with fading):
     {"layout": demap.PilotLayout, "cfo": cycles per symbol, "noise": "known" | "pilots"}: the
     bursts are framed and the pipeline estimates the gains (and the noise) from the pilots.
-    fading["branches"] = R: symbols, gains and frames are [n, R, ...] and the pipeline combines."""
+    fading["branches"] = R: symbols, gains and frames are [n, R, ...] and the pipeline combines.
+    crc (a kind, optional; neither pilots nor branches): the codewords carry a check field and the
+    counters are frame_check_counts' five."""
     import torch
     from . import sharding as S
     from .workload import count_errors, make_symbols
-    cnt = torch.zeros(3, dtype=torch.int64, device=device)
+    cnt = torch.zeros(5 if crc else 3, dtype=torch.int64, device=device)
     ev = []
     for off, n in S.batches(count, batch):
-        csi = {}
-        if fading is None:
+        csi, info = {}, None
+        if crc:
+            info, syms, n0, *gains = make_symbols(codec, n, mod, ebn0, seed, device, cw0=start + off, fading=fading,
+                                                  crc=crc)
+            if fading is not None:
+                csi = {"csi": gains[0], "coh": fading["coh"]}
+        elif fading is None:
             _, syms, n0 = make_symbols(codec, n, mod, ebn0, seed, device, cw0=start + off, want_info=False)
         elif pilots is not None:
             _, syms, n0, _ = make_symbols(codec, n, mod, ebn0, seed, device, cw0=start + off, want_info=False,
@@ -178,9 +216,12 @@ def run_point(pipe, codec, mod, ebn0, start, count, batch, seed, device, times=N
         else:
             bits = pipe.run(syms, n0, events=e3[1:], **csi)[:n]
         ev.append(e3)
-        e = count_errors(codec, bits, seed, cw0=start + off)
         if iter_hist is not None:
             iter_hist += torch.bincount(pipe.n_iter[:n], minlength=iter_hist.numel())[:iter_hist.numel()]
+        if crc:
+            cnt += frame_check_counts(bits, info, crc)
+            continue
+        e = count_errors(codec, bits, seed, cw0=start + off)
         cnt += torch.stack([e.sum(dtype=torch.int64), (e > 0).sum(), torch.tensor(n, device=device)]).to(torch.int64)
     if times is not None:
         torch.cuda.synchronize()
@@ -188,35 +229,54 @@ def run_point(pipe, codec, mod, ebn0, start, count, batch, seed, device, times=N
     return cnt
 
 
-def run_point_harq(pipe, mod, ebn0, start, count, batch, seed, device, tx_hist, fading=None):
+def run_point_harq(pipe, mod, ebn0, start, count, batch, seed, device, tx_hist, fading=None, crc=None, ack="genie"):
     """run_point through a workload.HarqPipeline: global codewords [start, start + count) are sent up
     to pipe.max_tx times, a row again while its decode has bit errors (genie-aided ACK), each
     transmission with its codec (pipe.codec(t)), fresh noise and fresh gains.  Returns the residual
     counters; tx_hist (int64 [max_tx + 1] device tensor) gains at entry i the codewords that used i
-    transmissions (the ones still wrong after the last count there)."""
+    transmissions (the ones still wrong after the last count there).
+    crc (a kind; a pipeline built with crc=): the codewords carry a check field, the genie compares
+    the decoded rows against the attached info bits, and the counters are frame_check_counts' five.
+    ack="crc" then sends a row again while the pipeline's own frame check rejects it (receive()
+    without `active`: no decision comes from the host)."""
     import torch
     from . import demap as D
     from . import sharding as S
     from .workload import count_errors, make_symbols
-    cnt = torch.zeros(3, dtype=torch.int64, device=device)
+    cnt = torch.zeros(5 if crc else 3, dtype=torch.int64, device=device)
     for off, n in S.batches(count, batch):
-        active, used, e = None, torch.zeros(n, dtype=torch.int64, device=device), None
+        active, used, e, info = None, torch.zeros(n, dtype=torch.int64, device=device), None, None
         for t in range(pipe.max_tx):
-            out = make_symbols(pipe.codec(t), n, mod, ebn0, seed, device, cw0=start + off, want_info=False,
-                               fading=fading, tx=t)
+            out = make_symbols(pipe.codec(t), n, mod, ebn0, seed, device, cw0=start + off,
+                               want_info=bool(crc) and t == 0, fading=fading, tx=t, crc=crc)
+            info = out[0] if t == 0 else info
+            given = None if ack == "crc" else active
             if fading is None:
-                bits = pipe.receive(t, out[1], out[2], active=active)
+                bits = pipe.receive(t, out[1], out[2], active=given)
             else:
                 z, nvs = D.equalize_device(out[1], out[3], out[2], coh=fading["coh"])
-                bits = pipe.receive(t, z, nvs, active=active)
+                bits = pipe.receive(t, z, nvs, active=given)
             used += 1 if active is None else active
-            e = count_errors(pipe.mother, bits, seed, cw0=start + off)
-            active = e != 0
+            if ack == "crc":
+                active = pipe.ack[:n] == 0
+            elif crc:   # the genie: any wrong bit of the row, check field included
+                active = (bits != info).any(dim=1)
+            else:
+                e = count_errors(pipe.mother, bits, seed, cw0=start + off)
+                active = e != 0
             if not bool(active.any()):   # (the tool's only host round trip: nothing left to send)
                 break
         tx_hist += torch.bincount(used, minlength=tx_hist.numel())[:tx_hist.numel()]
+        if crc:
+            cnt += frame_check_counts(bits, info, crc, ok=pipe.ack[:n])
+            continue
         cnt += torch.stack([e.sum(dtype=torch.int64), (e > 0).sum(), torch.tensor(n, device=device)]).to(torch.int64)
     return cnt
+
+
+def _payload_bits(codec, kind):
+    from . import crc as CRC
+    return CRC.payload_bits(codec, kind)
 
 
 def arg_parser():
@@ -265,6 +325,14 @@ def arg_parser():
                          "soft-combine; chase repeats the pattern, ir cycles its redundancy versions into a "
                          "rate-1/3 decoder (known CSI, one branch)")
     ap.add_argument("--max-tx", type=int, default=4, help="--harq: transmissions per codeword at most")
+    ap.add_argument("--crc", choices=["crc16", "crc32"], default=None,
+                    help="attach this check field to the info bits of every codeword and verify the decoded bits on "
+                         "the device: a point reports the payload BER, FER, crc_fail and undetected (frames that "
+                         "pass the check with a payload bit error).  The check field's rate loss is not charged to "
+                         "Eb/N0, as for pilots (--csi known, one receive branch)")
+    ap.add_argument("--ack", choices=["genie", "crc"], default=None,
+                    help="--harq: what asks for a retransmission -- the comparison with the known info bits "
+                         "(genie, the default), or the frame check of --crc on the decoded bits (crc)")
     ap.add_argument("--out", default=None)
     ap.add_argument("--dist-backend", default="nccl", help="nccl (= RCCL) on the node; gloo to rehearse")
     ap.add_argument("--all-on-device0", action="store_true", help="every rank on GPU 0 (rehearsal on a 1-GPU box)")
@@ -283,6 +351,12 @@ def main(argv=None):
     a = ap.parse_args(argv)
     if a.harq and (a.csi == "pilots" or a.rx_branches > 1 or not 1 <= a.max_tx <= 65536):
         ap.error("--harq takes --csi known, one receive branch and 1 <= --max-tx <= 65536")
+    if a.ack and not a.harq:
+        ap.error("--ack needs --harq")
+    if a.ack == "crc" and not a.crc:
+        ap.error("--ack crc needs --crc")
+    if a.crc and (a.csi == "pilots" or a.rx_branches > 1):
+        ap.error("--crc takes --csi known and one receive branch")
     if a.coherence < 1 or not (0.0 <= a.rician_k < float("inf")):
         ap.error("--coherence must be >= 1 and --rician-k a finite value >= 0")
     if not 1 <= a.rx_branches <= 8:
@@ -338,15 +412,16 @@ def main(argv=None):
         codecs = [codec if r == 0 else M.DVBRCS2_Turbo(a.n, a.rate, a.iterations, rv=r, **kw) for r in versions]
         mother = codec if a.harq == "chase" else M.DVBRCS2_Turbo(a.n, "1/3", a.iterations, early_stop=a.early_stop,
                                                                  es_decoder=a.es_decoder, **kw)
-        pipe = HarqPipeline(codecs, mother, a.mod, a.batch, device, demap=a.demap, max_tx=a.max_tx)
+        pipe = HarqPipeline(codecs, mother, a.mod, a.batch, device, demap=a.demap, max_tx=a.max_tx, crc=a.crc)
         run_point_harq(pipe, a.mod, 2.0, 0, min(a.batch, 65536), a.batch, a.seed, device,
-                       torch.zeros(a.max_tx + 1, dtype=torch.int64, device=device), fading=fading)
+                       torch.zeros(a.max_tx + 1, dtype=torch.int64, device=device), fading=fading, crc=a.crc,
+                       ack=a.ack or "genie")
     else:
         pipe = DevicePipeline(codec, a.mod, a.batch, device, demap=a.demap, csi=fading is not None)
         # one untimed batch first: code-object loading and first-launch costs stay out of
         # the first point's figures
         run_point(pipe, codec, a.mod, 2.0, 0, min(a.batch, 65536), a.batch, a.seed, device, fading=fading,
-                  pilots=pilots)
+                  pilots=pilots, crc=a.crc)
     for e in parse_points(a.ebn0):
         if e in done:
             continue
@@ -357,10 +432,11 @@ def main(argv=None):
         if a.harq:   # (no iteration histogram: a row is decoded once per transmission)
             hist = torch.zeros(a.max_tx + 1, dtype=torch.int64, device=device)
             cnt = run_point_harq(pipe, a.mod, e, start, count, a.batch, ebn0_seed(a.seed, e), device, hist,
-                                 fading=fading)
+                                 fading=fading, crc=a.crc, ack=a.ack or "genie")
         else:
             cnt = run_point(pipe, codec, a.mod, e, start, count, a.batch, ebn0_seed(a.seed, e), device, times, hist,
-                            fading=fading, pilots=pilots)
+                            fading=fading, pilots=pilots, crc=a.crc)
+        nc = 5 if a.crc else 3   # the error counters in front of the histogram
         if hist is not None:
             cnt = torch.cat([cnt, hist])   # one reduction for the error counters and the histogram
         if world > 1 and a.dist_backend != "nccl":
@@ -368,10 +444,11 @@ def main(argv=None):
         S.reduce_counters(cnt, dist if world > 1 else None)
         torch.cuda.synchronize()
         be, fe, ncw = (int(x) for x in cnt[:3].tolist())
+        info_bits = _payload_bits(codec, a.crc) if a.crc else codec.k_info   # the bits `ber` is over
         dt = time.time() - t0
         rec = {"ebn0_db": e, "mod": a.mod, "n_couples": a.n, "rate": a.rate, "algo": a.algo,
                "interleaver": a.interleaver, "codewords": ncw,
-               "bit_errors": be, "frame_errors": fe, "ber": be / (ncw * codec.k_info), "fer": fe / ncw,
+               "bit_errors": be, "frame_errors": fe, "ber": be / (ncw * info_bits), "fer": fe / ncw,
                "seconds": dt, "codewords_per_s": ncw / dt, "gpus": world,
                # this rank's demap + decode (the bench's step) and decode alone, HIP events
                "step_ms": sum(t[0] for t in times), "decode_ms": sum(t[1] for t in times),
@@ -387,7 +464,7 @@ def main(argv=None):
             rec.update(csi="pilots", pilot_len=a.pilot_len, pilot_spacing=a.pilot_spacing, cfo=a.cfo,
                        csi_noise=a.csi_noise)
         if a.harq:
-            h = [int(x) for x in cnt[3:].tolist()]
+            h = [int(x) for x in cnt[nc:].tolist()]
             for k in ("step_ms", "decode_ms", "step_codewords_per_s", "decode_codewords_per_s"):
                 del rec[k]   # (the bench step's figures: not taken here)
             # ber / fer are the residual ones after max_tx; tx_hist[i]: codewords that used i transmissions
@@ -396,12 +473,16 @@ def main(argv=None):
             if a.early_stop:
                 rec["early_stop"] = True
         elif a.early_stop:
-            h = [int(x) for x in cnt[3:].tolist()]
+            h = [int(x) for x in cnt[nc:].tolist()]
             rec["early_stop"] = True
             if a.es_decoder != "frame":
                 rec["es_decoder"] = a.es_decoder
             rec["iter_hist"] = h   # iter_hist[i]: codewords that ran i iterations
             rec["mean_iters"] = sum(i * c for i, c in enumerate(h)) / max(1, ncw)
+        if a.crc:   # ber is the payload's; fer: frames with a wrong bit, check field included
+            rec.update(crc=a.crc, payload_bits=info_bits, crc_fail=int(cnt[3]), undetected=int(cnt[4]))
+            if a.harq:
+                rec["ack"] = a.ack or "genie"
         results.append(rec)
         if rank == 0:
             print(json.dumps(rec), flush=True)

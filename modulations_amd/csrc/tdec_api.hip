@@ -6,7 +6,8 @@
 //
 // One translation unit: the kernel files, the kernel-order manifest, the handle and the
 // decoder's entry points here, the soft demapper's host code in tdec_demap_api.hip, then
-// the self-tests, the workload generators and hybrid ARQ's host code (tdec_harq.hip).
+// the self-tests, the workload generators, hybrid ARQ's host code (tdec_harq.hip) and the
+// frame check's (tdec_crc_api.hip).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -26,6 +27,7 @@
 #include "tdec_spl.hip"
 #include "tdec_lowlat.hip"
 #include "tdec_frame.hip"
+#include "tdec_crc.hip"
 
 using namespace tdec;
 
@@ -73,6 +75,7 @@ namespace {
         (void)k_combine<2, true>, (void)k_combine<2, false>;                                       // diversity (§14)
     (void)k_workload_faded<BranchArgs>, (void)k_workload_frame_branches<false>, (void)k_workload_frame_branches<true>;
     (void)k_depuncture_acc<true>, (void)k_depuncture_acc<false>, (void)k_workload_faded<TxArgs>;   // HARQ (§15)
+    (void)k_crc<int32_t, false>, (void)k_crc<uint8_t, false>, (void)k_crc<uint8_t, true>;         // frame check (§16)
 }
 #undef EACH_BPS
 #undef BOTH
@@ -2161,3 +2164,6 @@ int tdec_encode_dev(tdec_t *h, int B, const uint8_t *d_bits, uint8_t *d_coded, v
 
 // ---- hybrid ARQ: soft combining into the planes, retransmissions of the generator (§15) ----
 #include "tdec_harq.hip"
+
+// ---- frame check: CRC attach and verify, the generator with the caller's info bits (§16) ----
+#include "tdec_crc_api.hip"

@@ -18,7 +18,7 @@ def noise_n0(constellation, rate, bps, ebn0_db):
 
 
 def make_symbols(codec, B, mod, ebn0_db, seed, device, cw0=0, want_info=True, fading=None, pilots=None, cfo=0.0,
-                 tx=0):
+                 tx=0, crc=None):
     """(info uint8 [B, 2N] or None, received symbols complex64 [B, S], N0) on `device`.
 
     One launch of the counter-based generator (tdec_workload_dev): Philox info
@@ -51,7 +51,14 @@ def make_symbols(codec, B, mod, ebn0_db, seed, device, cw0=0, want_info=True, fa
     (harq_workload_tx_dev): the same info bits through `codec`'s pattern (a codec built
     with rv= sends another redundancy version), noise and gains of streams of their own,
     those of receive branch t.  With or without `fading`; neither `pilots` nor
-    "branches".  tx=0 (default) is the calls above."""
+    "branches".  tx=0 (default) is the calls above.
+
+    crc="crc16" | "crc32" (DESIGN.md §16): the last r info bits of every codeword become the
+    check field of the others (crc.attach_device on the counter-based info bits), and the
+    generator encodes those bits (crc_workload_tx_dev): three launches on the codec's stream.
+    The returned info bits carry the check field (they are always made; want_info only says
+    whether they are returned); noise and gains are those of the same call without crc.  With
+    `tx` and `fading`; neither `pilots` nor "branches".  crc=None (default) is the calls above."""
     import torch
     from . import _native as _n
     bps = D.MODULATIONS[mod]["bps"]
@@ -73,6 +80,9 @@ def make_symbols(codec, B, mod, ebn0_db, seed, device, cw0=0, want_info=True, fa
             raise ValueError(f"tx must be 0 .. 65535, got {tx}")
         if pilots is not None or (fading is not None and fading.get("branches") is not None):
             raise ValueError("a retransmission (tx > 0) takes neither pilots nor receive branches")
+    if crc is not None:
+        return _make_symbols_crc(codec, B, crc, cw0, seed, table, len(cons), bps, sigma, n0, S, fading, pilots, tx,
+                                 want_info, device)
     if fading is None and tx:
         syms = torch.empty((B, S), dtype=torch.complex64, device=device)
         h.call("harq_workload_tx_dev", int(B), tx, cw0, seed, _n.ptr(table), len(cons), bps, sigma, 0, 0.0, 1,
@@ -121,6 +131,33 @@ def make_symbols(codec, B, mod, ebn0_db, seed, device, cw0=0, want_info=True, fa
             _n.ptr(pilots.pilots_device(S, frames.device)), sigma, cw0, seed, float(cfo), _n.ptr(frames), _n.ptr(h_true),
             codec._stream(None)))
     return info, frames, n0, h_true
+
+
+def _make_symbols_crc(codec, B, crc, cw0, seed, table, M, bps, sigma, n0, S, fading, pilots, tx, want_info, device):
+    """make_symbols' crc= path: info bits -> check field -> the generator on those bits."""
+    import torch
+    from . import _native as _n
+    from . import crc as CRC
+    CRC.payload_bits(codec, crc)
+    if pilots is not None or (fading is not None and fading.get("branches") is not None):
+        raise ValueError("crc= takes neither pilots nor receive branches")
+    k, coh = 0.0, 1
+    if fading is not None:
+        unknown = set(fading) - {"K", "coh", "branches"}
+        if unknown:
+            raise ValueError(f"fading takes the keys 'K', 'coh' and 'branches', not {sorted(unknown)}")
+        k, coh = float(fading.get("K", 0.0)), int(fading.get("coh", 1))
+        if not (0.0 <= k < float("inf")) or coh < 1:
+            raise ValueError("fading needs a finite K >= 0 and coh >= 1")
+    info = info_bits(codec, B, seed, device, cw0=cw0)
+    if B:
+        CRC.attach_device(info, crc, stream=codec._stream(None))
+    syms = torch.empty((B, S), dtype=torch.complex64, device=device)
+    gains = torch.empty((B, -(-S // coh)), dtype=torch.complex64, device=device) if fading is not None else None
+    codec.handle.call("crc_workload_tx_dev", int(B), int(tx), cw0, seed, _n.ptr(table), M, bps, sigma,
+                      int(fading is not None), k, coh, _n.ptr(info), _n.ptr(syms), _n.ptr(gains), codec._stream(None))
+    info = info if want_info else None
+    return (info, syms, n0) if fading is None else (info, syms, n0, gains)
 
 
 def info_bits(codec, B, seed, device, cw0=0):
@@ -409,9 +446,15 @@ class HarqPipeline:
     trip: transmission 0 through codecs[0]'s fused plane demapper straight into the planes;
     transmission t > 0 through the flat demapper (demap.compute_llr_device, decoder sign) and
     the combining kernel (depuncture_accumulate_device); then mother.decode_planes_device.
-    max_tx bounds t.  Buffers are sized once."""
+    max_tx bounds t.  Buffers are sized once.
 
-    def __init__(self, codecs, mother, mod, B, device, demap="max-log", max_tx=4):
+    crc="crc16" | "crc32" (DESIGN.md §16): the codewords carry a check field
+    (make_symbols(..., crc=...)).  After every decode the bits are verified on the device into
+    `ack` (int32 [B]: 1 = the row passed), and a receive(t > 0) without `active` combines only
+    the rows whose ack is 0 from the call before: the retransmission loop runs with no host
+    decision in it.  An explicit `active` still wins.  crc=None: no `ack`, nothing else changes."""
+
+    def __init__(self, codecs, mother, mod, B, device, demap="max-log", max_tx=4, crc=None):
         import torch
         codecs = list(codecs)
         if not codecs:
@@ -441,6 +484,14 @@ class HarqPipeline:
         self.row_of = torch.empty(self.B, dtype=torch.int32, device=device)
         self._iota = torch.arange(self.B, dtype=torch.int32, device=device)
         self._none = torch.full((self.B,), -1, dtype=torch.int32, device=device)
+        self.crc, self.ack = crc, None
+        if crc is not None:
+            from . import crc as CRC
+            CRC.payload_bits(mother, crc)
+            self.bits.zero_()
+            # (the first check of a row length uploads its table: here, not between transmissions)
+            self.ack = CRC.check_device(self.bits, crc) if self.B else torch.zeros(0, dtype=torch.int32, device=device)
+            self.ack.zero_()
 
     def codec(self, t):
         """The codec transmission t is sent with."""
@@ -452,8 +503,9 @@ class HarqPipeline:
         channel.  noise_var: a scalar, a float64 [n] device tensor (one per row) or a
         float64 [n, S_t] one (one per symbol, equalize_device's nv_sym).  active (t > 0): a bool
         or int32 [n] device tensor; rows with 0 are not combined, so their planes and hence
-        their bits stay as they were (None: every row).  Returns the bits, int32 [n, 2N]
-        (a view of `bits`), ready for work queued on `stream` afterwards."""
+        their bits stay as they were (None: every row, or with crc= the rows whose `ack` is 0).
+        Returns the bits, int32 [n, 2N] (a view of `bits`), ready for work queued on `stream`
+        afterwards; with crc=, `ack[:n]` is their frame check."""
         import torch
         t = int(t)
         if not 0 <= t < self.max_tx:
@@ -481,6 +533,10 @@ class HarqPipeline:
                 row_of = self.row_of[:n]
                 with torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream(c.device)):
                     torch.where(active != 0, self._iota[:n], self._none[:n], out=row_of)
+            elif self.crc is not None:   # the rows the previous call's frame check failed
+                row_of = self.row_of[:n]
+                with torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream(c.device)):
+                    torch.where(self.ack[:n] == 0, self._iota[:n], self._none[:n], out=row_of)
             llr = self.llr[:n * S * self.bps].view(n, S * self.bps)
             # (a numpy float64 scalar: the division's dtype of transmission 0's plane demapper)
             D.compute_llr_device(syms, self.mod, nve if isinstance(nve, torch.Tensor) else np.float64(noise_var),
@@ -489,4 +545,7 @@ class HarqPipeline:
         bits = self.bits[:n]
         es = {"n_iter": self.n_iter[:n]} if self.early_stop else {}
         self.mother.decode_planes_device(self.planes, n, bits, stream=stream, **es)
+        if self.crc is not None:
+            from . import crc as CRC
+            CRC.check_device(bits, self.crc, ok=self.ack[:n], stream=stream)
         return bits
