@@ -150,6 +150,32 @@ def _declare_crc(L):
             f.argtypes, f.restype = argtypes[name], i
 
 
+# every symbol include/llrq.h declares (quantised channel LLRs): built into
+# libtdec.so, kept apart as HARQ_EXPORTS is
+LLRQ_EXPORTS = ("llrq_quantize_dev", "llrq_depuncture_dev", "llrq_depuncture_acc_dev", "llrq_decode_dev",
+                "llrq_decode_batch")
+LLRQ_KINDS = {"int8": 0, "f16": 1}              # the header's LLRQ_INT8 / LLRQ_F16
+LLRQ_MODES = {None: 0, "frame": 1, "tile": 2, "refill": 3}   # LLRQ_DEC_*: fixed iterations, or early stop by es_decoder
+LLRQ_DEFAULT_STEP = np.float32(30 / 127)        # compute_llr clips to +-30
+
+
+def _declare_llrq(L):
+    """argtypes and restype of include/llrq.h's exports; a library that lacks them (an older
+    build loaded by the A/B tools) is left as it is, and a call then fails by name."""
+    i, l, f, p = C.c_int, C.c_long, C.c_float, _vp
+    argtypes = {
+        "llrq_quantize_dev": [i, p, i, l, f, p, p, p],
+        "llrq_depuncture_dev": [p, i, p, i, f, l, p, p],
+        "llrq_depuncture_acc_dev": [p, i, p, i, f, l, i, p, p, p],
+        "llrq_decode_dev": [p, i, i, p, i, f, l, p, p, p, p],
+        "llrq_decode_batch": [p, i, p, i, f, l, p, p],
+    }
+    for name in LLRQ_EXPORTS:
+        if hasattr(L, name):
+            fn = getattr(L, name)
+            fn.argtypes, fn.restype = argtypes[name], i
+
+
 def lib():
     """Load libtdec.so (building it first if this is a build tree without it)."""
     global _lib
@@ -163,6 +189,7 @@ def lib():
                 _declare(L)
                 _declare_harq(L)
                 _declare_crc(L)
+                _declare_llrq(L)
                 _lib = L
     return _lib
 

@@ -53,6 +53,11 @@ check drive the retransmissions (a row is sent again while it fails) in place of
 (--ack genie, the default, which then compares with the info bits that carry the check field);
 the two can differ only on undetected rows.  The rate loss of the check field is not charged to
 Eb/N0, as for pilots.
+
+--llr int8 | f16 puts a soft-bit link between demapper and decoder: the flat
+demapper's LLRs are narrowed to int8 (demap.quantize_llr_device with --llr-step, default
+float32(30 / 127)) or float16 and widened again by the de-puncture kernel.  --llr f32 (default)
+is the plane demapper as before and leaves the sweep configuration as it was.
 """
 from __future__ import annotations
 
@@ -104,9 +109,22 @@ def sweep_config(a, inv_perm=None):
         cfg["crc"] = a.crc
     if getattr(a, "ack", None):   # (absent unless given, likewise)
         cfg["ack"] = a.ack
+    if getattr(a, "llr", "f32") != "f32":   # (absent at the default, likewise)
+        cfg["llr"] = a.llr
+        cfg["llr_step"] = llr_step_of(a)
     if inv_perm is not None:
         cfg["inv_perm_digest"] = interleaver_digest(inv_perm)
     return cfg
+
+
+def llr_step_of(a):
+    """The step of the sweep's --llr link as the configuration records it: the float32 value int8
+    rows are widened with (--llr-step, default float32(30 / 127)), 1.0 for f16 (it has none)."""
+    from ._native import LLRQ_DEFAULT_STEP
+    if a.llr != "int8":
+        return 1.0
+    step = getattr(a, "llr_step", None)
+    return float(LLRQ_DEFAULT_STEP if step is None else np.float32(step))
 
 
 def channel_fading(a):
@@ -333,6 +351,12 @@ def arg_parser():
     ap.add_argument("--ack", choices=["genie", "crc"], default=None,
                     help="--harq: what asks for a retransmission -- the comparison with the known info bits "
                          "(genie, the default), or the frame check of --crc on the decoded bits (crc)")
+    ap.add_argument("--llr", choices=["f32", "int8", "f16"], default="f32",
+                    help="the soft-bit link between demapper and decoder (DESIGN.md §17): f32 (the plane demapper, "
+                         "no link), or the flat demapper's LLRs narrowed to int8 (--llr-step) or float16 and widened "
+                         "by the de-puncture kernel")
+    ap.add_argument("--llr-step", type=float, default=None,
+                    help="--llr int8: the LLR value of one quantiser step (default 30 / 127 as float32)")
     ap.add_argument("--out", default=None)
     ap.add_argument("--dist-backend", default="nccl", help="nccl (= RCCL) on the node; gloo to rehearse")
     ap.add_argument("--all-on-device0", action="store_true", help="every rank on GPU 0 (rehearsal on a 1-GPU box)")
@@ -363,6 +387,8 @@ def main(argv=None):
         ap.error("--rx-branches must be 1 .. 8")
     if a.rx_branches > 1 and a.channel == "awgn":
         ap.error("--rx-branches needs --channel rayleigh or rician")
+    if a.llr_step is not None and (a.llr != "int8" or not 0.0 < a.llr_step < float("inf")):
+        ap.error("--llr-step goes with --llr int8 and must be a finite value > 0")
     fading = channel_fading(a)
     pilots = None
     if a.csi == "pilots":
@@ -412,12 +438,14 @@ def main(argv=None):
         codecs = [codec if r == 0 else M.DVBRCS2_Turbo(a.n, a.rate, a.iterations, rv=r, **kw) for r in versions]
         mother = codec if a.harq == "chase" else M.DVBRCS2_Turbo(a.n, "1/3", a.iterations, early_stop=a.early_stop,
                                                                  es_decoder=a.es_decoder, **kw)
-        pipe = HarqPipeline(codecs, mother, a.mod, a.batch, device, demap=a.demap, max_tx=a.max_tx, crc=a.crc)
+        pipe = HarqPipeline(codecs, mother, a.mod, a.batch, device, demap=a.demap, max_tx=a.max_tx, crc=a.crc,
+                            llr=a.llr, llr_step=a.llr_step)
         run_point_harq(pipe, a.mod, 2.0, 0, min(a.batch, 65536), a.batch, a.seed, device,
                        torch.zeros(a.max_tx + 1, dtype=torch.int64, device=device), fading=fading, crc=a.crc,
                        ack=a.ack or "genie")
     else:
-        pipe = DevicePipeline(codec, a.mod, a.batch, device, demap=a.demap, csi=fading is not None)
+        pipe = DevicePipeline(codec, a.mod, a.batch, device, demap=a.demap, csi=fading is not None, llr=a.llr,
+                              llr_step=a.llr_step)
         # one untimed batch first: code-object loading and first-launch costs stay out of
         # the first point's figures
         run_point(pipe, codec, a.mod, 2.0, 0, min(a.batch, 65536), a.batch, a.seed, device, fading=fading,
@@ -456,6 +484,8 @@ def main(argv=None):
                "decode_codewords_per_s": count / max(1e-9, sum(t[1] for t in times) * 1e-3)}
         if a.demap != "max-log":
             rec["demap"] = a.demap
+        if a.llr != "f32":
+            rec.update(llr=a.llr, llr_step=llr_step_of(a))
         if fading is not None:
             rec.update(channel=a.channel, rician_k=fading["K"], coherence=fading["coh"])
             if "branches" in fading:

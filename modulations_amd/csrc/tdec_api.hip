@@ -6,8 +6,8 @@
 //
 // One translation unit: the kernel files, the kernel-order manifest, the handle and the
 // decoder's entry points here, the soft demapper's host code in tdec_demap_api.hip, then
-// the self-tests, the workload generators, hybrid ARQ's host code (tdec_harq.hip) and the
-// frame check's (tdec_crc_api.hip).
+// the self-tests, the workload generators, hybrid ARQ's host code (tdec_harq.hip), the
+// frame check's (tdec_crc_api.hip) and the quantised LLRs' (tdec_llrq_api.hip).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -28,6 +28,7 @@
 #include "tdec_lowlat.hip"
 #include "tdec_frame.hip"
 #include "tdec_crc.hip"
+#include "tdec_llrq.hip"
 
 using namespace tdec;
 
@@ -76,6 +77,8 @@ namespace {
     (void)k_workload_faded<BranchArgs>, (void)k_workload_frame_branches<false>, (void)k_workload_frame_branches<true>;
     (void)k_depuncture_acc<true>, (void)k_depuncture_acc<false>, (void)k_workload_faded<TxArgs>;   // HARQ (§15)
     (void)k_crc<int32_t, false>, (void)k_crc<uint8_t, false>, (void)k_crc<uint8_t, true>;         // frame check (§16)
+    (void)k_depuncture_q<Q_INT8>, (void)k_depuncture_q<Q_F16>, (void)k_depuncture_acc_q<Q_INT8>,
+        (void)k_depuncture_acc_q<Q_F16>, (void)k_llr_quantize<true>, (void)k_llr_quantize<false>;  // quantised LLRs (§17)
 }
 #undef EACH_BPS
 #undef BOTH
@@ -1187,9 +1190,12 @@ static int ensure_es(tdec_t *h, int B) {
 // The body of the three tdec_decode_batch*_dev: de-puncture into the handle's own planes, then the mode's
 // tdec_decode_planes*_dev.  The tile modes take the batch whole and refuse one above tdec_reserve(); the early-stop
 // frame mode walks it in chunks of es_rows() and sizes the planes for one chunk on first use, like its workspace.
+// depuncture(n, r0, planes) fills the planes from rows r0 .. r0 + n - 1: tdec_depuncture_dev here, the narrow rows'
+// llrq_depuncture_dev in tdec_llrq_api.hip.
 enum DecodeMode { DEC_PLAIN, DEC_ES_FRAME, DEC_ES_TILE, DEC_ES_REFILL };
-static int decode_batch_dev(tdec_t *h, DecodeMode mode, int B, const float *d_llr, long llr_stride, int32_t *d_bits,
-                            double *d_lfinal, int32_t *d_n_iter, void *stream) {
+template <typename Depuncture>
+static int decode_batch_dev(tdec_t *h, DecodeMode mode, int B, int32_t *d_bits, double *d_lfinal, int32_t *d_n_iter,
+                            void *stream, Depuncture depuncture) {
     if (mode != DEC_ES_FRAME && B > h->cap_batch) return fail(TDEC_ECAPACITY, "batch larger than tdec_reserve()");
     int C = B;
     if (mode == DEC_ES_FRAME) {
@@ -1207,7 +1213,7 @@ static int decode_batch_dev(tdec_t *h, DecodeMode mode, int B, const float *d_ll
         const int n = (int)std::min<long>(C, B - r0);
         int32_t *bits = d_bits + r0 * 2 * h->N, *n_iter = d_n_iter ? d_n_iter + r0 : nullptr;
         double *lfinal = d_lfinal ? d_lfinal + r0 * 2 * h->N : nullptr;
-        int rc = tdec_depuncture_dev(h, n, d_llr + r0 * llr_stride, llr_stride, planes, stream);
+        int rc = depuncture(n, r0, planes);
         if (!rc && mode == DEC_PLAIN) rc = tdec_decode_planes_dev(h, n, planes, bits, lfinal, stream);
         if (!rc && mode == DEC_ES_FRAME) rc = tdec_decode_planes_es_dev(h, n, planes, bits, lfinal, n_iter, stream);
         if (!rc && mode == DEC_ES_TILE) rc = tdec_decode_planes_es_tile_dev(h, n, planes, bits, lfinal, n_iter, stream);
@@ -1215,6 +1221,12 @@ static int decode_batch_dev(tdec_t *h, DecodeMode mode, int B, const float *d_ll
         if (rc) return rc;
     }
     return 0;
+}
+static int decode_batch_dev(tdec_t *h, DecodeMode mode, int B, const float *d_llr, long llr_stride, int32_t *d_bits,
+                            double *d_lfinal, int32_t *d_n_iter, void *stream) {
+    return decode_batch_dev(h, mode, B, d_bits, d_lfinal, d_n_iter, stream, [=](int n, long r0, float *planes) {
+        return tdec_depuncture_dev(h, n, d_llr + r0 * llr_stride, llr_stride, planes, stream);
+    });
 }
 
 // Zero-copy single calls: a small host-pointer call of at most ZC_MAX_ROWS rows lets the kernels read their
@@ -1225,15 +1237,16 @@ static int decode_batch_dev(tdec_t *h, DecodeMode mode, int B, const float *d_ll
 constexpr int ZC_MAX_ROWS = 64;
 static bool zero_copy(int B) { return B <= ZC_MAX_ROWS; }
 
-// The page-locked staging of a small host-pointer decode: LLR rows, bits, L_final and (early stop) n_iter.
+// The page-locked staging of a small host-pointer decode: LLR rows (of esz-byte elements), bits, L_final and
+// (early stop) n_iter.
 struct Staging {
     size_t in_b, bits_b, lf_b, ni_b, o_bits, o_lf, o_ni, pin_b;
-    Staging(const tdec_t *h, int B, long llr_stride, bool lfinal, bool n_iter)
-        : in_b((size_t)B * llr_stride * sizeof(float)), bits_b((size_t)B * 2 * h->N * sizeof(int32_t)),
+    Staging(const tdec_t *h, int B, long llr_stride, bool lfinal, bool n_iter, size_t esz = sizeof(float))
+        : in_b((size_t)B * llr_stride * esz), bits_b((size_t)B * 2 * h->N * sizeof(int32_t)),
           lf_b(lfinal ? (size_t)B * 2 * h->N * sizeof(double) : 0), ni_b(n_iter ? (size_t)B * sizeof(int32_t) : 0),
           o_bits(up256(in_b)), o_lf(up256(o_bits + bits_b)), o_ni(n_iter ? up256(o_lf + lf_b) : o_lf + lf_b),
           pin_b(o_ni + ni_b) {}
-    void copy_in(char *pin, const float *llr) const { std::memcpy(pin, llr, in_b); }
+    void copy_in(char *pin, const void *llr) const { std::memcpy(pin, llr, in_b); }
     void copy_out(const char *pin, int32_t *bits, double *lfinal, int32_t *n_iter) const {
         std::memcpy(bits, pin + o_bits, bits_b);
         if (lfinal) std::memcpy(lfinal, pin + o_lf, lf_b);
@@ -1523,8 +1536,15 @@ int tdec_es_refill_stats(const tdec_t *h, long *trips, long *refills) {
 // stages every copy through its own pinned buffer on the CPU, which caps the
 // path at the host's staging rate; host buffers from tdec_host_alloc (or
 // registered by the caller) go straight to the DMA engines.
-int tdec_decode_batch(tdec_t *h, int B, const float *llr, long llr_stride, int32_t *bits, double *lfinal) {
-    CHECK_ARGS(h, B, llr, bits, &llr_stride);
+//
+// host_decode_batch is that path for rows of esz-byte elements: tdec_decode_batch's float rows and
+// llrq_decode_batch's narrow ones (tdec_llrq_api.hip) differ in the bytes staged and uploaded and in
+// decode(n, d_rows, d_bits, d_lfinal), which de-punctures n uploaded rows and decodes them on the handle's stream.
+}  // extern "C"
+template <typename Decode>
+static int host_decode_batch(tdec_t *h, int B, const void *llr_, size_t esz, long llr_stride, int32_t *bits,
+                             double *lfinal, Decode decode) {
+    const char *llr = (const char *)llr_;
     Guard g(h->device);
     quiesce(h);   // earlier _dev work on other streams may still use the buffers staged below
     const int C = (int)std::min<long>(B, tile_host_chunk(h));
@@ -1533,7 +1553,7 @@ int tdec_decode_batch(tdec_t *h, int B, const float *llr, long llr_stride, int32
     // 12 KB in and 6 KB out): one page-locked staging buffer, one DMA each way on
     // the handle's stream, no events -- the pageable copies' runtime staging and
     // the pipeline's event setup were most of a per-frame call.
-    const Staging s(h, B, llr_stride, lfinal != nullptr, false);
+    const Staging s(h, B, llr_stride, lfinal != nullptr, false, esz);
     if (n_chunks == 1 && s.pin_b <= SMALL_CALL_BYTES) {
         int rc = tdec_reserve(h, B);
         if (!rc) rc = h->h_llr.ensure(s.in_b);
@@ -1548,13 +1568,10 @@ int tdec_decode_batch(tdec_t *h, int B, const float *llr, long llr_stride, int32
             // zero copy: the de-puncture kernel reads the LLR rows from the page-locked
             // buffer and the frame decoder writes bits / L_final into it
             char *dp = (char *)h->pin.dev;
-            rc = tdec_decode_batch_dev(h, B, (const float *)dp, llr_stride, (int32_t *)(dp + s.o_bits),
-                                       lfinal ? (double *)(dp + s.o_lf) : nullptr, h->stream);
+            rc = decode(B, dp, (int32_t *)(dp + s.o_bits), lfinal ? (double *)(dp + s.o_lf) : nullptr);
         } else {
             HIPCHK(hipMemcpyAsync(h->h_llr.p, pin, s.in_b, hipMemcpyHostToDevice, h->stream));
-            if ((rc = tdec_decode_batch_dev(h, B, (const float *)h->h_llr.p, llr_stride, (int32_t *)h->h_bits.p,
-                                            lfinal ? (double *)h->h_lf.p : nullptr, h->stream)))
-                return rc;
+            if ((rc = decode(B, h->h_llr.p, (int32_t *)h->h_bits.p, lfinal ? (double *)h->h_lf.p : nullptr))) return rc;
             HIPCHK(hipMemcpyAsync(pin + s.o_bits, h->h_bits.p, s.bits_b, hipMemcpyDeviceToHost, h->stream));
             if (lfinal) HIPCHK(hipMemcpyAsync(pin + s.o_lf, h->h_lf.p, s.lf_b, hipMemcpyDeviceToHost, h->stream));
         }
@@ -1563,8 +1580,8 @@ int tdec_decode_batch(tdec_t *h, int B, const float *llr, long llr_stride, int32
     }
     const int nbuf = n_chunks > 1 ? 2 : 1;
     int rc = tdec_reserve(h, C);
-    const size_t row_b = (size_t)2 * h->N, llr_c = (size_t)C * llr_stride, bits_c = (size_t)C * row_b;
-    if (!rc) rc = h->h_llr.ensure(nbuf * llr_c * sizeof(float));
+    const size_t row_b = (size_t)2 * h->N, llr_c = (size_t)C * llr_stride * esz, bits_c = (size_t)C * row_b;
+    if (!rc) rc = h->h_llr.ensure(nbuf * llr_c);
     if (!rc) rc = h->h_bits.ensure(nbuf * bits_c * sizeof(int32_t));
     if (!rc && lfinal) rc = h->h_lf.ensure(nbuf * bits_c * sizeof(double));
     if (rc) return rc;
@@ -1575,7 +1592,7 @@ int tdec_decode_batch(tdec_t *h, int B, const float *llr, long llr_stride, int32
     // declared after the events, so it is destroyed (drains the streams) before they are
     DrainOnExit drain{h->stream, us != h->stream ? us : nullptr, ds != h->stream ? ds : nullptr};
     if ((rc = up.create()) || (rc = dec.create()) || (rc = down.create())) return rc;
-    float *dl = (float *)h->h_llr.p;
+    char *dl = (char *)h->h_llr.p;   // llr_c bytes per buffer
     int32_t *db = (int32_t *)h->h_bits.p;
     double *df = lfinal ? (double *)h->h_lf.p : nullptr;
     auto rows = [&](long i) { return (int)std::min<long>(C, B - i * C); };
@@ -1587,14 +1604,12 @@ int tdec_decode_batch(tdec_t *h, int B, const float *llr, long llr_stride, int32
     auto stage = [&](long i) -> int {
         const int k = (int)(i % nbuf), n = rows(i);
         if (i >= 2) HIPCHK(hipStreamWaitEvent(us, dec.e[k], 0));
-        HIPCHK(hipMemcpyAsync(dl + k * llr_c, llr + i * C * llr_stride, (size_t)n * llr_stride * sizeof(float),
+        HIPCHK(hipMemcpyAsync(dl + k * llr_c, llr + i * C * llr_stride * esz, (size_t)n * llr_stride * esz,
                               hipMemcpyHostToDevice, us));
         HIPCHK(hipEventRecord(up.e[k], us));
         HIPCHK(hipStreamWaitEvent(h->stream, up.e[k], 0));
         if (i >= 2) HIPCHK(hipStreamWaitEvent(h->stream, down.e[k], 0));
-        if (int r = tdec_decode_batch_dev(h, n, dl + k * llr_c, llr_stride, db + k * bits_c,
-                                          df ? df + k * bits_c : nullptr, h->stream))
-            return r;
+        if (int r = decode(n, dl + k * llr_c, db + k * bits_c, df ? df + k * bits_c : nullptr)) return r;
         HIPCHK(hipEventRecord(dec.e[k], h->stream));
         return 0;
     };
@@ -1614,6 +1629,15 @@ int tdec_decode_batch(tdec_t *h, int B, const float *llr, long llr_stride, int32
     HIPCHK(hipStreamSynchronize(us));
     HIPCHK(hipStreamSynchronize(h->stream));
     return 0;
+}
+extern "C" {
+
+int tdec_decode_batch(tdec_t *h, int B, const float *llr, long llr_stride, int32_t *bits, double *lfinal) {
+    CHECK_ARGS(h, B, llr, bits, &llr_stride);
+    return host_decode_batch(h, B, llr, sizeof(float), llr_stride, bits, lfinal,
+                             [=](int n, const void *d_llr, int32_t *d_bits, double *d_lf) {
+                                 return tdec_decode_batch_dev(h, n, (const float *)d_llr, llr_stride, d_bits, d_lf, h->stream);
+                             });
 }
 
 // tdec_decode_batch with early stop.  Up to ZC_MAX_ROWS rows take tdec_decode_batch's
@@ -2167,3 +2191,6 @@ int tdec_encode_dev(tdec_t *h, int B, const uint8_t *d_bits, uint8_t *d_coded, v
 
 // ---- frame check: CRC attach and verify, the generator with the caller's info bits (§16) ----
 #include "tdec_crc_api.hip"
+
+// ---- quantised channel LLRs (include/llrq.h) ---------------------------------------------
+#include "tdec_llrq_api.hip"

@@ -339,6 +339,44 @@ def compute_llr_device(syms, mod_type, noise_var, out=None, sign=+1, stream=None
     return out
 
 
+# ---- quantised LLRs ----------------------------------------------
+LLR_DEFAULT_STEP = _n.LLRQ_DEFAULT_STEP               # float32(30 / 127): compute_llr clips to +-30
+
+
+def quantize_llr_device(llr, step=LLR_DEFAULT_STEP, out=None, count_saturated=False, stream=None):
+    """int8 soft bits of a float32 or float64 device tensor of LLRs (llrq_quantize_dev,
+    include/llrq.h): q = clamp(rint(float32(x) * inv_step), -127, 127), ties to even, with
+    inv_step = float32(1) / float32(step) formed here; NaN -> 0, +-inf -> +-127.  Any shape and
+    any view whose elements are contiguous (a sliced base needs no alignment); the result has
+    the input's shape.  The decoder widens q as float32(q) * step (decode_device(llr_step=step)).
+    count_saturated: an int64 [1] device tensor to ADD the number of elements with
+    |x * inv_step| > 127 to, or True for a fresh one; the result is then (q, counter)."""
+    import torch
+    if not isinstance(llr, torch.Tensor) or llr.dtype not in (torch.float32, torch.float64):
+        raise TypeError(f"llr must be a float32 or float64 tensor, got {getattr(llr, 'dtype', type(llr))}")
+    if llr.device.type != "cuda" or not llr.is_contiguous():
+        raise ValueError("llr must be a contiguous tensor on a HIP device")
+    step = np.float32(step)
+    if not np.isfinite(step) or step <= 0:
+        raise ValueError("step must be finite and > 0")
+    inv_step = np.float32(1) / step
+    if not np.isfinite(inv_step):
+        raise ValueError("1 / step must be finite in float32")
+    out = _out_tensor(out, llr, llr.shape, torch.int8, "out")
+    sat = None
+    if count_saturated is True:
+        sat = torch.zeros(1, dtype=torch.int64, device=llr.device)
+    elif count_saturated is not False and count_saturated is not None:
+        sat = count_saturated
+        if (not isinstance(sat, torch.Tensor) or sat.dtype != torch.int64 or sat.numel() != 1
+                or sat.device != llr.device):
+            raise ValueError("count_saturated must be True or an int64 [1] tensor on the input's device")
+    dev = llr.device.index or 0
+    _n.check(_n.lib().llrq_quantize_dev(dev, _n.ptr(llr), int(llr.dtype == torch.float64), llr.numel(), inv_step,
+                                        _n.ptr(out), _n.ptr(sat), _stream_of(dev, stream)))
+    return (out, sat) if sat is not None else out
+
+
 # ---- pilot-aided channel estimation (DESIGN.md section 13) ------------------------------
 CSI_MODES = {"linear": 0, "mean": 1}
 CSI_MAX_BLOCKS = 2048                                 # pilot blocks per burst the estimator's LDS holds

@@ -128,6 +128,38 @@ def _default_device():
     return 0
 
 
+def llr_step_arg(kind, llr_step):
+    """The float32 step a narrow LLR row of `kind` ('int8', 'f16') is widened with (include/llrq.h):
+    int8 takes llr_step, by default float32(30 / 127); float16 takes none (TypeError)."""
+    if kind == "f16":
+        if llr_step is not None:
+            raise TypeError("llr_step applies to int8 LLRs only (a float16 LLR stands for itself)")
+        return np.float32(1)
+    step = _n.LLRQ_DEFAULT_STEP if llr_step is None else np.float32(llr_step)
+    if not np.isfinite(step) or step <= 0:
+        raise ValueError("llr_step must be finite and > 0")
+    return step
+
+
+def _narrow_kind(dtype, llr_step, wide):
+    """'int8' / 'f16' for a narrow LLR dtype (numpy or torch), None for one of `wide`; TypeError otherwise
+    (uint8, int16, bfloat16, ...) and for llr_step with anything but int8."""
+    name = str(dtype).replace("torch.", "")
+    if name in wide:
+        if llr_step is not None:
+            raise TypeError("llr_step applies to int8 LLRs only")
+        return None
+    kind = {"int8": "int8", "float16": "f16"}.get(name)
+    if kind is None:
+        raise TypeError(f"llr must be {', '.join(wide)}, int8 or float16, got {name}")
+    return kind
+
+
+# numpy dtypes decode_batch takes for quantised soft bits or refuses as such; every other dtype is converted
+# to float32 LLR values as the reference converts it
+_NARROW_NUMPY = (np.dtype(np.int8), np.dtype(np.float16), np.dtype(np.uint8), np.dtype(np.int16))
+
+
 class DVBRCS2_Turbo:
     """DVB-RCS2 duo-binary turbo codec (reference :287-537), decode on MI355X.
 
@@ -258,20 +290,62 @@ class DVBRCS2_Turbo:
                    + p["Y2"][i % p["period"]] for i in range(self.N))
 
     # -- decode (:464-537) -----------------------------------------------------------
-    def decode(self, llr):
-        """Decode one codeword's LLRs (LLR = log P(0)/P(1)) into int32[2N] info bits."""
-        llr = np.array(llr, dtype=np.float32)
+    def decode(self, llr, llr_step=None):
+        """Decode one codeword's LLRs (LLR = log P(0)/P(1)) into int32[2N] info bits.
+        An int8 or float16 numpy vector is taken as quantised LLRs (decode_batch)."""
+        if isinstance(llr, np.ndarray) and llr.dtype in _NARROW_NUMPY:
+            llr = np.array(llr)                      # (decode_batch takes int8 / float16 and refuses uint8 / int16)
+        else:
+            if llr_step is not None:
+                raise TypeError("llr_step applies to int8 LLRs only")
+            llr = np.array(llr, dtype=np.float32)
         if llr.ndim != 1:
             raise ValueError("decode() takes one codeword; use decode_batch for [B, n] input")
-        return self.decode_batch(llr[None, :])[0]
+        return self.decode_batch(llr[None, :], llr_step=llr_step)[0]
 
-    def decode_batch(self, llr, return_lfinal=False, out=None, return_iters=False):
+    def _decode_batch_narrow(self, llr, kind, llr_step, return_lfinal, out):
+        """decode_batch of an int8 / float16 numpy array: llrq_decode_batch uploads the narrow rows
+        and widens them on the device.  Fixed iterations only."""
+        if self.early_stop:
+            raise ValueError("int8 / float16 host arrays decode with fixed iterations; early_stop codecs take them "
+                             "through decode_device")
+        step = llr_step_arg(kind, llr_step)
+        llr = np.ascontiguousarray(llr)
+        if llr.ndim != 2:
+            raise ValueError("decode_batch takes a [B, n] array")
+        h = self.handle
+        if llr.shape[1] < h.llr_len:
+            raise IndexError(f"index {llr.shape[1]} is out of bounds for axis 0 with size {llr.shape[1]}")
+        B = llr.shape[0]
+        if out is not None:
+            if out.dtype != np.int32 or out.shape != (B, self.k_info) or not out.flags.c_contiguous:
+                raise ValueError("out must be a C-contiguous int32 [B, 2N] array")
+            bits = out
+        else:
+            bits = np.zeros((B, self.k_info), np.int32)
+        lf = np.zeros((B, self.k_info)) if return_lfinal else None
+        if B:
+            h.call("llrq_decode_batch", B, _n.ptr(llr), _n.LLRQ_KINDS[kind], step, llr.shape[1], _n.ptr(bits), _n.ptr(lf))
+        return bits, lf
+
+    def decode_batch(self, llr, return_lfinal=False, out=None, return_iters=False, llr_step=None):
         """Decode B codewords: llr [B, >= n_llr] -> int32 [B, 2N]
         (and L_final f64 [B, 2N] = Lc + La + Le1, :529-530, when asked).
         out: optional C-contiguous int32 [B, 2N] array for the bits (e.g. a
         host_buffer(), which the copies reach without runtime staging).
         return_iters: append the int32 [B] iterations run per codeword (with
-        early_stop; `iterations` for every row without)."""
+        early_stop; `iterations` for every row without).
+        An int8 or float16 numpy array is taken as quantised LLRs (include/llrq.h): int8 q
+        stands for float32(q) * llr_step (default float32(30 / 127)), float16 for itself;
+        the narrow rows are what crosses to the device.  Other narrow dtypes: TypeError."""
+        if isinstance(llr, np.ndarray) and llr.dtype in _NARROW_NUMPY:
+            kind = _narrow_kind(llr.dtype, llr_step, ())   # (uint8 and int16 are refused, not read as LLR values)
+            bits, lf = self._decode_batch_narrow(llr, kind, llr_step, return_lfinal, out)
+            iters = np.full(bits.shape[0], self.iterations, np.int32) if return_iters else None
+            res = (bits,) + ((lf,) if return_lfinal else ()) + ((iters,) if return_iters else ())
+            return res if len(res) > 1 else bits
+        if llr_step is not None:
+            raise TypeError("llr_step applies to int8 LLRs only")
         llr = np.ascontiguousarray(np.asarray(llr, dtype=np.float32))
         if llr.ndim != 2:
             raise ValueError("decode_batch takes a [B, n] array")
@@ -361,12 +435,27 @@ class DVBRCS2_Turbo:
                 raise ValueError("n_iter is filled by early_stop=True codecs only")
             self._dev_check(n_iter, "n_iter", torch.int32, (B,))
 
-    def decode_device(self, llr, bits=None, lfinal=None, stream=None, n_iter=None):
+    @staticmethod
+    def _llr_kind(llr, llr_step):
+        """'int8' / 'f16' for a tensor of quantised LLRs, None for anything else (which the caller's own
+        dtype check then accepts or refuses as it always has); TypeError for llr_step without int8."""
+        import torch
+        kind = {torch.int8: "int8", torch.float16: "f16"}.get(getattr(llr, "dtype", None)) \
+            if isinstance(llr, torch.Tensor) else None
+        if llr_step is not None and kind != "int8":
+            raise TypeError("llr_step applies to int8 LLRs only (a float16 LLR stands for itself)")
+        return kind
+
+    def decode_device(self, llr, bits=None, lfinal=None, stream=None, n_iter=None, llr_step=None):
         """llr: float32 [B, n] device tensor (rows contiguous) -> int32 [B, 2N] device tensor.
         Stream-ordered on `stream` (default: torch's current stream).
-        n_iter (early_stop codecs): int32 [B] device tensor for the iterations run."""
+        n_iter (early_stop codecs): int32 [B] device tensor for the iterations run.
+        An int8 or float16 tensor is taken as quantised LLRs: de-punctured into the
+        handle's planes by llrq_depuncture_dev (int8 q is float32(q) * llr_step, default
+        float32(30 / 127); float16 stands for itself), then decoded as decode_planes_device decodes."""
         import torch
-        self._dev_check(llr, "llr", torch.float32, rows_contig=True)
+        kind = self._llr_kind(llr, llr_step)
+        self._dev_check(llr, "llr", llr.dtype if kind else torch.float32, rows_contig=True)
         B = llr.shape[0]
         if B and llr.shape[1] < self.handle.llr_len:
             raise IndexError(f"index {llr.shape[1]} is out of bounds for axis 0 with size {llr.shape[1]}")
@@ -380,6 +469,12 @@ class DVBRCS2_Turbo:
         self._dev_check(bits, "bits", torch.int32, (B, self.k_info))
         if lfinal is not None:
             self._dev_check(lfinal, "lfinal", torch.float64, (B, self.k_info))
+        if kind is not None:
+            self.handle.call("llrq_decode_dev", _n.LLRQ_MODES[self.es_decoder if self.early_stop else None], B,
+                             _n.ptr(llr), _n.LLRQ_KINDS[kind], llr_step_arg(kind, llr_step),
+                             llr.stride(0) if B > 1 else llr.shape[1], _n.ptr(bits), _n.ptr(lfinal), _n.ptr(n_iter),
+                             self._stream(stream))
+            return bits
         if self.early_stop:
             self.handle.call(_ES_CALLS[self.es_decoder][1], B, _n.ptr(llr), llr.stride(0) if B > 1 else llr.shape[1],
                              _n.ptr(bits), _n.ptr(lfinal), _n.ptr(n_iter), self._stream(stream))
@@ -406,27 +501,40 @@ class DVBRCS2_Turbo:
                          self._stream(stream))
         return bits
 
-    def depuncture_device(self, llr, planes, stream=None):
+    def depuncture_device(self, llr, planes, stream=None, llr_step=None):
+        """llr rows -> planes.  llr: float32, or quantised int8 / float16 (llr_step: decode_device)."""
         import torch
-        self._dev_check(llr, "llr", torch.float32, rows_contig=True)
+        kind = self._llr_kind(llr, llr_step)
+        self._dev_check(llr, "llr", llr.dtype if kind else torch.float32, rows_contig=True)
         self._dev_check(planes, "planes", torch.float32)
         if planes.numel() * 4 < self.planes_bytes(llr.shape[0]):
             raise ValueError("planes buffer smaller than planes_bytes(B)")
+        if kind is not None:
+            self.handle.call("llrq_depuncture_dev", llr.shape[0], _n.ptr(llr), _n.LLRQ_KINDS[kind],
+                             llr_step_arg(kind, llr_step), llr.stride(0) if llr.shape[0] > 1 else llr.shape[1],
+                             _n.ptr(planes), self._stream(stream))
+            return planes
         self.handle.call("tdec_depuncture_dev", llr.shape[0], _n.ptr(llr),
                          llr.stride(0) if llr.shape[0] > 1 else llr.shape[1], _n.ptr(planes), self._stream(stream))
         return planes
 
-    def depuncture_accumulate_device(self, llr, planes, B, row_of=None, stream=None):
+    def depuncture_accumulate_device(self, llr, planes, B, row_of=None, stream=None, llr_step=None, f16=False):
         """planes += this codec's de-puncture of `llr` (hybrid ARQ soft combining, DESIGN.md §15;
         harq_depuncture_acc_dev): plane slot c of the B slots takes row row_of[c] of llr, a
         float32 or float64 [n_rows, >= llr_len] device tensor with contiguous rows (float64 values
         are rounded to float32 first).  row_of: int32 [B] device tensor; an entry outside
         [0, n_rows), -1 by convention, leaves the slot untouched; None: row c, n_rows == B.
         What the pattern does not transmit keeps its bits.  `planes` may have been written
-        by any codec of the same N, and is read by the decoder of any."""
+        by any codec of the same N, and is read by the decoder of any.
+        llr may also be quantised rows (llrq_depuncture_acc_dev): int8 (llr_step: decode_device), or
+        float16 when f16=True says so -- without it a float16 tensor stays the TypeError it has been
+        here since §15, where a half tensor could only be a float32 one converted by mistake."""
         import torch
-        if not isinstance(llr, torch.Tensor) or llr.dtype not in (torch.float32, torch.float64):
-            raise TypeError("llr must be a float32 or float64 tensor")
+        kind = self._llr_kind(llr, llr_step)
+        if kind == "f16" and not f16:
+            raise TypeError("llr must be a float32, float64 or int8 tensor (float16 soft bits: f16=True)")
+        if not isinstance(llr, torch.Tensor) or (kind is None and llr.dtype not in (torch.float32, torch.float64)):
+            raise TypeError("llr must be a float32, float64, int8 or float16 tensor")
         self._dev_check(llr, "llr", llr.dtype, rows_contig=True)
         self._dev_check(planes, "planes", torch.float32)
         B = int(B)
@@ -441,6 +549,11 @@ class DVBRCS2_Turbo:
             self._dev_check(row_of, "row_of", torch.int32, (B,))
         elif n_rows != B:
             raise ValueError(f"without row_of every slot takes its own row: llr must have {B} rows, got {n_rows}")
+        if kind is not None:
+            self.handle.call("llrq_depuncture_acc_dev", B, _n.ptr(llr), _n.LLRQ_KINDS[kind],
+                             llr_step_arg(kind, llr_step), llr.stride(0) if n_rows > 1 else llr.shape[1], n_rows,
+                             _n.ptr(row_of), _n.ptr(planes), self._stream(stream))
+            return planes
         self.handle.call("harq_depuncture_acc_dev", B, _n.ptr(llr), int(llr.dtype == torch.float64),
                          llr.stride(0) if n_rows > 1 else llr.shape[1], n_rows, _n.ptr(row_of), _n.ptr(planes),
                          self._stream(stream))

@@ -223,11 +223,23 @@ class DevicePipeline:
     Receive diversity: 3-D symbols [B, R, S] with csi [B, R, nh] go through
     the maximal-ratio combiner (demap.combine_device) in place of the equaliser, 3-D frames
     [B, R, T] through the pilot strip on all B * R rows and then the combiner; `z` and
-    `nv_sym` are the same buffers, and everything behind them is unchanged."""
+    `nv_sym` are the same buffers, and everything behind them is unchanged.
 
-    def __init__(self, codec, mod, B, device, fused=False, overlap=False, gate=True, demap="max-log", csi=False):
+    llr="int8" | "f16"  models a soft-bit link between demapper and decoder: the
+    flat demapper's LLRs (demap.compute_llr_device, decoder sign) are narrowed -- int8 by
+    demap.quantize_llr_device with llr_step (default float32(30 / 127)), float16 by rounding -- into
+    `llr_q`, and the narrow rows de-punctured into the planes (codec.depuncture_device).  The plane
+    demappers have no flat LLRs: fused=True and overlap=True refuse it, as fused refuses csi.
+    llr="f32" (default) is the pipeline above, unchanged."""
+
+    def __init__(self, codec, mod, B, device, fused=False, overlap=False, gate=True, demap="max-log", csi=False,
+                 llr="f32", llr_step=None):
         import torch
         self.codec, self.mod, self.B = codec, mod, B
+        self.llr_kind, self.llr_step = _llr_link(llr, llr_step)
+        if self.llr_kind is not None and (fused or overlap):
+            raise ValueError(f"llr={llr!r} needs the flat demapper's LLRs: the plane demappers of fused=True and "
+                             "overlap=True have none")
         self.bps = D.MODULATIONS[mod]["bps"]
         self.cons = D.constellation(mod)
         self.demap = demap
@@ -247,6 +259,10 @@ class DevicePipeline:
             self.planes = torch.empty(codec.planes_bytes(B) // 4, dtype=torch.float32, device=device)
         self.bits = torch.empty((B, codec.k_info), dtype=torch.int32, device=device)
         self.n_iter = torch.empty(B, dtype=torch.int32, device=device) if self.early_stop else None
+        self.llr = self.llr_q = None
+        if self.llr_kind is not None:
+            self.llr, self.llr_q = _llr_link_buffers(self.llr_kind, B * -(-codec.handle.enc_len // self.bps) * self.bps,
+                                                     device)
         self.z = self.nv_sym = None
         self._strip = {}                          # run_frames' per-branch buffers, by R (sized on first use)
         if csi:
@@ -411,8 +427,13 @@ class DevicePipeline:
         else:
             if front is not None:
                 syms, nve, div32 = front(stream)
-            self.codec.demap_planes_device(syms, self.cons, self.bps, nve, self.planes, div_f32=div32,
-                                           stream=stream, algo=self.demap)
+            if self.llr_kind is not None:
+                n, L = syms.shape[0], syms.shape[1] * self.bps
+                q = _llr_link_run(self, syms, nve if isinstance(nve, torch.Tensor) else np.float64(noise_var), n, L, stream)
+                self.codec.depuncture_device(q, self.planes, stream=stream, llr_step=self.llr_step)
+            else:
+                self.codec.demap_planes_device(syms, self.cons, self.bps, nve, self.planes, div_f32=div32,
+                                               stream=stream, algo=self.demap)
             if events is not None:
                 events[0].record(stream)
             self.codec.decode_planes_device(self.planes, syms.shape[0], bits, stream=stream, **es)
@@ -428,6 +449,39 @@ class DevicePipeline:
         n = syms.shape[0]
         z, nvs = fn(syms, csi, nv, coh=coh, out=self.z[:n], nv_out=self.nv_sym[:n], stream=stream)
         return z, nvs, self.div_f32_t
+
+
+def _llr_link(llr, llr_step):
+    """(kind, step) of a pipeline's llr= / llr_step= arguments: (None, None) for "f32", else
+    ('int8' | 'f16', the int8 step or None); llr_step with anything but int8 is a TypeError."""
+    from .dvb_rcs2_turbo import llr_step_arg
+    if llr not in ("f32", "int8", "f16"):
+        raise ValueError(f"unknown llr {llr!r} ('f32', 'int8' or 'f16')")
+    if llr != "int8" and llr_step is not None:
+        raise TypeError("llr_step applies to llr='int8' only")
+    if llr == "f32":
+        return None, None
+    return llr, (llr_step_arg(llr, llr_step) if llr == "int8" else None)
+
+
+def _llr_link_buffers(kind, n, device):
+    """The flat demapper's float64 LLRs and their narrow form, n elements each."""
+    import torch
+    return (torch.empty(n, dtype=torch.float64, device=device),
+            torch.empty(n, dtype=torch.int8 if kind == "int8" else torch.float16, device=device))
+
+
+def _llr_link_run(p, syms, nv, n, L, stream):
+    """Flat demap of `syms` (decoder sign) into p.llr, narrowed into p.llr_q: the [n, L] narrow rows."""
+    import torch
+    llr, q = p.llr[:n * L].view(n, L), p.llr_q[:n * L].view(n, L)
+    D.compute_llr_device(syms, p.mod, nv, out=llr, sign=-1, stream=stream, algo=p.demap)
+    if p.llr_kind == "int8":
+        D.quantize_llr_device(llr, p.llr_step, out=q, stream=stream)
+    else:
+        with torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream(syms.device)):
+            q.copy_(llr)   # float64 -> float16, round to nearest even (one rounding)
+    return q
 
 
 class HarqPipeline:
@@ -452,10 +506,15 @@ class HarqPipeline:
     (make_symbols(..., crc=...)).  After every decode the bits are verified on the device into
     `ack` (int32 [B]: 1 = the row passed), and a receive(t > 0) without `active` combines only
     the rows whose ack is 0 from the call before: the retransmission loop runs with no host
-    decision in it.  An explicit `active` still wins.  crc=None: no `ack`, nothing else changes."""
+    decision in it.  An explicit `active` still wins.  crc=None: no `ack`, nothing else changes.
 
-    def __init__(self, codecs, mother, mod, B, device, demap="max-log", max_tx=4, crc=None):
+    llr="int8" | "f16" (llr_step: int8's step): every transmission, the first
+    included, goes through the flat demapper, is narrowed as DevicePipeline narrows it and is
+    de-punctured (t = 0) or combined (t > 0) from the narrow rows."""
+
+    def __init__(self, codecs, mother, mod, B, device, demap="max-log", max_tx=4, crc=None, llr="f32", llr_step=None):
         import torch
+        self.llr_kind, self.llr_step = _llr_link(llr, llr_step)
         codecs = list(codecs)
         if not codecs:
             raise ValueError("HarqPipeline needs at least one transmission codec")
@@ -481,6 +540,9 @@ class HarqPipeline:
         # symbols per codeword of each transmission codec (the versions of one rate differ where N % period != 0)
         self.S = [-(-c.handle.enc_len // self.bps) for c in codecs]
         self.llr = torch.empty(self.B * max(self.S) * self.bps, dtype=torch.float64, device=device)
+        self.llr_q = None
+        if self.llr_kind is not None:
+            self.llr_q = _llr_link_buffers(self.llr_kind, self.llr.numel(), device)[1]
         self.row_of = torch.empty(self.B, dtype=torch.int32, device=device)
         self._iota = torch.arange(self.B, dtype=torch.int32, device=device)
         self._none = torch.full((self.B,), -1, dtype=torch.int32, device=device)
@@ -519,11 +581,16 @@ class HarqPipeline:
             div32, nve = self.div_f32_t, noise_var
         else:
             _, div32, nve = D.demap_mode(np.complex64, self.cons.dtype, np.float64(noise_var))
+        nvf = nve if isinstance(nve, torch.Tensor) else np.float64(noise_var)   # the flat demapper's
         if t == 0:
             if active is not None:
                 raise ValueError("transmission 0 writes every row's planes: it takes no `active`")
-            c.demap_planes_device(syms, self.cons, self.bps, nve, self.planes, div_f32=div32, stream=stream,
-                                  algo=self.demap)
+            if self.llr_kind is not None:
+                c.depuncture_device(_llr_link_run(self, syms, nvf, n, S * self.bps, stream), self.planes, stream=stream,
+                                    llr_step=self.llr_step)
+            else:
+                c.demap_planes_device(syms, self.cons, self.bps, nve, self.planes, div_f32=div32, stream=stream,
+                                      algo=self.demap)
         else:
             row_of = None
             if active is not None:
@@ -537,11 +604,15 @@ class HarqPipeline:
                 row_of = self.row_of[:n]
                 with torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream(c.device)):
                     torch.where(self.ack[:n] == 0, self._iota[:n], self._none[:n], out=row_of)
-            llr = self.llr[:n * S * self.bps].view(n, S * self.bps)
-            # (a numpy float64 scalar: the division's dtype of transmission 0's plane demapper)
-            D.compute_llr_device(syms, self.mod, nve if isinstance(nve, torch.Tensor) else np.float64(noise_var),
-                                 out=llr, sign=-1, stream=stream, algo=self.demap)
-            c.depuncture_accumulate_device(llr, self.planes, n, row_of=row_of, stream=stream)
+            if self.llr_kind is not None:
+                c.depuncture_accumulate_device(_llr_link_run(self, syms, nvf, n, S * self.bps, stream), self.planes, n,
+                                               row_of=row_of, stream=stream, llr_step=self.llr_step,
+                                               f16=self.llr_kind == "f16")
+            else:
+                llr = self.llr[:n * S * self.bps].view(n, S * self.bps)
+                # (a numpy float64 scalar: the division's dtype of transmission 0's plane demapper)
+                D.compute_llr_device(syms, self.mod, nvf, out=llr, sign=-1, stream=stream, algo=self.demap)
+                c.depuncture_accumulate_device(llr, self.planes, n, row_of=row_of, stream=stream)
         bits = self.bits[:n]
         es = {"n_iter": self.n_iter[:n]} if self.early_stop else {}
         self.mother.decode_planes_device(self.planes, n, bits, stream=stream, **es)
