@@ -18,33 +18,13 @@ pytestmark = pytest.mark.gpu
 from oracle import oracle as O  # noqa: E402
 from modulations_amd import demap as D  # noqa: E402
 from modulations_amd import dvb_rcs2_turbo as M  # noqa: E402
+from plane_matrix import adversarial as _adversarial  # noqa: E402
 
 
 @pytest.fixture(scope="module", autouse=True)
 def _gpu():
     if not torch.cuda.is_available():
         pytest.skip("no GPU")
-
-
-def _adversarial(cons, rng, shape):
-    """Noisy points mixed with exact points, bisector ties, near-ties, far / tiny /
-    huge values and NaN / inf, shuffled over the batch."""
-    n = int(np.prod(shape))
-    lv = np.unique(cons.real.astype(np.float64))
-    mids = (lv[:-1] + lv[1:]) / 2
-    k = n // 10
-    parts = [cons[rng.integers(0, len(cons), n - 7 * k)] + 0.2 * (rng.standard_normal(n - 7 * k) +
-                                                                 1j * rng.standard_normal(n - 7 * k)),
-             cons[rng.integers(0, len(cons), k)],
-             rng.choice(mids, k) + 1j * rng.choice(lv, k),
-             rng.choice(mids, k) + 1j * rng.choice(mids, k),
-             np.nextafter(rng.choice(mids, k), 9) + 1j * np.nextafter(rng.choice(mids, k), -9),
-             10 * (rng.standard_normal(k) + 1j * rng.standard_normal(k)),
-             1e-20 * (rng.standard_normal(k) + 1j * rng.standard_normal(k)),
-             rng.choice(np.array([np.nan, np.inf, -np.inf + 1j, 1 + np.nan * 1j, 3e38 + 3e38j]), k)]
-    s = np.concatenate(parts)
-    rng.shuffle(s)
-    return s.reshape(shape).astype(np.complex64)
 
 
 def _check(c, syms, mod, nv, cons=None):
