@@ -176,6 +176,25 @@ def _declare_llrq(L):
             fn.argtypes, fn.restype = argtypes[name], i
 
 
+# every symbol include/stbc.h declares (transmit diversity): built into
+# libtdec.so, kept apart as HARQ_EXPORTS is
+STBC_EXPORTS = ("stbc_combine_dev", "stbc_workload_dev")
+
+
+def _declare_stbc(L):
+    """argtypes and restype of include/stbc.h's exports; a library that lacks them (an older
+    build loaded by the A/B tools) is left as it is, and a call then fails by name."""
+    i, d, p, q, Q = C.c_int, C.c_double, _vp, C.c_int64, C.c_uint64
+    argtypes = {
+        "stbc_combine_dev": [i, p, p, i, i, i, i, d, p, p, p, p, p],
+        "stbc_workload_dev": [p, i, i, q, Q, p, i, i, d, d, i, p, p, p, p],
+    }
+    for name in STBC_EXPORTS:
+        if hasattr(L, name):
+            f = getattr(L, name)
+            f.argtypes, f.restype = argtypes[name], i
+
+
 def lib():
     """Load libtdec.so (building it first if this is a build tree without it)."""
     global _lib
@@ -190,6 +209,7 @@ def lib():
                 _declare_harq(L)
                 _declare_crc(L)
                 _declare_llrq(L)
+                _declare_stbc(L)
                 _lib = L
     return _lib
 

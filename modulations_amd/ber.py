@@ -36,6 +36,12 @@ faded, independently noisy branches and combines them (maximal ratio) in front o
 demapper, with --csi known or pilots.  Eb/N0 is per branch: the array gain (10 log10 R dB
 of collected energy) is not charged, so the curves show it together with the diversity gain.
 
+--tx-antennas 2 (fading channels, --csi known) sends every codeword from two
+antennas with the Alamouti space-time block code and combines the R = --rx-branches branches'
+pairs of slots in front of the demapper; with --llr, --demap and --early-stop as without it.
+--coherence counts slots and must be even.  Eb/N0 is per receive branch at fixed total transmit
+power: the two antennas share it.  Recorded in the sweep configuration only when 2.
+
 --harq chase | ir with --max-tx T sends a codeword again while its decode is
 wrong, up to T transmissions, and soft-combines them (workload.HarqPipeline): chase repeats
 the --rate pattern, ir cycles through its redundancy versions into a rate-1/3 decoder.  The
@@ -103,6 +109,8 @@ def sweep_config(a, inv_perm=None):
                        cfo=float(a.cfo), csi_noise=a.csi_noise)
         if "branches" in fading:   # (absent for one branch, likewise)
             cfg["rx_branches"] = fading["branches"]
+        if "tx_antennas" in fading:   # (absent for one antenna, likewise)
+            cfg["tx_antennas"] = fading["tx_antennas"]
     if getattr(a, "harq", None):   # (absent without the flag, likewise)
         cfg.update(harq=a.harq, max_tx=int(a.max_tx))
     if getattr(a, "crc", None):   # (absent without the flag, likewise)
@@ -136,6 +144,8 @@ def channel_fading(a):
     fading = {"K": float(a.rician_k) if channel == "rician" else 0.0, "coh": int(a.coherence)}
     if int(getattr(a, "rx_branches", 1)) > 1:   # (one branch is the call without the key: the same data)
         fading["branches"] = int(a.rx_branches)
+    if int(getattr(a, "tx_antennas", 1)) == 2:   # (one antenna is the call without the key, likewise)
+        fading["tx_antennas"] = 2
     return fading
 
 
@@ -338,6 +348,10 @@ def arg_parser():
                     help="fading channels: receive branches per burst (1 .. 8), independently faded and noisy, "
                          "maximal-ratio combined in front of the demapper; Eb/N0 is per branch (the array gain "
                          "is not charged)")
+    ap.add_argument("--tx-antennas", type=int, default=1,
+                    help="fading channels, --csi known: transmit antennas (1 or 2).  2 sends every codeword with the "
+                         "Alamouti space-time block code (DESIGN.md §18); --coherence then counts slots and must be "
+                         "even.  Eb/N0 is per receive branch at fixed total transmit power: the antennas share it")
     ap.add_argument("--harq", choices=["chase", "ir"], default=None,
                     help="hybrid ARQ with a genie-aided ACK: resend a codeword while its decode is wrong and "
                          "soft-combine; chase repeats the pattern, ir cycles its redundancy versions into a "
@@ -387,6 +401,15 @@ def main(argv=None):
         ap.error("--rx-branches must be 1 .. 8")
     if a.rx_branches > 1 and a.channel == "awgn":
         ap.error("--rx-branches needs --channel rayleigh or rician")
+    if a.tx_antennas not in (1, 2):
+        ap.error("--tx-antennas must be 1 or 2")
+    if a.tx_antennas == 2:
+        if a.channel == "awgn" or a.csi != "known":
+            ap.error("--tx-antennas 2 needs --channel rayleigh or rician and --csi known")
+        if a.harq or a.crc:
+            ap.error("--tx-antennas 2 takes neither --harq nor --crc")
+        if a.coherence < 2 or a.coherence % 2:
+            ap.error("--tx-antennas 2 needs an even --coherence (a pair of slots shares its gains)")
     if a.llr_step is not None and (a.llr != "int8" or not 0.0 < a.llr_step < float("inf")):
         ap.error("--llr-step goes with --llr int8 and must be a finite value > 0")
     fading = channel_fading(a)
@@ -490,6 +513,8 @@ def main(argv=None):
             rec.update(channel=a.channel, rician_k=fading["K"], coherence=fading["coh"])
             if "branches" in fading:
                 rec["rx_branches"] = fading["branches"]
+            if "tx_antennas" in fading:
+                rec["tx_antennas"] = fading["tx_antennas"]
         if pilots is not None:
             rec.update(csi="pilots", pilot_len=a.pilot_len, pilot_spacing=a.pilot_spacing, cfo=a.cfo,
                        csi_noise=a.csi_noise)

@@ -20,7 +20,8 @@ SRC = os.path.join(HERE, "csrc", "tdec_api.hip")
 # every csrc/tdec_*.hip is part of the one translation unit that tdec_api.hip includes
 DEPS = [*sorted(glob.glob(os.path.join(HERE, "csrc", "tdec_*.hip"))), os.path.join(HERE, "csrc", "npmath.hip"),
         os.path.join(ROOT, "include", "tdec.h"), os.path.join(ROOT, "include", "harq.h"),
-        os.path.join(ROOT, "include", "crc.h"), os.path.join(ROOT, "include", "llrq.h")]
+        os.path.join(ROOT, "include", "crc.h"), os.path.join(ROOT, "include", "llrq.h"),
+        os.path.join(ROOT, "include", "stbc.h")]
 OUT = os.path.join(HERE, "lib", "libtdec.so")
 MODEM_SRC = os.path.join(HERE, "csrc", "modem_api.hip")
 MODEM_DEPS = [MODEM_SRC, os.path.join(HERE, "csrc", "modem_kernels.hip"), os.path.join(HERE, "csrc", "npmath.hip"),

@@ -7,7 +7,8 @@
 // One translation unit: the kernel files, the kernel-order manifest, the handle and the
 // decoder's entry points here, the soft demapper's host code in tdec_demap_api.hip, then
 // the self-tests, the workload generators, hybrid ARQ's host code (tdec_harq.hip), the
-// frame check's (tdec_crc_api.hip) and the quantised LLRs' (tdec_llrq_api.hip).
+// frame check's (tdec_crc_api.hip), the quantised LLRs' (tdec_llrq_api.hip) and transmit
+// diversity's (tdec_stbc_api.hip).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -29,6 +30,7 @@
 #include "tdec_frame.hip"
 #include "tdec_crc.hip"
 #include "tdec_llrq.hip"
+#include "tdec_stbc.hip"
 
 using namespace tdec;
 
@@ -79,6 +81,9 @@ namespace {
     (void)k_crc<int32_t, false>, (void)k_crc<uint8_t, false>, (void)k_crc<uint8_t, true>;         // frame check (§16)
     (void)k_depuncture_q<Q_INT8>, (void)k_depuncture_q<Q_F16>, (void)k_depuncture_acc_q<Q_INT8>,
         (void)k_depuncture_acc_q<Q_F16>, (void)k_llr_quantize<true>, (void)k_llr_quantize<false>;  // quantised LLRs (§17)
+    (void)k_stbc_combine<0, true>, (void)k_stbc_combine<0, false>, (void)k_stbc_combine<1, true>,
+        (void)k_stbc_combine<1, false>, (void)k_stbc_combine<2, true>, (void)k_stbc_combine<2, false>,
+        (void)k_workload_faded<StbcArgs>;                                                          // transmit diversity (§18)
 }
 #undef EACH_BPS
 #undef BOTH
@@ -2194,3 +2199,6 @@ int tdec_encode_dev(tdec_t *h, int B, const uint8_t *d_bits, uint8_t *d_coded, v
 
 // ---- quantised channel LLRs (include/llrq.h) ---------------------------------------------
 #include "tdec_llrq_api.hip"
+
+// ---- transmit diversity: the Alamouti combiner and the generator's 2 x R link (include/stbc.h) ----
+#include "tdec_stbc_api.hip"

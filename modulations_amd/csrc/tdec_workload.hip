@@ -12,6 +12,7 @@
 //   gains       ctr = {cw_lo, cw_hi, gain-block pair, 0x3C5D}, key = seed   (k_workload_fading)
 //   pilot noise ctr = {cw_lo, cw_hi, pilot pair,      0x4D6C}, key = seed   (k_workload_frame)
 //   rotation    ctr = {cw_lo, cw_hi, 0,               0x5E7B}, key = seed   (k_workload_frame)
+//   gains, 2nd  ctr = {cw_lo, cw_hi, gain-block pair, 0x6F8A}, key = seed   (transmit antenna 1)
 // Receive branch b of a codeword draws its noise, gains and pilot noise with
 // b in the upper 16 bits of the domain word (0x2B0E | b << 16, ...): branch 0 is the
 // streams above; the info bits and the rotation are the codeword's, shared by its branches.
@@ -198,6 +199,12 @@ struct BranchArgs : FadeArgs {
 struct TxArgs : FadeArgs {
     int tx, fade;
 };
+// StbcArgs (include/stbc.h): the Alamouti 2 x R link.  syms rows [B][R] of S2 = S + (S & 1)
+// slots, h rows [B][R][2] of nh = ceil(S2 / coh) gains, coh even
+struct StbcArgs : FadeArgs {
+    int R, S2;
+};
+constexpr uint32_t FADE1_DOMAIN = 0x6F8Au;      // antenna 1's gains (antenna 0's: FADE_DOMAIN, the branch generator's)
 __device__ __forceinline__ float2 fade_gain(uint64_t cw, long j, uint64_t seed, const FadeArgs &f,
                                             uint32_t domain = FADE_DOMAIN) {
     const Philox4 r = philox4x32_10(Philox4{(uint32_t)cw, (uint32_t)(cw >> 32), (uint32_t)(j >> 1), domain},
@@ -224,6 +231,45 @@ __device__ __forceinline__ void branch_symbol(const WorkloadArgs &p, const FadeA
     p.syms[row * p.S + s] = make_float2((g.x * x.x - g.y * x.y) + nb.x, (g.x * x.y + g.y * x.x) + nb.y);
 }
 
+// The Alamouti link's flush (StbcArgs): the chunk's pairs (x[2m], x[2m+1]), one per item, consecutive
+// lanes on consecutive pairs of one codeword.  s0 is even (SYM_CHUNK is), and only a codeword's last
+// chunk can have an odd ns: its last pair takes the pad point x[S] = 0.  Per branch b: the two paths'
+// effective gains (the raw draws times sqrt(1/2) per component), written by the first pair of their
+// block (coh is even: a block starts on an even slot), and the two slots
+//   2m:    antenna 0 sends  x[2m],          antenna 1  x[2m+1]
+//   2m+1:  antenna 0 sends -conj(x[2m+1]),  antenna 1  conj(x[2m])
+// each h0 s0 + h1 s1 in the order include/stbc.h states, plus branch b's noise sample of that slot.
+__device__ __forceinline__ float2 stbc_slot(float2 h0, float2 s0, float2 h1, float2 s1, float2 n) {
+    return make_float2(((h0.x * s0.x - h0.y * s0.y) + (h1.x * s1.x - h1.y * s1.y)) + n.x,
+                       ((h0.x * s0.y + h0.y * s0.x) + (h1.x * s1.y + h1.y * s1.x)) + n.y);
+}
+__device__ __forceinline__ void flush_stbc(const WorkloadArgs &p, const StbcArgs &f, long base, uint8_t (*lab)[64],
+                                           const float2 *cons, int ns, long s0, int lane) {
+    const int np = (ns + 1) >> 1;
+    for (int t = lane; t < 64 * np; t += 64) {
+        const int l = t / np, k = 2 * (t - l * np);
+        if (base + l >= p.B) continue;
+        const uint64_t cw = p.cw0 + (uint64_t)(base + l);
+        const float2 x0 = cons[lab[k][l]], x1 = k + 1 < ns ? cons[lab[k + 1][l]] : make_float2(0.0f, 0.0f);
+        const float2 c0 = make_float2(-x1.x, x1.y), c1 = make_float2(x0.x, -x0.y);   // -conj(x1), conj(x0)
+        const long s = s0 + k, j = s / f.coh;
+        for (int b = 0; b < f.R; ++b) {
+            const uint32_t tag = (uint32_t)b << 16;
+            const long row = (base + l) * f.R + b;
+            float2 g0 = fade_gain(cw, j, p.seed, f, FADE_DOMAIN | tag), g1 = fade_gain(cw, j, p.seed, f, FADE1_DOMAIN | tag);
+            g0 = make_float2(g0.x * 0.70710678118654752f, g0.y * 0.70710678118654752f);
+            g1 = make_float2(g1.x * 0.70710678118654752f, g1.y * 0.70710678118654752f);
+            if (s == j * f.coh) {
+                f.h[(row * 2 + 0) * f.nh + j] = g0;
+                f.h[(row * 2 + 1) * f.nh + j] = g1;
+            }
+            float2 *out = p.syms + row * f.S2 + s;   // s + 1 < S2: S2 is even
+            out[0] = stbc_slot(g0, x0, g1, x1, awgn(cw, s, p, NOISE_DOMAIN | tag));
+            out[1] = stbc_slot(g0, c0, g1, c1, awgn(cw, s + 1, p, NOISE_DOMAIN | tag));
+        }
+    }
+}
+
 // Row-order flush of a chunk of symbol labels lab[k][lane] (k < ns): symbols
 // [s0, s0 + ns) of every codeword, table point + AWGN, complex64.  FADE: h x + AWGN, and
 // the first symbol of each gain block writes its gain.  F = BranchArgs: f.R independently faded
@@ -232,6 +278,11 @@ template <bool FADE, typename F>
 __device__ __forceinline__ void flush_syms(const WorkloadArgs &p, const F &f, long base, uint8_t (*lab)[64],
                                            const float2 *cons, int ns, long s0, int lane) {
     __syncthreads();
+    if constexpr (std::is_same<F, StbcArgs>::value) {
+        flush_stbc(p, f, base, lab, cons, ns, s0, lane);
+        __syncthreads();
+        return;
+    }
     for (int t = lane; t < 64 * ns; t += 64) {
         const int l = t / ns, k = t - l * ns;
         if (base + l < p.B) {

@@ -272,6 +272,66 @@ def combine_device(y, h, noise_var, coh=1, out=None, nv_out=None, stream=None):
     return out, nv_out
 
 
+def stbc_coh(coh):
+    """An Alamouti link's gain-block length in slots: an even int >= 2 (a pair never straddles two blocks)."""
+    coh = int(coh)
+    if coh < 2 or coh % 2:
+        raise ValueError(f"transmit diversity needs an even coh >= 2 (a pair of slots shares its gains), got {coh}")
+    return coh
+
+
+def stbc_combine_device(y, h, noise_var, S=None, coh=2, out=None, nv_out=None, stream=None):
+    """Alamouti 2 x R combiner (include/stbc.h): complex64 [B, R, S2]
+    device slots, S2 even, branch r of burst b received from the two transmit antennas through
+    the known effective gains h[b, r, 0] and h[b, r, 1], complex64 [B, R, 2, ceil(S2 / coh)]
+    (E|h|^2 = 1/2 each at fixed total transmit power), -> (z complex64 [B, S], nv_sym float64
+    [B, S]), what equalize_device and combine_device give, stream-ordered.  S: the codeword's
+    symbols, S2 or (an odd S, passed explicitly) S2 - 1: the pad slot's second output is then not
+    written.  noise_var: a scalar, a float64 [B] or a float64 [B, R] device tensor, as
+    combine_device takes it.  A branch whose |h0|^2 + |h1|^2 is zero or not finite is skipped;
+    with none left the pair is an erasure, z = 0 and nv_sym = +inf."""
+    import torch
+    for t, n in ((y, "y"), (h, "h")):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.complex64:
+            raise TypeError(f"{n} must be a torch.complex64 tensor, got {getattr(t, 'dtype', type(t))}")
+    if y.dim() != 3 or y.shape[2] % 2:
+        raise ValueError("y must be a 3-D [B, R, S2] tensor with an even S2 (pairs of slots)")
+    if y.device.type != "cuda" or not y.is_contiguous():
+        raise ValueError("y must be a contiguous 3-D [B, R, S2] tensor on a HIP device")
+    B, R, S2 = y.shape
+    if not 1 <= R <= MAX_BRANCHES:
+        raise ValueError(f"1 .. {MAX_BRANCHES} branches, got {R}")
+    coh = stbc_coh(coh)
+    S = S2 if S is None else int(S)
+    if S < 0 or S not in (S2, S2 - 1):
+        raise ValueError(f"S must be S2 = {S2} or the odd S2 - 1, got {S}")
+    want = (B, R, 2, -(-S2 // coh))
+    if h.dim() != 4 or tuple(h.shape) != want or not h.is_contiguous() or h.device != y.device:
+        raise ValueError(f"h must be a contiguous 4-D tensor of shape {want} on the symbols' device, "
+                         f"got {tuple(h.shape)}")
+    rows = branches = None
+    if isinstance(noise_var, torch.Tensor):
+        if noise_var.dtype != torch.float64:
+            raise TypeError(f"noise_var must be torch.float64, got {noise_var.dtype}")
+        if tuple(noise_var.shape) not in ((B,), (B, R)) or not noise_var.is_contiguous():
+            raise ValueError(f"noise_var must be a contiguous tensor of shape ({B},) or ({B}, {R}), "
+                             f"got {tuple(noise_var.shape)}")
+        if noise_var.device != y.device:
+            raise ValueError("noise_var must be on the symbols' HIP device")
+        if noise_var.dim() == 2:
+            branches = noise_var
+        else:
+            rows = noise_var
+    out = _out_tensor(out, y, (B, S), torch.complex64, "out")
+    nv_out = _out_tensor(nv_out, y, (B, S), torch.float64, "nv_out")
+    dev = y.device.index or 0
+    _n.check(_n.lib().stbc_combine_dev(dev, _n.ptr(y), _n.ptr(h), B, R, S, coh,
+                                       0.0 if isinstance(noise_var, torch.Tensor) else float(noise_var),
+                                       _n.ptr(rows), _n.ptr(branches), _n.ptr(out), _n.ptr(nv_out),
+                                       _stream_of(dev, stream)))
+    return out, nv_out
+
+
 def estimate_noise_var_device(syms, mod_type, floor=0.02, out=None, stream=None):
     """The receiver's decision-directed noise variance (test_sdr_with_coding.py:459-467:
     hard decision, re-map, mean |rx - const|^2, max(nv, 0.02)) of each row of complex64

@@ -58,9 +58,27 @@ def make_symbols(codec, B, mod, ebn0_db, seed, device, cw0=0, want_info=True, fa
     generator encodes those bits (crc_workload_tx_dev): three launches on the codec's stream.
     The returned info bits carry the check field (they are always made; want_info only says
     whether they are returned); noise and gains are those of the same call without crc.  With
-    `tx` and `fading`; neither `pilots` nor "branches".  crc=None (default) is the calls above."""
+    `tx` and `fading`; neither `pilots` nor "branches".  crc=None (default) is the calls above.
+
+    fading={..., "tx_antennas": 2}: the codeword is sent from two antennas with the
+    Alamouti space-time block code (stbc_workload_dev) and received on "branches" (default 1)
+    branches; "coh" counts slots and must be even.  The result is (info, slots complex64
+    [B, R, S2], N0, h complex64 [B, R, 2, ceil(S2 / coh)]), S2 = S + (S & 1), 3-D / 4-D for one
+    branch as well; h holds the effective gains, E|h|^2 = 1/2 each: the two antennas share the
+    transmit power, so ebn0_db is per receive branch at fixed total transmit power.  Neither
+    `pilots`, `tx` nor `crc`.  "tx_antennas" absent or 1 is the calls above."""
     import torch
     from . import _native as _n
+    n_ant = 1 if fading is None else fading.get("tx_antennas", 1)
+    if n_ant not in (1, 2) or isinstance(n_ant, bool):
+        raise ValueError(f"fading: tx_antennas must be 1 or 2, got {n_ant!r}")
+    if n_ant == 2:
+        if pilots is not None or tx or crc is not None:
+            raise ValueError("transmit diversity (tx_antennas = 2) takes neither pilots, tx nor crc")
+        D.stbc_coh(fading.get("coh", 1))
+        fading = {k: v for k, v in fading.items() if k != "tx_antennas"}
+    elif fading is not None and "tx_antennas" in fading:   # 1: exactly the calls without the key
+        fading = {k: v for k, v in fading.items() if k != "tx_antennas"}
     bps = D.MODULATIONS[mod]["bps"]
     cons = D.constellation(mod)
     rate = codec.k_info / codec.n_coded
@@ -104,6 +122,13 @@ def make_symbols(codec, B, mod, ebn0_db, seed, device, cw0=0, want_info=True, fa
         R = int(R)
         if not 1 <= R <= D.MAX_BRANCHES:
             raise ValueError(f"fading: 1 .. {D.MAX_BRANCHES} branches, got {R}")
+    if n_ant == 2:
+        R, S2 = R or 1, S + (S & 1)
+        syms = torch.empty((B, R, S2), dtype=torch.complex64, device=device)
+        gains = torch.empty((B, R, 2, -(-S2 // coh)), dtype=torch.complex64, device=device)
+        h.call("stbc_workload_dev", int(B), R, cw0, seed, _n.ptr(table), len(cons), bps, sigma, k, coh, _n.ptr(syms),
+               _n.ptr(gains), _n.ptr(info), codec._stream(None))
+        return info, syms, n0, gains
     if pilots is not None:
         if not isinstance(pilots, D.PilotLayout):
             raise TypeError(f"pilots must be a demap.PilotLayout, got {type(pilots)}")
@@ -225,6 +250,12 @@ class DevicePipeline:
     [B, R, T] through the pilot strip on all B * R rows and then the combiner; `z` and
     `nv_sym` are the same buffers, and everything behind them is unchanged.
 
+    Transmit diversity: 4-D csi [B, R, 2, nh] with slots [B, R, S2] selects the
+    Alamouti combiner (demap.stbc_combine_device) in place of the maximal-ratio one; it writes the
+    same `z` and `nv_sym`, so there is nothing further to size and the call is allocation free from
+    the first.  fused=True refuses it as it refuses csi, and run_frames refuses 4-D gains: pilot
+    estimation for two transmit antennas is not built.
+
     llr="int8" | "f16"  models a soft-bit link between demapper and decoder: the
     flat demapper's LLRs (demap.compute_llr_device, decoder sign) are narrowed -- int8 by
     demap.quantize_llr_device with llr_step (default float32(30 / 127)), float16 by rounding -- into
@@ -308,6 +339,8 @@ class DevicePipeline:
         tensor, one value per branch."""
         if syms.dim() == 3 and csi is None:
             raise ValueError("3-D symbols are receive branches: they need their gains (csi=h)")
+        if csi is not None and csi.dim() == 4:
+            return self._run_stbc(syms, noise_var, stream, events, syms_ready, csi, coh)
         if csi is not None:
             if self.fused_asked:
                 raise ValueError("csi needs the two-launch pipeline: the fused demap+decode kernel has no "
@@ -325,7 +358,28 @@ class DevicePipeline:
             front = lambda st: self._front(D.equalize_device, syms, csi, noise_var, coh, st)  # noqa: E731
         return self._run(syms, noise_var, stream, events, syms_ready, front)
 
-    def run_frames(self, frames, layout, noise_var=None, mode="linear", stream=None, events=None):
+    def _run_stbc(self, syms, noise_var, stream, events, syms_ready, csi, coh):
+        """run() for an Alamouti link: slots [n, R, S2] with 4-D gains [n, R, 2, nh] through
+        demap.stbc_combine_device into `z` / `nv_sym`; everything behind them is unchanged."""
+        if self.fused_asked:
+            raise ValueError("csi needs the two-launch pipeline: the fused demap+decode kernel has no "
+                             "per-symbol form (fused=True)")
+        if self.z is None:
+            raise ValueError("csi needs a pipeline built with csi=True")
+        S = self.z.shape[1]
+        if syms.dim() != 3 or syms.shape[0] > self.B or syms.shape[2] != S + (S & 1):
+            raise ValueError(f"4-D gains are two transmit antennas': the slots must be [<= {self.B}, R, {S + (S & 1)}], "
+                             f"got {tuple(syms.shape)}")
+        coh = D.stbc_coh(coh)
+        n = syms.shape[0]
+
+        def front(st):
+            z, nvs = D.stbc_combine_device(syms, csi, noise_var, S=S, coh=coh, out=self.z[:n], nv_out=self.nv_sym[:n],
+                                           stream=st)
+            return z, nvs, self.div_f32_t
+        return self._run(syms, 1.0, stream, events, syms_ready, front)
+
+    def run_frames(self, frames, layout, noise_var=None, mode="linear", stream=None, events=None, csi=None):
         """One batch of framed bursts (demap.PilotLayout): the pilots' channel
         estimate and the equalisation in one launch into `z` / `nv_sym`, the per-symbol
         demap, the decode, all on `stream`.  noise_var: a scalar, a float64 [B] device
@@ -335,7 +389,15 @@ class DevicePipeline:
         3-D `frames` [B, R, T] are R receive branches of each burst: one strip
         launch over the B * R rows (stripped data, interpolated gains and, for noise_var None,
         each branch's own noise estimate), then the combiner; an estimated noise goes in per
-        branch, a scalar or [B] noise_var as the common one."""
+        branch, a scalar or [B] noise_var as the common one.
+
+        csi: refused.  run_frames estimates the gains from the pilots, and for the 4-D gains of two
+        transmit antennas no pilot layout or estimator is built: run() takes those."""
+        if (csi is not None and csi.dim() == 4) or frames.dim() == 4:
+            raise ValueError("run_frames has no pilot estimation for two transmit antennas (4-D gains): pass the "
+                             "known gains to run(slots, nv, csi=h, coh=...)")
+        if csi is not None:
+            raise ValueError("run_frames estimates the gains from the pilots: it takes no csi")
         if self.fused_asked:
             raise ValueError("framed bursts need the two-launch pipeline: the fused demap+decode kernel has no "
                              "per-symbol form (fused=True)")
