@@ -195,6 +195,25 @@ def _declare_stbc(L):
             f.argtypes, f.restype = argtypes[name], i
 
 
+# every symbol include/sm.h declares (spatial multiplexing): built into
+# libtdec.so, kept apart as STBC_EXPORTS is
+SM_EXPORTS = ("sm_detect_dev", "sm_workload_dev")
+
+
+def _declare_sm(L):
+    """argtypes and restype of include/sm.h's exports; a library that lacks them (an older
+    build loaded by the A/B tools) is left as it is, and a call then fails by name."""
+    i, d, p, q, Q, l = C.c_int, C.c_double, _vp, C.c_int64, C.c_uint64, C.c_long
+    argtypes = {
+        "sm_detect_dev": [i, p, p, i, i, i, i, p, i, i, d, p, p, i, p, l, p],
+        "sm_workload_dev": [p, i, i, q, Q, p, i, i, d, d, i, p, p, p, p],
+    }
+    for name in SM_EXPORTS:
+        if hasattr(L, name):
+            f = getattr(L, name)
+            f.argtypes, f.restype = argtypes[name], i
+
+
 def lib():
     """Load libtdec.so (building it first if this is a build tree without it)."""
     global _lib
@@ -210,6 +229,7 @@ def lib():
                 _declare_crc(L)
                 _declare_llrq(L)
                 _declare_stbc(L)
+                _declare_sm(L)
                 _lib = L
     return _lib
 

@@ -42,6 +42,13 @@ pairs of slots in front of the demapper; with --llr, --demap and --early-stop as
 --coherence counts slots and must be even.  Eb/N0 is per receive branch at fixed total transmit
 power: the two antennas share it.  Recorded in the sweep configuration only when 2.
 
+--tx-antennas 2 --tx-mode sm multiplexes instead: the two antennas send two
+different symbols in every slot and the R = --rx-branches branches are detected jointly (max-log
+over the M^2 hypotheses of a slot; up to 64QAM); with --llr and --early-stop as without it,
+--coherence counts slots and may be odd.  Eb/N0 is per receive branch at fixed total transmit
+power, as for the block code; the doubled rate is not charged.  Recorded in the sweep
+configuration only when sm.
+
 --harq chase | ir with --max-tx T sends a codeword again while its decode is
 wrong, up to T transmissions, and soft-combines them (workload.HarqPipeline): chase repeats
 the --rate pattern, ir cycles through its redundancy versions into a rate-1/3 decoder.  The
@@ -111,6 +118,8 @@ def sweep_config(a, inv_perm=None):
             cfg["rx_branches"] = fading["branches"]
         if "tx_antennas" in fading:   # (absent for one antenna, likewise)
             cfg["tx_antennas"] = fading["tx_antennas"]
+        if sm_mode(a):   # (absent for the block code: files of earlier sweeps keep resuming)
+            cfg.update(tx_antennas=2, tx_mode="sm")
     if getattr(a, "harq", None):   # (absent without the flag, likewise)
         cfg.update(harq=a.harq, max_tx=int(a.max_tx))
     if getattr(a, "crc", None):   # (absent without the flag, likewise)
@@ -135,16 +144,22 @@ def llr_step_of(a):
     return float(LLRQ_DEFAULT_STEP if step is None else np.float32(step))
 
 
+def sm_mode(a):
+    """Whether the sweep multiplexes its two transmit antennas (--tx-antennas 2 --tx-mode sm)."""
+    return int(getattr(a, "tx_antennas", 1)) == 2 and getattr(a, "tx_mode", "stbc") == "sm"
+
+
 def channel_fading(a):
     """workload.make_symbols' `fading` for the sweep's --channel (None: awgn).  rayleigh is
-    rician with K = 0, whatever --rician-k says."""
+    rician with K = 0, whatever --rician-k says.  A multiplexed link (sm_mode) goes without the
+    "tx_antennas" key: make_symbols takes it as streams=2."""
     channel = getattr(a, "channel", "awgn")
     if channel == "awgn":
         return None
     fading = {"K": float(a.rician_k) if channel == "rician" else 0.0, "coh": int(a.coherence)}
     if int(getattr(a, "rx_branches", 1)) > 1:   # (one branch is the call without the key: the same data)
         fading["branches"] = int(a.rx_branches)
-    if int(getattr(a, "tx_antennas", 1)) == 2:   # (one antenna is the call without the key, likewise)
+    if int(getattr(a, "tx_antennas", 1)) == 2 and not sm_mode(a):   # (one antenna is the call without the key, likewise)
         fading["tx_antennas"] = 2
     return fading
 
@@ -199,7 +214,7 @@ def frame_check_counts(bits, info, kind, ok=None):
 
 
 def run_point(pipe, codec, mod, ebn0, start, count, batch, seed, device, times=None, iter_hist=None, fading=None,
-              pilots=None, crc=None):
+              pilots=None, crc=None, sm=False):
     """Bit errors, frame errors and codewords of global codewords
     [start, start + count) at one Eb/N0 point.  The data of codeword g is a
     counter-based stream of (seed, g) (workload.make_symbols), so the counters
@@ -214,7 +229,8 @@ def run_point(pipe, codec, mod, ebn0, start, count, batch, seed, device, times=N
     bursts are framed and the pipeline estimates the gains (and the noise) from the pilots.
     fading["branches"] = R: symbols, gains and frames are [n, R, ...] and the pipeline combines.
     crc (a kind, optional; neither pilots nor branches): the codewords carry a check field and the
-    counters are frame_check_counts' five."""
+    counters are frame_check_counts' five.  sm (with fading; neither pilots nor crc): the link is
+    spatially multiplexed (make_symbols' streams=2) and the pipeline, built with sm=True, detects jointly."""
     import torch
     from . import sharding as S
     from .workload import count_errors, make_symbols
@@ -229,6 +245,9 @@ def run_point(pipe, codec, mod, ebn0, start, count, batch, seed, device, times=N
                 csi = {"csi": gains[0], "coh": fading["coh"]}
         elif fading is None:
             _, syms, n0 = make_symbols(codec, n, mod, ebn0, seed, device, cw0=start + off, want_info=False)
+        elif sm:
+            _, syms, n0, gains = make_symbols(codec, n, mod, ebn0, seed, device, cw0=start + off, want_info=False,
+                                              fading=fading, streams=2)
         elif pilots is not None:
             _, syms, n0, _ = make_symbols(codec, n, mod, ebn0, seed, device, cw0=start + off, want_info=False,
                                           fading=fading, pilots=pilots["layout"], cfo=pilots["cfo"])
@@ -238,7 +257,9 @@ def run_point(pipe, codec, mod, ebn0, start, count, batch, seed, device, times=N
             csi = {"csi": gains, "coh": fading["coh"]}
         e3 = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
         e3[0].record()
-        if pilots is not None:
+        if sm:
+            bits = pipe.run_sm(syms, n0, gains, coh=fading["coh"], events=e3[1:])[:n]
+        elif pilots is not None:
             bits = pipe.run_frames(syms, pilots["layout"], n0 if pilots["noise"] == "known" else None,
                                    events=e3[1:])[:n]
         else:
@@ -352,6 +373,11 @@ def arg_parser():
                     help="fading channels, --csi known: transmit antennas (1 or 2).  2 sends every codeword with the "
                          "Alamouti space-time block code (DESIGN.md §18); --coherence then counts slots and must be "
                          "even.  Eb/N0 is per receive branch at fixed total transmit power: the antennas share it")
+    ap.add_argument("--tx-mode", choices=["stbc", "sm"], default="stbc",
+                    help="--tx-antennas 2: stbc (the default) sends the Alamouti block code, one symbol per slot; sm "
+                         "multiplexes, two symbols per slot, detected jointly over the receive branches (max-log, up "
+                         "to 64QAM; DESIGN.md §19); --coherence then counts slots and may be odd.  Eb/N0 stays per "
+                         "receive branch at fixed total transmit power: the doubled rate is not charged")
     ap.add_argument("--harq", choices=["chase", "ir"], default=None,
                     help="hybrid ARQ with a genie-aided ACK: resend a codeword while its decode is wrong and "
                          "soft-combine; chase repeats the pattern, ir cycles its redundancy versions into a "
@@ -408,8 +434,15 @@ def main(argv=None):
             ap.error("--tx-antennas 2 needs --channel rayleigh or rician and --csi known")
         if a.harq or a.crc:
             ap.error("--tx-antennas 2 takes neither --harq nor --crc")
-        if a.coherence < 2 or a.coherence % 2:
+        if a.tx_mode == "sm":
+            if a.demap != "max-log":
+                ap.error("--tx-mode sm detects jointly with max-log only: it takes no --demap log-map")
+            if a.mod == "256QAM":
+                ap.error("--tx-mode sm detects up to 64QAM jointly")
+        elif a.coherence < 2 or a.coherence % 2:
             ap.error("--tx-antennas 2 needs an even --coherence (a pair of slots shares its gains)")
+    if a.tx_mode == "sm" and a.tx_antennas != 2:
+        ap.error("--tx-mode sm needs --tx-antennas 2")
     if a.llr_step is not None and (a.llr != "int8" or not 0.0 < a.llr_step < float("inf")):
         ap.error("--llr-step goes with --llr int8 and must be a finite value > 0")
     fading = channel_fading(a)
@@ -467,12 +500,12 @@ def main(argv=None):
                        torch.zeros(a.max_tx + 1, dtype=torch.int64, device=device), fading=fading, crc=a.crc,
                        ack=a.ack or "genie")
     else:
-        pipe = DevicePipeline(codec, a.mod, a.batch, device, demap=a.demap, csi=fading is not None, llr=a.llr,
-                              llr_step=a.llr_step)
+        pipe = DevicePipeline(codec, a.mod, a.batch, device, demap=a.demap, csi=fading is not None and not sm_mode(a),
+                              llr=a.llr, llr_step=a.llr_step, sm=sm_mode(a))
         # one untimed batch first: code-object loading and first-launch costs stay out of
         # the first point's figures
         run_point(pipe, codec, a.mod, 2.0, 0, min(a.batch, 65536), a.batch, a.seed, device, fading=fading,
-                  pilots=pilots, crc=a.crc)
+                  pilots=pilots, crc=a.crc, sm=sm_mode(a))
     for e in parse_points(a.ebn0):
         if e in done:
             continue
@@ -486,7 +519,7 @@ def main(argv=None):
                                  fading=fading, crc=a.crc, ack=a.ack or "genie")
         else:
             cnt = run_point(pipe, codec, a.mod, e, start, count, a.batch, ebn0_seed(a.seed, e), device, times, hist,
-                            fading=fading, pilots=pilots, crc=a.crc)
+                            fading=fading, pilots=pilots, crc=a.crc, sm=sm_mode(a))
         nc = 5 if a.crc else 3   # the error counters in front of the histogram
         if hist is not None:
             cnt = torch.cat([cnt, hist])   # one reduction for the error counters and the histogram
@@ -515,6 +548,8 @@ def main(argv=None):
                 rec["rx_branches"] = fading["branches"]
             if "tx_antennas" in fading:
                 rec["tx_antennas"] = fading["tx_antennas"]
+            if sm_mode(a):
+                rec.update(tx_antennas=2, tx_mode="sm")
         if pilots is not None:
             rec.update(csi="pilots", pilot_len=a.pilot_len, pilot_spacing=a.pilot_spacing, cfo=a.cfo,
                        csi_noise=a.csi_noise)

@@ -21,7 +21,7 @@ SRC = os.path.join(HERE, "csrc", "tdec_api.hip")
 DEPS = [*sorted(glob.glob(os.path.join(HERE, "csrc", "tdec_*.hip"))), os.path.join(HERE, "csrc", "npmath.hip"),
         os.path.join(ROOT, "include", "tdec.h"), os.path.join(ROOT, "include", "harq.h"),
         os.path.join(ROOT, "include", "crc.h"), os.path.join(ROOT, "include", "llrq.h"),
-        os.path.join(ROOT, "include", "stbc.h")]
+        os.path.join(ROOT, "include", "stbc.h"), os.path.join(ROOT, "include", "sm.h")]
 OUT = os.path.join(HERE, "lib", "libtdec.so")
 MODEM_SRC = os.path.join(HERE, "csrc", "modem_api.hip")
 MODEM_DEPS = [MODEM_SRC, os.path.join(HERE, "csrc", "modem_kernels.hip"), os.path.join(HERE, "csrc", "npmath.hip"),

@@ -7,8 +7,8 @@
 // One translation unit: the kernel files, the kernel-order manifest, the handle and the
 // decoder's entry points here, the soft demapper's host code in tdec_demap_api.hip, then
 // the self-tests, the workload generators, hybrid ARQ's host code (tdec_harq.hip), the
-// frame check's (tdec_crc_api.hip), the quantised LLRs' (tdec_llrq_api.hip) and transmit
-// diversity's (tdec_stbc_api.hip).
+// frame check's (tdec_crc_api.hip), the quantised LLRs' (tdec_llrq_api.hip), transmit
+// diversity's (tdec_stbc_api.hip) and spatial multiplexing's (tdec_sm_api.hip).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -31,6 +31,7 @@
 #include "tdec_crc.hip"
 #include "tdec_llrq.hip"
 #include "tdec_stbc.hip"
+#include "tdec_sm.hip"
 
 using namespace tdec;
 
@@ -84,6 +85,10 @@ namespace {
     (void)k_stbc_combine<0, true>, (void)k_stbc_combine<0, false>, (void)k_stbc_combine<1, true>,
         (void)k_stbc_combine<1, false>, (void)k_stbc_combine<2, true>, (void)k_stbc_combine<2, false>,
         (void)k_workload_faded<StbcArgs>;                                                          // transmit diversity (§18)
+#define SM_EACH_NV(M) (void)k_sm_detect<M, 0>, (void)k_sm_detect<M, 1>, (void)k_sm_detect<M, 2>
+    SM_EACH_NV(2), SM_EACH_NV(4), SM_EACH_NV(8), SM_EACH_NV(16), SM_EACH_NV(32), SM_EACH_NV(64),
+        (void)k_workload_faded<SmArgs>;                                                            // spatial multiplexing (§19)
+#undef SM_EACH_NV
 }
 #undef EACH_BPS
 #undef BOTH
@@ -2202,3 +2207,6 @@ int tdec_encode_dev(tdec_t *h, int B, const uint8_t *d_bits, uint8_t *d_coded, v
 
 // ---- transmit diversity: the Alamouti combiner and the generator's 2 x R link (include/stbc.h) ----
 #include "tdec_stbc_api.hip"
+
+// ---- spatial multiplexing: the joint detector and the generator's multiplexed 2 x R link (include/sm.h) ----
+#include "tdec_sm_api.hip"

@@ -204,6 +204,11 @@ struct TxArgs : FadeArgs {
 struct StbcArgs : FadeArgs {
     int R, S2;
 };
+// SmArgs (include/sm.h): the multiplexed 2 x R link.  syms rows [B][R] of T = ceil(S / 2)
+// slots, h rows [B][R][2] of nh = ceil(T / coh) gains, coh >= 1 in slots
+struct SmArgs : FadeArgs {
+    int R, T;
+};
 constexpr uint32_t FADE1_DOMAIN = 0x6F8Au;      // antenna 1's gains (antenna 0's: FADE_DOMAIN, the branch generator's)
 __device__ __forceinline__ float2 fade_gain(uint64_t cw, long j, uint64_t seed, const FadeArgs &f,
                                             uint32_t domain = FADE_DOMAIN) {
@@ -270,6 +275,35 @@ __device__ __forceinline__ void flush_stbc(const WorkloadArgs &p, const StbcArgs
     }
 }
 
+// The multiplexed link's flush (SmArgs): the chunk's pairs (x[2m], x[2m+1]), one slot per item, consecutive
+// lanes on consecutive slots of one codeword (s0 is even, as above; the last pair of an odd S sends 0 from
+// antenna 1).  Per branch b: the Alamouti link's effective gains of block m / coh, written by the block's
+// first slot, and slot m = h0 x[2m] + h1 x[2m+1] in stbc_slot's order plus branch b's noise sample at
+// symbol index m.
+__device__ __forceinline__ void flush_sm(const WorkloadArgs &p, const SmArgs &f, long base, uint8_t (*lab)[64],
+                                         const float2 *cons, int ns, long s0, int lane) {
+    const int np = (ns + 1) >> 1;
+    for (int t = lane; t < 64 * np; t += 64) {
+        const int l = t / np, k = 2 * (t - l * np);
+        if (base + l >= p.B) continue;
+        const uint64_t cw = p.cw0 + (uint64_t)(base + l);
+        const float2 x0 = cons[lab[k][l]], x1 = k + 1 < ns ? cons[lab[k + 1][l]] : make_float2(0.0f, 0.0f);
+        const long m = (s0 + k) >> 1, j = m / f.coh;
+        for (int b = 0; b < f.R; ++b) {
+            const uint32_t tag = (uint32_t)b << 16;
+            const long row = (base + l) * f.R + b;
+            float2 g0 = fade_gain(cw, j, p.seed, f, FADE_DOMAIN | tag), g1 = fade_gain(cw, j, p.seed, f, FADE1_DOMAIN | tag);
+            g0 = make_float2(g0.x * 0.70710678118654752f, g0.y * 0.70710678118654752f);
+            g1 = make_float2(g1.x * 0.70710678118654752f, g1.y * 0.70710678118654752f);
+            if (m == j * f.coh) {
+                f.h[(row * 2 + 0) * f.nh + j] = g0;
+                f.h[(row * 2 + 1) * f.nh + j] = g1;
+            }
+            p.syms[row * f.T + m] = stbc_slot(g0, x0, g1, x1, awgn(cw, m, p, NOISE_DOMAIN | tag));
+        }
+    }
+}
+
 // Row-order flush of a chunk of symbol labels lab[k][lane] (k < ns): symbols
 // [s0, s0 + ns) of every codeword, table point + AWGN, complex64.  FADE: h x + AWGN, and
 // the first symbol of each gain block writes its gain.  F = BranchArgs: f.R independently faded
@@ -280,6 +314,11 @@ __device__ __forceinline__ void flush_syms(const WorkloadArgs &p, const F &f, lo
     __syncthreads();
     if constexpr (std::is_same<F, StbcArgs>::value) {
         flush_stbc(p, f, base, lab, cons, ns, s0, lane);
+        __syncthreads();
+        return;
+    }
+    if constexpr (std::is_same<F, SmArgs>::value) {
+        flush_sm(p, f, base, lab, cons, ns, s0, lane);
         __syncthreads();
         return;
     }

@@ -332,6 +332,83 @@ def stbc_combine_device(y, h, noise_var, S=None, coh=2, out=None, nv_out=None, s
     return out, nv_out
 
 
+SM_MAX_ORDER = 64                                     # the joint detector searches M^2 hypotheses per slot
+
+
+def sm_order(mod_type):
+    """(constellation, bps) of a modulation the joint detector takes: up to 64 points."""
+    m = MODULATIONS[mod_type]
+    if m['order'] > SM_MAX_ORDER:
+        raise ValueError(f"spatial multiplexing detects up to {SM_MAX_ORDER}-point constellations jointly, "
+                         f"not {mod_type}")
+    return _cons(mod_type), m['bps']
+
+
+def sm_detect_device(y, h, mod_type, noise_var, S=None, coh=1, out=None, sign=+1, stream=None):
+    """2 x R joint max-log detector of a spatially multiplexed link (DESIGN.md section 19,
+    include/sm.h): complex64 [B, R, T] device slots, slot m carrying x[2m] from antenna 0 and
+    x[2m+1] from antenna 1 through the known effective gains h[b, r, 0] and h[b, r, 1], complex64
+    [B, R, 2, ceil(T / coh)] -> float32 [B, S * bps] LLRs, symbol s, bit j at s * bps + j, clipped
+    to +-30, stream-ordered.  S: the codeword's symbols, 2 T or (an odd S, passed explicitly)
+    2 T - 1: antenna 1 is then silent in the last slot.  noise_var: a scalar, a float64 [B] or a
+    float64 [B, R] device tensor, floored at 0.005 on the device.  sign as compute_llr's (-1: the
+    decoder's).  out: a float32 [B, S * bps] tensor, or a [B, >= S * bps] view of rows whose
+    elements are contiguous (a column slice of a wider buffer: its row stride is passed on).
+    max-log only; 256QAM is refused."""
+    import torch
+    cons, bps = sm_order(mod_type)
+    for t, n in ((y, "y"), (h, "h")):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.complex64:
+            raise TypeError(f"{n} must be a torch.complex64 tensor, got {getattr(t, 'dtype', type(t))}")
+    if y.dim() != 3:
+        raise ValueError("y must be a 3-D [B, R, T] tensor (one slot per pair of symbols)")
+    if y.device.type != "cuda" or not y.is_contiguous():
+        raise ValueError("y must be a contiguous 3-D [B, R, T] tensor on a HIP device")
+    B, R, T = y.shape
+    if not 1 <= R <= MAX_BRANCHES:
+        raise ValueError(f"1 .. {MAX_BRANCHES} branches, got {R}")
+    coh = int(coh)
+    if coh < 1:
+        raise ValueError("coh must be >= 1")
+    S = 2 * T if S is None else int(S)
+    if S < 0 or S not in (2 * T, 2 * T - 1):
+        raise ValueError(f"S must be 2 T = {2 * T} or the odd 2 T - 1, got {S}")
+    want = (B, R, 2, -(-T // coh))
+    if h.dim() != 4 or tuple(h.shape) != want or not h.is_contiguous() or h.device != y.device:
+        raise ValueError(f"h must be a contiguous 4-D tensor of shape {want} on the symbols' device, "
+                         f"got {tuple(h.shape)}")
+    rows = branches = None
+    if isinstance(noise_var, torch.Tensor):
+        if noise_var.dtype != torch.float64:
+            raise TypeError(f"noise_var must be torch.float64, got {noise_var.dtype}")
+        if tuple(noise_var.shape) not in ((B,), (B, R)) or not noise_var.is_contiguous():
+            raise ValueError(f"noise_var must be a contiguous tensor of shape ({B},) or ({B}, {R}), "
+                             f"got {tuple(noise_var.shape)}")
+        if noise_var.device != y.device:
+            raise ValueError("noise_var must be on the symbols' HIP device")
+        if noise_var.dim() == 2:
+            branches = noise_var
+        else:
+            rows = noise_var
+    if sign not in (1, -1):
+        raise ValueError(f"sign must be +1 or -1, got {sign!r}")
+    L = S * bps
+    if out is None:
+        out = torch.empty((B, L), dtype=torch.float32, device=y.device)
+    if (not isinstance(out, torch.Tensor) or out.dtype != torch.float32 or out.dim() != 2 or tuple(out.shape) != (B, L)
+            or out.device != y.device or (L > 1 and out.stride(1) != 1) or (B > 1 and out.stride(0) < L)):
+        raise ValueError(f"out must be a float32 tensor of shape ({B}, {L}) on the input's device whose rows are "
+                         "contiguous")
+    stride = out.stride(0) if B > 1 else L
+    c = np.ascontiguousarray(cons)
+    dev = y.device.index or 0
+    _n.check(_n.lib().sm_detect_dev(dev, _n.ptr(y), _n.ptr(h), B, R, S, coh, _n.ptr(c), int(c.dtype == np.complex128),
+                                    len(c), 0.0 if isinstance(noise_var, torch.Tensor) else float(noise_var),
+                                    _n.ptr(rows), _n.ptr(branches), int(sign), _n.ptr(out), int(stride),
+                                    _stream_of(dev, stream)))
+    return out
+
+
 def estimate_noise_var_device(syms, mod_type, floor=0.02, out=None, stream=None):
     """The receiver's decision-directed noise variance (test_sdr_with_coding.py:459-467:
     hard decision, re-map, mean |rx - const|^2, max(nv, 0.02)) of each row of complex64

@@ -18,7 +18,7 @@ def noise_n0(constellation, rate, bps, ebn0_db):
 
 
 def make_symbols(codec, B, mod, ebn0_db, seed, device, cw0=0, want_info=True, fading=None, pilots=None, cfo=0.0,
-                 tx=0, crc=None):
+                 tx=0, crc=None, streams=1):
     """(info uint8 [B, 2N] or None, received symbols complex64 [B, S], N0) on `device`.
 
     One launch of the counter-based generator (tdec_workload_dev): Philox info
@@ -66,9 +66,25 @@ def make_symbols(codec, B, mod, ebn0_db, seed, device, cw0=0, want_info=True, fa
     [B, R, S2], N0, h complex64 [B, R, 2, ceil(S2 / coh)]), S2 = S + (S & 1), 3-D / 4-D for one
     branch as well; h holds the effective gains, E|h|^2 = 1/2 each: the two antennas share the
     transmit power, so ebn0_db is per receive branch at fixed total transmit power.  Neither
-    `pilots`, `tx` nor `crc`.  "tx_antennas" absent or 1 is the calls above."""
+    `pilots`, `tx` nor `crc`.  "tx_antennas" absent or 1 is the calls above.
+
+    streams=2 (with `fading`): spatial multiplexing.  Slot m carries x[2m] from
+    antenna 0 and x[2m+1] from antenna 1 (sm_workload_dev), received on "branches" (default 1)
+    branches; "coh" counts slots, any value >= 1.  The result is (info, slots complex64 [B, R, T],
+    N0, h complex64 [B, R, 2, ceil(T / coh)]), T = ceil(S / 2), the gains those of the Alamouti
+    link (effective, E|h|^2 = 1/2 each), the silent antenna of an odd S sending 0.  Neither `pilots`,
+    `tx`, `crc` nor "tx_antennas": 2.  streams=1 (default) is the calls above."""
     import torch
     from . import _native as _n
+    if streams not in (1, 2) or isinstance(streams, bool):
+        raise ValueError(f"streams must be 1 or 2, got {streams!r}")
+    if streams == 2:
+        if fading is None:
+            raise ValueError("spatial multiplexing (streams = 2) needs a fading channel: pass fading={...}")
+        if pilots is not None or tx or crc is not None or fading.get("tx_antennas", 1) == 2:
+            raise ValueError("spatial multiplexing (streams = 2) takes neither pilots, tx, crc nor "
+                             "fading['tx_antennas'] = 2")
+        D.sm_order(mod)
     n_ant = 1 if fading is None else fading.get("tx_antennas", 1)
     if n_ant not in (1, 2) or isinstance(n_ant, bool):
         raise ValueError(f"fading: tx_antennas must be 1 or 2, got {n_ant!r}")
@@ -122,6 +138,13 @@ def make_symbols(codec, B, mod, ebn0_db, seed, device, cw0=0, want_info=True, fa
         R = int(R)
         if not 1 <= R <= D.MAX_BRANCHES:
             raise ValueError(f"fading: 1 .. {D.MAX_BRANCHES} branches, got {R}")
+    if streams == 2:
+        R, T = R or 1, (S + 1) // 2
+        syms = torch.empty((B, R, T), dtype=torch.complex64, device=device)
+        gains = torch.empty((B, R, 2, -(-T // coh)), dtype=torch.complex64, device=device)
+        h.call("sm_workload_dev", int(B), R, cw0, seed, _n.ptr(table), len(cons), bps, sigma, k, coh, _n.ptr(syms),
+               _n.ptr(gains), _n.ptr(info), codec._stream(None))
+        return info, syms, n0, gains
     if n_ant == 2:
         R, S2 = R or 1, S + (S & 1)
         syms = torch.empty((B, R, S2), dtype=torch.complex64, device=device)
@@ -261,13 +284,27 @@ class DevicePipeline:
     demap.quantize_llr_device with llr_step (default float32(30 / 127)), float16 by rounding -- into
     `llr_q`, and the narrow rows de-punctured into the planes (codec.depuncture_device).  The plane
     demappers have no flat LLRs: fused=True and overlap=True refuse it, as fused refuses csi.
-    llr="f32" (default) is the pipeline above, unchanged."""
+    llr="f32" (default) is the pipeline above, unchanged.
+
+    sm=True sizes one float32 [B, S * bps] buffer `llr_sm` for the joint detector of a
+    spatially multiplexed 2 x R link, and run_sm(slots, noise_var, h, coh) runs detect
+    (demap.sm_detect_device, decoder sign) -> the llr= narrowing, if any -> codec.depuncture_device ->
+    decode.  The detector is max-log and has no plane form: fused=True, overlap=True and
+    demap="log-map" are refused.  run() and run_frames() are untouched: with llr="int8" | "f16" the
+    pipeline still holds the flat demapper's float64 buffer `llr`, which run() narrows from and
+    run_sm() (its LLRs are float32 already) does not use."""
 
     def __init__(self, codec, mod, B, device, fused=False, overlap=False, gate=True, demap="max-log", csi=False,
-                 llr="f32", llr_step=None):
+                 llr="f32", llr_step=None, sm=False):
         import torch
         self.codec, self.mod, self.B = codec, mod, B
         self.llr_kind, self.llr_step = _llr_link(llr, llr_step)
+        self.sm = bool(sm)
+        if self.sm:
+            if fused or overlap or demap != "max-log":
+                raise ValueError("sm=True detects jointly into flat max-log LLRs: it takes neither fused=True, "
+                                 "overlap=True nor demap='log-map'")
+            D.sm_order(mod)
         if self.llr_kind is not None and (fused or overlap):
             raise ValueError(f"llr={llr!r} needs the flat demapper's LLRs: the plane demappers of fused=True and "
                              "overlap=True have none")
@@ -294,6 +331,10 @@ class DevicePipeline:
         if self.llr_kind is not None:
             self.llr, self.llr_q = _llr_link_buffers(self.llr_kind, B * -(-codec.handle.enc_len // self.bps) * self.bps,
                                                      device)
+        self.llr_sm = None
+        if self.sm:
+            self.llr_sm = torch.empty((B, -(-codec.handle.enc_len // self.bps) * self.bps), dtype=torch.float32,
+                                      device=device)
         self.z = self.nv_sym = None
         self._strip = {}                          # run_frames' per-branch buffers, by R (sized on first use)
         if csi:
@@ -357,6 +398,41 @@ class DevicePipeline:
         if csi is not None:
             front = lambda st: self._front(D.equalize_device, syms, csi, noise_var, coh, st)  # noqa: E731
         return self._run(syms, noise_var, stream, events, syms_ready, front)
+
+    def run_sm(self, y, noise_var, h, coh=1, stream=None, events=None):
+        """One batch of a spatially multiplexed link: slots complex64 [n <= B, R, T],
+        T = ceil(S / 2), with the known effective gains h complex64 [n, R, 2, ceil(T / coh)] -> the joint
+        detector's decoder-sign LLRs into `llr_sm` -> (llr="int8" | "f16": narrowed into `llr_q`) ->
+        the de-puncture kernel -> the decode, all on `stream`.  noise_var: a scalar, a float64 [n] or a
+        float64 [n, R] device tensor.  Allocation free; returns the bits (a view of `bits`), and with
+        an early-stop codec `n_iter` holds the iterations, as after run()."""
+        import torch
+        if not self.sm:
+            raise ValueError("run_sm needs a pipeline built with sm=True")
+        L = self.llr_sm.shape[1]
+        S = L // self.bps
+        if not isinstance(y, torch.Tensor) or y.dim() != 3 or y.shape[0] > self.B or y.shape[2] != (S + 1) // 2:
+            raise ValueError(f"the slots must be [<= {self.B}, R, {(S + 1) // 2}], got {tuple(getattr(y, 'shape', ()))}")
+        n = y.shape[0]
+        llr = D.sm_detect_device(y, h, self.mod, noise_var, S=S, coh=coh, out=self.llr_sm[:n], sign=-1, stream=stream)
+        if self.llr_kind == "int8":
+            q = self.llr_q[:n * L].view(n, L)
+            D.quantize_llr_device(llr, self.llr_step, out=q, stream=stream)
+            llr = q
+        elif self.llr_kind == "f16":
+            q = self.llr_q[:n * L].view(n, L)
+            with torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream(y.device)):
+                q.copy_(llr)   # float32 -> float16, round to nearest even
+            llr = q
+        self.codec.depuncture_device(llr, self.planes, stream=stream, llr_step=self.llr_step)
+        if events is not None:
+            events[0].record(stream)
+        bits = self.bits[:n]
+        es = {"n_iter": self.n_iter[:n]} if self.early_stop else {}
+        self.codec.decode_planes_device(self.planes, n, bits, stream=stream, **es)
+        if events is not None:
+            events[1].record(stream)
+        return bits
 
     def _run_stbc(self, syms, noise_var, stream, events, syms_ready, csi, coh):
         """run() for an Alamouti link: slots [n, R, S2] with 4-D gains [n, R, 2, nh] through
